@@ -4,6 +4,7 @@ bf16 HIP path, one training step = forward + cross-entropy + backward (+ gradien
 all-reduce for N > 1) + SGD update, on N GPUs of one node (one process per GPU, RCCL).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--frames T] [--stream bf16|fp32|fp32+grad]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no torchrun environment re-launches itself under
@@ -11,14 +12,23 @@ torch.distributed.run with N ranks (one per GPU, rendezvous on 127.0.0.1); if th
 than N GPUs it says so on stderr and runs on the GPUs that exist (`n_gpus` reports the real count).
 
 Prints ONE JSON line on rank 0.  `value` = clips/s over all N GPUs with clips already resident in
-HBM.  `roofline` is for the dominant kernel class (all vtx_gemm_nt launches): achieved =
-algorithmic FLOPs (2*M*N*K per launch) / launch time measured with HIP events on the launch stream
-inside the timed region, against the 2.5 PFLOP/s dense bf16 MFMA peak.  After the timed region a
-short instrumented pass (not part of `value`) times every kernel class the same way:
-`gemm_shapes` (each GEMM shape of the step with its own algorithmic bytes, bound and fraction of
-that bound) and `roofline_hbm` (LayerNorm, attention cores, patch gather, HOG against 8 TB/s).
-`cpu_baseline` times the CPU oracle (oracle/, fp32, the host cores this process may use) on a
-bounded sample of the same workload -- a reported baseline only.
+HBM; `ms_per_step` = wall time of one timed step.  `roofline` is for the dominant kernel class (all
+vtx_gemm_nt launches): achieved = algorithmic FLOPs (2*M*N*K per launch) / launch time measured with
+HIP events on the launch stream inside the timed region, against the 2.5 PFLOP/s dense bf16 MFMA peak.
+
+A plain run does only that: set up, warm up, time `--steps` steps, print the line.  `--full` adds what
+takes runs of its own, all after the timed region and never part of `value`: a short instrumented pass
+that times every kernel class the same way -- `gemm_shapes` (each GEMM shape of the step with its own
+algorithmic bytes, bound and fraction of that bound) and `roofline_hbm` (LayerNorm, attention cores,
+patch gather, HOG against 8 TB/s); `other_configs` (5-step mini-runs of the other shapes and stream
+modes); `cpu_baseline`, the CPU oracle (oracle/, fp32, the host cores this process may use) on a
+bounded sample of the same workload -- a reported baseline only.  --no-breakdown / --no-other-configs /
+--no-cpu-baseline drop one of them from a --full run.
+
+`--dump-outputs DIR` writes what the last timed step computed, on rank 0, right after the timed region:
+loss.npy (the scalar loss), logits.npy (the classifier's [batch, 400] logits), and a fixed seeded sample
+of every parameter after the optimizer update (params_sample.npy) and of its gradient (grads_sample.npy),
+all float32 (a few MB).  Inputs and weights are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -52,10 +62,16 @@ def parse():
     ap.add_argument('--precision', default='bf16', choices=['bf16', 'fp32'])
     ap.add_argument('--stream', default='bf16', choices=['bf16', 'fp32', 'fp32+grad'],
                     help="residual stream of the bf16 path: bf16 (default, the headline), fp32 = vtx.set_stream('fp32'), the exact stream, or fp32+grad = its gradient in float32 too (DESIGN.md 3)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-breakdown', action='store_true', help='skip the instrumented per-kernel-class pass')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region also run the instrumented per-kernel-class pass, the other configurations and the '
+                         'CPU baseline (each can be dropped again with its --no-* switch); a plain run measures the headline only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the outputs of the last timed step as DIR/<name>.npy (float32): loss, logits, seeded samples of the '
+                         'updated parameters and of their gradients')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full: skip the CPU baseline')
+    ap.add_argument('--no-breakdown', action='store_true', help='--full: skip the instrumented per-kernel-class pass')
     ap.add_argument('--no-other-configs', action='store_true',
-                    help="skip the 5-step mini-runs of north_star's other shapes after the timed region (other_configs in the JSON line)")
+                    help="--full: skip the 5-step mini-runs of north_star's other shapes after the timed region (other_configs in the JSON line)")
     ap.add_argument('--no-optimizer', action='store_true')
     ap.add_argument('--no-direct-grads', action='store_true',
                     help='parameter gradients through autograd accumulation instead of straight into the buckets')
@@ -185,6 +201,45 @@ def pmc_mfma_busy(B, args):
         return None
     out['source'] = 'replayed: ' + os.path.relpath(path, here)
     return out
+
+
+def library_up_to_date():
+    """build.py's own rule, applied without writing anything: libvtx.so exists, every object is newer than its source and the
+    headers / flags, and the library is not older than any object.  A tree that build() has already built may belong to another
+    user and be read-only here, and build() takes a lock file under csrc/_obj/ even when there is nothing to do."""
+    sys.path.insert(0, os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc'))
+    import build as vtx_build
+    if not os.path.isfile(vtx_build.OUT):
+        return False
+    deps = vtx_build._deps()
+    newest_obj = 0.0
+    for src in vtx_build.SOURCES:
+        obj = os.path.join(vtx_build.OBJ, src.replace('.hip', '.o'))
+        if not os.path.isfile(obj) or os.path.getmtime(obj) <= max(os.path.getmtime(os.path.join(vtx_build.HERE, src)), deps):
+            return False
+        newest_obj = max(newest_obj, os.path.getmtime(obj))
+    return os.path.getmtime(vtx_build.OUT) >= newest_obj
+
+
+DUMP_SAMPLE_PER_TENSOR = 4096      # --dump-outputs: elements drawn from every larger parameter / gradient
+
+
+def dump_outputs(out_dir, loss, logits, params):
+    """The last timed step's results as float32 .npy files (see the module docstring).  The sample positions depend only on the
+    parameter shapes (a CPU generator with a fixed seed), so two builds of the project dump the same elements."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator(device='cpu').manual_seed(20241016)
+    ps, gs = [], []
+    for p in params:
+        n = p.numel()
+        idx = torch.arange(n) if n <= DUMP_SAMPLE_PER_TENSOR else torch.randint(0, n, (DUMP_SAMPLE_PER_TENSOR,), generator=g)
+        idx = idx.to(p.device)
+        ps.append(p.detach().reshape(-1)[idx].float())
+        gs.append(p.grad.detach().reshape(-1)[idx].float() if p.grad is not None else torch.full((len(idx),), float('nan'), device=p.device))
+    arrays = {'loss': loss.detach().float().reshape(1), 'logits': logits.float(), 'params_sample': torch.cat(ps), 'grads_sample': torch.cat(gs)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy().astype(np.float32))
 
 
 def _free_port():
@@ -380,7 +435,8 @@ def main():
     dev = torch.device('cuda', local)
     force_dp = os.environ.get('VTX_FORCE_DP', '0') == '1'     # 1-rank RCCL group: exercises the DP path on one GPU
     import __graft_entry__ as ge
-    ge.ensure_built()
+    if not library_up_to_date():
+        ge.ensure_built()
     import vtx
     if world > 1 or force_dp:
         from vtx import dp as _dp
@@ -425,7 +481,7 @@ def main():
         buckets.finish()
         if opt is not None:
             opt.step()
-        return loss
+        return loss, logits.detach()
 
     for _ in range(args.warmup):
         step()
@@ -436,7 +492,7 @@ def main():
     ops.profile_start(('gemm_nt',))
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, logits = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -449,10 +505,13 @@ def main():
         elapsed = t.item()
     final_loss = float(loss.detach())
     rccl_world = dist.get_world_size() if dist.is_initialized() else 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, logits, params)
+    del logits
 
     # ---- instrumented pass (outside the timed region): every kernel class, HIP events per launch ----
     classes = None
-    if not args.no_breakdown and rank == 0:
+    if args.full and not args.no_breakdown and rank == 0:
         names = ('gemm_nt', 'gemm_tn', 'wprod', 'attn_fwd_time', 'attn_bwd_time', 'attn_fwd_space', 'attn_bwd_space', 'ln_fwd', 'ln_bwd',
                  'colsum', 'patch_rows', 'hog')
         nb = 2
@@ -472,7 +531,7 @@ def main():
         classes['_step_ms'] = step_ms
         classes['_steps'] = nb
     others = None
-    if world == 1 and not force_dp and not args.no_other_configs and args.precision == 'bf16' and args.frames == 8 and args.stream == 'bf16':
+    if args.full and world == 1 and not force_dp and not args.no_other_configs and args.precision == 'bf16' and args.frames == 8 and args.stream == 'bf16':
         buckets.remove()                                # the mini-runs build their own buckets over the same parameters
         del x
         torch.cuda.empty_cache()
@@ -550,7 +609,7 @@ def main():
             out['roofline_hbm'] = hbm
         if others is not None:
             out['other_configs'] = others
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline_subprocess(args.frames)
     else:
         out = None

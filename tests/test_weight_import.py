@@ -1,5 +1,5 @@
 """Pretrained-checkpoint importers (weight_init.py) against golden key maps produced by the reference's own
-functions (tests/golden/make_golden_import.py), and -- in the dev container -- against the reference live."""
+functions (tests/golden/make_golden_import.py): within a tolerance for every case, and bit for bit for a third of them."""
 import json
 import os
 
@@ -8,7 +8,6 @@ import torch
 
 from helpers import GOLD
 from import_cases import CASES, summarize, synth_checkpoint
-from oracle import ref_loader
 
 
 class Recorder:
@@ -41,12 +40,13 @@ def test_importer_matches_reference_golden(name, kind, kw, tmp_path):
         assert abs(got[k][1] - gold[k][1]) < 1e-4 and abs(got[k][2] - gold[k][2]) < 1e-4, k
 
 
-@pytest.mark.skipif(not ref_loader.available(), reason='needs /root/reference (dev container)')
 @pytest.mark.parametrize('name,kind,kw', CASES[::3], ids=[c[0] for c in CASES[::3]])
 def test_importer_matches_reference_live(name, kind, kw, tmp_path):
+    """The reference's result as its run recorded it (shape, sum and abs-sum rounded to 1e-6, JSON floats round-trip
+    exactly): the importer must reproduce it to the last digit."""
     import weight_init as W
-    ref = _run(ref_loader.load().weight_init, name, kind, kw, tmp_path)
-    assert _run(W, name, kind, kw, tmp_path) == ref
+    ref = json.load(open(os.path.join(GOLD, 'weight_import.json')))[name]
+    assert json.loads(json.dumps(_run(W, name, kind, kw, tmp_path))) == ref
 
 
 def test_vit_checkpoint_initialises_a_model(tmp_path):

@@ -11,8 +11,8 @@ for rep in 1 2; do
   VTX_GEMM_PP_EPI=4 timeout 300 python tools/gemm_shapes.py 96 8 > gpurun_out/r4a_shapes_old_$rep.txt 2>&1
 done
 grep "NT sum" gpurun_out/r4a_shapes_*.txt
-timeout 600 python bench.py --steps 10 --warmup 3 > gpurun_out/r4a_bench.log 2>&1
-tail -c 1500 gpurun_out/r4a_bench.log
+timeout 600 python bench.py --full --steps 10 --warmup 3 > /tmp/r4a_bench.log 2>&1
+tail -c 1500 /tmp/r4a_bench.log
 for k in plain residual gelu2 mul; do
   timeout 120 python tools/pp_timeline.py 150528 768 768 $k >> gpurun_out/r4a_timeline.txt 2>&1
 done

@@ -13,4 +13,4 @@ echo "tests rc=$?" >> $O/r5a_tests.log
 tail -25 $O/r5a_tests.log | cut -c1-250
 cp $O/parity_report.txt $O/r5a_parity_report.txt
 grep -c . $O/r5a_parity_report.txt; grep FAIL $O/r5a_parity_report.txt | cut -c1-200
-timeout 600 python bench.py > $O/r5a_bench.log 2>&1; tail -1 $O/r5a_bench.log | cut -c1-400
+timeout 600 python bench.py --full > $O/r5a_bench.log 2>&1; tail -1 $O/r5a_bench.log | cut -c1-400

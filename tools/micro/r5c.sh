@@ -6,7 +6,7 @@ timeout 300 python __graft_entry__.py smoke 2>&1 | grep -v amdgpu.ids | tail -9 
 timeout 600 python -m pytest tests/test_gpu_kernels.py -x -q -k "hog or gemm_tn or selftest or maskfeat" > $O/r5c_tests.log 2>&1; echo "rc=$?" >> $O/r5c_tests.log
 tail -6 $O/r5c_tests.log | cut -c1-300
 timeout 300 python tools/other_configs.py hog 2>&1 | grep -v amdgpu.ids > $O/r5c_hog.txt; cat $O/r5c_hog.txt | cut -c1-400
-timeout 600 python bench.py > $O/r5c_bench.log 2>&1; tail -1 $O/r5c_bench.log | python -c "
+timeout 600 python bench.py --full > $O/r5c_bench.log 2>&1; tail -1 $O/r5c_bench.log | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(d['value'], d['ms_per_step'], d['roofline'])

@@ -3,7 +3,7 @@
 # + the INTEGRATION.md stub test.
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; mkdir -p $O; cd $R; export TMPDIR=/tmp
 timeout 300 python -m pytest tests/test_gpu_kernels.py -x -q -k "integration_stub or selftest" > $O/r6a_tests.log 2>&1; echo "rc=$?" >> $O/r6a_tests.log; tail -3 $O/r6a_tests.log
-timeout 600 python bench.py > $O/r6a_bench.log 2>&1; tail -1 $O/r6a_bench.log > $O/r6a_bench.json; python - <<'PY'
+timeout 600 python bench.py --full > $O/r6a_bench.log 2>&1; tail -1 $O/r6a_bench.log > $O/r6a_bench.json; python - <<'PY'
 import json
 d = json.loads(open('gpurun_out/r6a_bench.json').read())
 print(d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['avg_launch_us'], d.get('gemm_tn_roofline'))
