@@ -280,7 +280,10 @@ typedef struct {
   int rows, cols;
 } vtx_ct_tensor;
 int vtx_mt_cast_transpose(int dtype, const vtx_ct_tensor* tab, const int* tile_start, int n_tensors, int n_tiles, void* stream);
-/* dst (dtype) = src (fp32), n elements; and the reverse. */
+/* dst (dtype) = src (fp32), n elements; and the reverse.  fp32 -> bf16 rounds to nearest even (ties to even, finite
+ * values that round past the largest bf16 become Inf), keeps fp32 subnormals (no flush to zero), and turns every NaN
+ * into a quiet NaN: bit-identical to torch's conversion except for a NaN's sign and payload (tests/test_gpu_exact_arith.py).
+ * bf16 -> fp32 is exact (the 16 bits shifted up, NaN payloads included). */
 int vtx_cast_from_f32(int dtype, size_t n, const float* src, void* dst, void* stream);
 int vtx_cast_to_f32(int dtype, size_t n, const void* src, float* dst, void* stream);
 
