@@ -1,6 +1,10 @@
 """Attention / LayerNorm kernels at the benchmark shapes (GPU box only): time and algorithmic TB/s per launch.
 
     python tools/attn_bench.py [clips] [option=value ...]       e.g.  python tools/attn_bench.py 96 attn_hw=1
+    python tools/attn_bench.py long [clips] [option=value ...]  only the sequences of more than 256 tokens (default 8 clips):
+                                                                joint space-time (contig, S = clips, L = 1569) and the spatial
+                                                                attention of a 448^2, 16-frame model (space, T = 16, P = 784),
+                                                                e.g.  python tools/attn_bench.py long 8 attn_long=0
 """
 import os
 import sys
@@ -29,12 +33,48 @@ def timeit(fn, iters=20, warm=3):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
+def long_shapes(B, H=12, hd=64):
+    """Time and achieved TFLOP/s (forward 4 S H L^2 hd, backward 10 S H L^2 hd: the formulas of vtx/ops.py) and the share of the
+    dense bf16 roof bench.py uses (2500 TFLOP/s)."""
+    bf, D = torch.bfloat16, H * hd
+    r = lambda *s: (torch.randn(*s, device=DEV) * 0.5).to(bf)   # noqa: E731
+    rows = []
+    S, L = B, 1569
+    qkv, o, do = r(S * L, 3 * D), torch.empty(S * L, D, device=DEV, dtype=bf), r(S * L, D)
+    lse = torch.empty(S * H * L, device=DEV)
+    dqkv = torch.empty(S * L, 3 * D, device=DEV, dtype=bf)
+    t = timeit(lambda: ops.attn_fwd(qkv, o, lse, ATTN_CONTIG, S, L, H, hd, hd ** -0.5), iters=10)
+    rows.append((f'attn fwd joint   S={S} L={L}', t, 4.0 * S * H * L * L * hd))
+    t = timeit(lambda: ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, S, L, H, hd, hd ** -0.5), iters=10)
+    rows.append((f'attn bwd joint   S={S} L={L}', t, 10.0 * S * H * L * L * hd))
+    del qkv, o, do, lse, dqkv
+    T, P = 16, 784
+    S, L, N = B * T, P + 1, P * T
+    M1, Mo = B * (N + 1), B * N + B * T
+    qkv, o, do = r(M1, 3 * D), torch.empty(Mo, D, device=DEV, dtype=bf), r(Mo, D)
+    lse = torch.empty(S * H * L, device=DEV)
+    dqkv = torch.empty(M1, 3 * D, device=DEV, dtype=bf)
+    dcls = torch.empty(B * T, 3 * D, device=DEV, dtype=bf)
+    t = timeit(lambda: ops.attn_fwd(qkv, o, lse, ATTN_SPACE, S, L, H, hd, hd ** -0.5, B, T, P), iters=10)
+    rows.append((f'attn fwd spatial S={S} L={L}', t, 4.0 * S * H * L * L * hd))
+    t = timeit(lambda: ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, S, L, H, hd, hd ** -0.5, B, T, P, dqkv_cls=dcls), iters=10)
+    rows.append((f'attn bwd spatial S={S} L={L}', t, 10.0 * S * H * L * L * hd))
+    for name, t, fl in rows:
+        print(f'{name:30s} {t * 1e3:9.3f} ms  {fl / t / 1e12:7.1f} TFLOP/s  {fl / t / 1e12 / 2500.0 * 100:5.2f} % of 2500', flush=True)
+
+
 def main():
     args = [a for a in sys.argv[1:] if '=' not in a]
     for a in sys.argv[1:]:
         if '=' in a:
             k, v = a.split('=')
             vtx.set_option(k, v)
+    if 'long' in args:
+        args.remove('long')
+        B = int(args[0]) if args else 8
+        print(f'clips {B}; options ' + ' '.join(a for a in sys.argv[1:] if '=' in a))
+        long_shapes(B)
+        return
     B = int(args[0]) if args else 96
     T, P, D, H = 8, 196, 768, 12
     hd = D // H

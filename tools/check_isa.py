@@ -117,11 +117,39 @@ def check_tn_w4(obj):
     return problems
 
 
+def check_plain(obj, names):
+    """A compiled object whose kernels take no special care (csrc/attn_long.hip): every kernel of `names` is there, uses the
+    32x32x16 bf16 MFMA, and has neither scratch (spill) traffic nor an instruction of the scalar unit that writes memory."""
+    ks = dict((n, b) for n, b in kernels(disassemble(obj)))
+    bad = []
+    writes = re.compile(r'\bs_\w*(?:store|atomic|dcache)\w*')
+    for want in names:
+        hit = [n for n in ks if want in n]
+        if not hit:
+            bad.append(f'{want}: kernel not found')
+            continue
+        text = '\n'.join(ks[hit[0]])
+        if 'scratch_' in text:
+            bad.append(f'{want}: scratch traffic')
+        if 'v_mfma_f32_32x32x16_bf16' not in text:
+            bad.append(f'{want}: no v_mfma_f32_32x32x16_bf16')
+        m = writes.search(text)
+        if m:
+            bad.append(f'{want}: scalar memory write {m.group(0)}')
+        print(f'{want}: {len(ks[hit[0]])} lines, {text.count("v_mfma_")} MFMA, ok' if not any(b.startswith(want) for b in bad) else f'{want}: FAIL')
+    return bad
+
+
 if __name__ == '__main__':
     obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'gemm_nt.o')
-    bad = check(obj)
+    if os.path.basename(obj) == 'attn_long.o':
+        bad = check_plain(obj, ['attn_fwd_long_kernel', 'attn_bwd_dq_long_kernel', 'attn_bwd_dkv_long_kernel'])
+    else:
+        bad = check(obj)
     if len(sys.argv) <= 1:
         bad += check_tn_w4(os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'gemm_tn.o'))
+        bad += check_plain(os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'attn_long.o'),
+                           ['attn_fwd_long_kernel', 'attn_bwd_dq_long_kernel', 'attn_bwd_dkv_long_kernel'])
     for b in bad:
         print('VIOLATION', b)
     sys.exit(1 if bad else 0)

@@ -125,8 +125,20 @@ def hog(frames_n=1024, iters=10):
     print(json.dumps(res), flush=True)
 
 
+def timesformer_joint(batch=8):
+    # TimeSformer-B joint_space_time: one sequence of 1 + 196 * 8 = 1569 tokens per clip (csrc/attn_long.hip).  Per clip,
+    # 12 layers: linear layers 2 * 1569 * 12 * 768^2 * 12 = 0.267 TFLOP, attention core 4 * 1569^2 * 64 * 12 * 12 = 0.091 TFLOP
+    # forward; x 3 for forward + backward.
+    train('TimeSformer-B joint_space_time, 8x3x224x224, bf16, fwd+CE+bwd+SGD',
+          V.TimeSformer(num_frames=8, attention_type='joint_space_time'), batch, 8, 3 * (0.267e12 + 0.091e12))
+
+
 if __name__ == '__main__':
-    which = sys.argv[1:] or ['hog', 'vivit', 'tsf16', 'tsfl96']
+    for a in [a for a in sys.argv[1:] if '=' in a]:      # option=value, e.g. attn_long=0
+        vtx.set_option(*a.split('='))
+    which = [a for a in sys.argv[1:] if '=' not in a] or ['hog', 'vivit', 'tsf16', 'tsfl96']
+    if 'tsfjoint' in which:
+        timesformer_joint()
     if 'hog' in which:
         hog()
     if 'vivit' in which:

@@ -175,6 +175,7 @@ struct Options {
                              // round with up to 16 CUs held, at +4 .. 7 % per launch when none is.  Changes the slab partition, i.e. the
                              // fp32 summation order of the weight gradients (still fixed for a given value: bit-reproducible).
   int attn_valu = 0;         // VTX_ATTN_VALU: fp32-VALU attention kernels also for bf16
+  int attn_long = 1;         // VTX_ATTN_LONG: bf16 attention of more than 256 tokens on the MFMA kernels of attn_long.hip; 0 = the VALU kernels
   int attn_hw_fwd = 16;      // VTX_ATTN_HW_FWD / _BWD: short-sequence attention with n heads of a row tile in one workgroup
   int attn_hw_bwd = 4;       //   (0: one head per workgroup, four row tiles; backward: 4 heads -- 512 contiguous bytes per row -- measured best)
   int attn_fused = 2;        // VTX_ATTN_FUSED: backward of the 33..224-token attention: 2 = one phase per (sequence, head), operands streamed (193..224

@@ -326,7 +326,7 @@ def _attn_desc(qkv, out, lse, mode, S, L, H, hd, scale, B=0, T=0, P=0, probs=Non
 def attn_fwd(qkv, out, lse, mode, S, L, H, hd, scale, B=0, T=0, P=0, probs=None):
     need_cuda(qkv, out, lse)
     d = _attn_desc(qkv, out, lse, mode, S, L, H, hd, scale, B, T, P, probs)
-    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq')
+    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq' if L <= 256 else 'long')
     rows = S * L                       # algorithmic bytes: read q,k,v, write o (+ fp32 log-sum-exp)
     with _timed(f'attn_fwd_{kind}', 4.0 * S * H * L * L * hd, rows * H * hd * 4 * qkv.element_size() + rows * H * 4,
                 f'{S}x{L}x{H}'):
@@ -342,7 +342,7 @@ def attn_bwd(qkv, out, lse, dout, dqkv, mode, S, L, H, hd, scale, B=0, T=0, P=0,
     b.dqkv_cls = ptr(dqkv_cls)
     delta = torch.empty(S * H * L, dtype=torch.float32, device=qkv.device)
     b.delta = ptr(delta)
-    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq')
+    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq' if L <= 256 else 'long')
     rows = S * L                       # read q,k,v,o,do, write dq,dk,dv
     with _timed(f'attn_bwd_{kind}', 10.0 * S * H * L * L * hd, rows * H * hd * 8 * qkv.element_size() + rows * H * 4,
                 f'{S}x{L}x{H}'):
