@@ -178,22 +178,29 @@ def firing():
     return _firing
 
 
-def _linear_grads(w, b, A, Bm, M, N1, N2, **kw):
-    """(d_weight, d_bias) of a Linear out of the two GEMM operands; (None, None) when they went straight into
-    w.grad / b.grad."""
-    gw, gb = _sink(w), _sink(b)
-    if gw is not None and gb is not None:
-        ops.gemm_tn(A, Bm, M, N1, N2, out=gw.view(N1, N2), accumulate=True, colsum_out=gb, colsum_accumulate=True, **kw)
-        _fire(w, b)
-        return None, None
-    return ops.gemm_tn(A, Bm, M, N1, N2, want_colsum=True, **kw)
+def _weight_grads(params, A, Bm, M, N1, N2, bias=True, amap=IDENT):
+    """(d_weight, d_bias) of a Linear out of the two GEMM operands -- every weight gradient of this file is this call.
+    ``params``: the (weight, bias) parameters whose .grad takes the sums when direct gradients are on -- then (None, None)
+    comes back and their hooks have run -- or None: the gradients always go back to autograd.  bias=False: a Linear
+    without bias, no column sums, d_bias is None."""
+    if params is not None:
+        gw, gb = _sink(params[0]), _sink(params[1])
+        if gw is not None and gb is not None:
+            ops.gemm_tn(A, Bm, M, N1, N2, out=gw.view(N1, N2), accumulate=True, colsum_out=gb, colsum_accumulate=True, amap=amap)
+            _fire(*params)
+            return None, None
+    if bias:
+        return ops.gemm_tn(A, Bm, M, N1, N2, want_colsum=True, amap=amap)
+    return ops.gemm_tn(A, Bm, M, N1, N2, amap=amap), None
 
 
-def _ln_grad_buffers(ln_w, ln_b, D, device):
-    """Buffers vtx_layernorm_bwd accumulates d_gamma / d_beta into: the parameters' own .grad (direct), else zeros."""
-    gw, gb = _sink(ln_w), _sink(ln_b)
-    if gw is not None and gb is not None:
-        return gw, gb, True
+def _ln_grad_buffers(params, D, device):
+    """Buffers vtx_layernorm_bwd accumulates d_gamma / d_beta into: the .grad of ``params`` = (ln_w, ln_b) (direct gradients;
+    never with params None), else zeros.  -> (d_gamma, d_beta, direct)."""
+    if params is not None:
+        gw, gb = _sink(params[0]), _sink(params[1])
+        if gw is not None and gb is not None:
+            return gw, gb, True
     return (torch.zeros(D, dtype=torch.float32, device=device), torch.zeros(D, dtype=torch.float32, device=device), False)
 
 
@@ -288,6 +295,73 @@ def _chk(x):
     return x
 
 
+# ---- the pre-norm skeleton shared by TimeAttnFn, SpaceAttnFn, SelfAttnFn and FFNFn -------------------------------
+# LayerNorm -> body -> residual in the GEMM epilogue; backward: body -> weight gradients -> LayerNorm backward + residual.
+# The bodies live in the Functions; what surrounds them is here, once.
+def _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, rows, xmap):
+    """LayerNorm of ``rows`` rows of the block input (row m at xmap(m)) -> (xn, mean, rstd, x32, res): xn compact, res the
+    residual the GEMM epilogue is to add.  exact: x is the previous sub-block's contribution, the rows of the float32 stream
+    x32 = xs + x are formed on the way and normalised, and the epilogue adds nothing (res None); else x32 is None."""
+    D = x.shape[-1]
+    xn = _empty((rows, D), x)
+    mean = _empty((rows,), x, torch.float32)
+    rstd = _empty((rows,), x, torch.float32)
+    if exact:
+        x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        ops.layernorm_acc_fwd(xs, x, rows, D, D, xmap, x32, D, xmap, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
+        return xn, mean, rstd, x32, None
+    ops.layernorm_fwd(x, rows, D, D, xmap, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
+    return xn, mean, rstd, None, x
+
+
+def _prenorm_save(ctx, out, x, x32, saved, scale_vec, wts):
+    """End of a forward: save the stream the block read (x32 under the exact stream, never x next to it), ``saved``
+    (ln_w, mean, rstd, xn, then the body's own), the scale vector or an empty placeholder, and the transposed weights that
+    exist; -> what forward returns: out, or (out, x32)."""
+    ctx.save_for_backward(x if x32 is None else x32, *saved, scale_vec if scale_vec is not None else x.new_empty(0),
+                          *[t for t in wts if t is not None])
+    if x32 is None:
+        return out
+    ctx.mark_non_differentiable(x32)
+    ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
+    return out, x32
+
+
+def _prenorm_bwd(dout, dxn, x_stream, xmap, ln_w, mean, rstd, params, skip=None):
+    """End of a backward: dx = dout + LayerNorm-backward(dxn) on the rows the block normalised (row m at xmap(m)), with the
+    float32 gradient stream next to it when that is on -> (dx, d_ln_w, d_ln_b).  ``params``: as in _ln_grad_buffers.
+    ``skip`` = (rows, rowmap): rows the block does not touch, their gradient passes through."""
+    D = dout.shape[-1]
+    dx = torch.empty_like(dout)
+    g32 = _grad_stream(dout, x_stream)
+    dx32 = torch.empty_like(g32) if g32 is not None else None
+    d_ln_w, d_ln_b, direct = _ln_grad_buffers(params, D, dout.device)
+    _ln_bwd_res(dxn, x_stream, xmap, mean.numel(), D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
+    if direct:
+        _fire(*params)
+        d_ln_w = d_ln_b = None
+    if skip is not None:
+        _copy_rows_res(dout, dx, g32, dx32, skip[0], D, skip[1])
+    _hand_on(dx, dx32)
+    return dx, d_ln_w, d_ln_b
+
+
+def _qkv_fwd(xn, qkv_w, qkv_b, rows, D, need_t):
+    """The qkv projection of the three attention Functions -> (qkv [rows, 3D], W_qkv^T for the backward or None)."""
+    wq, wqT = weights(qkv_w, xn.dtype, need_t)
+    qkv = _empty((rows, 3 * D), xn)
+    ops.gemm_nt(xn, wq, qkv, rows, 3 * D, D, bias=qkv_b)
+    return qkv, wqT
+
+
+def _qkv_bwd(params, dqkv, xn, wqT, rows, D):
+    """Backward of _qkv_fwd -> (d_qkv_w, d_qkv_b, dxn); ``params``: as in _weight_grads."""
+    d_qkv_w, d_qkv_b = _weight_grads(params, dqkv, xn, rows, 3 * D, D)
+    dxn = _empty((rows, D), dqkv)
+    ops.gemm_nt(dqkv, wqT, dxn, rows, D, 3 * D)
+    return d_qkv_w, d_qkv_b, dxn
+
+
 # ---------------------------------------------------------------------------------
 class TimeAttnFn(torch.autograd.Function):
     """DividedTemporalAttentionWithPreNorm.forward, use_cls_token=False (reference transformer.py:234-282).
@@ -317,20 +391,10 @@ class TimeAttnFn(torch.autograd.Function):
         dtp = x.dtype
         need_t = any(ctx.needs_input_grad)
         merged = _merge_tfc and (scale_vec is None or keep_scale is not None) and proj_b is not None and tfc_b is not None
-        xn = _empty((M, D), x)
-        mean = _empty((M,), x, torch.float32)
-        rstd = _empty((M,), x, torch.float32)
-        x32 = None
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, tm)
         if exact:
-            x32 = torch.empty(B, N1, D, dtype=torch.float32, device=x.device)
-            ops.layernorm_acc_fwd(xs, x, M, D, D, tm, x32, D, tm, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
             ops.layernorm_acc_fwd(xs, x, B, D, D, ops.clsmap(N), x32, D, ops.clsmap(N))       # the cls rows: accumulate only
-        else:
-            ops.layernorm_fwd(x, M, D, D, tm, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        res = None if exact else x                  # the residual the GEMM epilogue adds: none under the exact stream
-        wq, wqT = weights(qkv_w, dtp, need_t)
-        qkv = _empty((M, 3 * D), x)
-        ops.gemm_nt(xn, wq, qkv, M, 3 * D, D, bias=qkv_b)
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t)
         o = _empty((M, D), x)
         S = M // T
         lse = _empty((S * heads * T,), x, torch.float32)
@@ -344,27 +408,21 @@ class TimeAttnFn(torch.autograd.Function):
             if scale_vec is not None:
                 ops.dropped_rows_fix(scale_vec, M, D, T, x=res, xmap=tm, bias=tfc_b.detach(), out=out, omap=tm, zero=o)
             a = x.new_empty(0)
-            wts = [t for t in (wqT, wcT) if t is not None]
+            wts = (wqT, wcT)
         else:
             wp, wpT = weights(proj_w, dtp, need_t)
             a = _empty((M, D), x)
             ops.gemm_nt(o, wp, a, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(T, 1, 1, 0))
             wt, wtT = weights(tfc_w, dtp, need_t)
             ops.gemm_nt(a, wt, out, M, D, D, cmap=tm, bias=tfc_b, R=res, rmap=tm)
-            wts = [t for t in (wqT, wpT, wtT) if t is not None]
+            wts = (wqT, wpT, wtT)
         if exact:
             _zero_rows(x, out, B, D, ops.clsmap(N))                 # the block contributes nothing to the cls rows
         else:
             ops.row_scale_copy(x, out, B, D, smap=ops.clsmap(N), dmap=ops.clsmap(N))
-        ctx.save_for_backward(x32 if exact else x, ln_w, mean, rstd, xn, qkv, o, lse, a,
-                              scale_vec if scale_vec is not None else x.new_empty(0), *wts)
         ctx.cfg = (T, heads, scale_vec is not None, merged, keep_scale)
         ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, tfc_w, tfc_b)
-        if exact:
-            ctx.mark_non_differentiable(x32)
-            ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
-            return out, x32
-        return out
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse, a), scale_vec, wts)
 
     @staticmethod
     def backward(ctx, dout, _dstream=None):
@@ -380,7 +438,6 @@ class TimeAttnFn(torch.autograd.Function):
         hd = D // heads
         S = M // T
         tm = ops.tokmap(N)
-        dtp = dout.dtype
         x_stream, x = x, dout                          # allocation template from here on
         do = _empty((M, D), x)
         if merged:
@@ -412,29 +469,18 @@ class TimeAttnFn(torch.autograd.Function):
         else:
             wpT, wtT = wrest
             # temporal_fc
-            d_tfc_w, d_tfc_b = _linear_grads(p_tfc_w, p_tfc_b, dout, a, M, D, D, amap=tm)
+            d_tfc_w, d_tfc_b = _weight_grads((p_tfc_w, p_tfc_b), dout, a, M, D, D, amap=tm)
             da = _empty((M, D), x)
             ops.gemm_nt(dout, wtT, da, M, D, D, amap=tm, row_scale=sv, rs=(T, 1, 1, 0))
             # proj
-            d_proj_w, d_proj_b = _linear_grads(p_proj_w, p_proj_b, da, o, M, D, D)
+            d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, M, D, D)
             ops.gemm_nt(da, wpT, do, M, D, D)
         # attention core
         dqkv = _empty((M, 3 * D), x)
         ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, S, T, heads, hd, hd ** -0.5)
-        d_qkv_w, d_qkv_b = _linear_grads(p_qkv_w, p_qkv_b, dqkv, xn, M, 3 * D, D)
-        dxn = _empty((M, D), x)
-        ops.gemm_nt(dqkv, wqT, dxn, M, D, 3 * D)
-        # LayerNorm + residual
-        dx = torch.empty_like(x)
-        g32 = _grad_stream(dout, x_stream)
-        dx32 = torch.empty_like(g32) if g32 is not None else None
-        d_ln_w, d_ln_b, direct = _ln_grad_buffers(p_ln_w, p_ln_b, D, x.device)
-        _ln_bwd_res(dxn, x_stream, tm, M, D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
-        if direct:
-            _fire(p_ln_w, p_ln_b)
-            d_ln_w = d_ln_b = None
-        _copy_rows_res(dout, dx, g32, dx32, B, D, ops.clsmap(N))
-        _hand_on(dx, dx32)
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M, D)
+        # LayerNorm + residual; the cls rows pass through
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=(B, ops.clsmap(N)))
         return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, d_tfc_w, d_tfc_b, None, None, None, None, None, None, None)
 
 
@@ -453,19 +499,9 @@ class SpaceAttnFn(torch.autograd.Function):
         P = N // T
         M1 = B * N1
         hd = D // heads
-        dtp = x.dtype
-        xn = _empty((M1, D), x)
-        mean = _empty((M1,), x, torch.float32)
-        rstd = _empty((M1,), x, torch.float32)
-        x32 = None
-        if exact:
-            x32 = torch.empty(B, N1, D, dtype=torch.float32, device=x.device)
-            ops.layernorm_acc_fwd(xs, x, M1, D, D, IDENT, x32, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        else:
-            ops.layernorm_fwd(x, M1, D, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        wq, wqT = weights(qkv_w, dtp, any(ctx.needs_input_grad))
-        qkv = _empty((M1, 3 * D), x)
-        ops.gemm_nt(xn, wq, qkv, M1, 3 * D, D, bias=qkv_b)
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M1, IDENT)
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M1, D, need_t)
         Mo = B * N + B * T
         o = _empty((Mo, D), x)
         S, L = B * T, P + 1
@@ -475,23 +511,16 @@ class SpaceAttnFn(torch.autograd.Function):
         if want_probs:
             ctx.mark_non_differentiable(probs)
             return probs
-        wp, wpT = weights(proj_w, dtp, any(ctx.needs_input_grad))
+        wp, wpT = weights(proj_w, x.dtype, need_t)
         out = torch.empty_like(x)
         a_cls = _empty((B * T, D), x)
         tm = ops.tokmap(N)
         ops.gemm_nt(o, wp, out, Mo, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(N, T, T, 1),
-                    R=None if exact else x, rmap=tm, split_row=B * N, Csplit=a_cls)
-        ops.cls_mean_fwd(a_cls, None if exact else x, out, B, T, D, N1)
-        ctx.save_for_backward(x32 if exact else x, ln_w, mean, rstd, xn, qkv, o, lse,
-                              scale_vec if scale_vec is not None else x.new_empty(0),
-                              *[t for t in (wqT, wpT) if t is not None])
+                    R=res, rmap=tm, split_row=B * N, Csplit=a_cls)
+        ops.cls_mean_fwd(a_cls, res, out, B, T, D, N1)
         ctx.cfg = (T, heads, scale_vec is not None)
         ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
-        if exact:
-            ctx.mark_non_differentiable(x32)
-            ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
-            return out, x32
-        return out
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
 
     @staticmethod
     def backward(ctx, dout, _dstream=None):
@@ -506,11 +535,10 @@ class SpaceAttnFn(torch.autograd.Function):
         M1 = B * N1
         Mo = B * N + B * T
         hd = D // heads
-        dtp = dout.dtype
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
         da = _empty((Mo, D), x)
         ops.space_grad_prep(dout, sv, da, B, T, P, D)
-        d_proj_w, d_proj_b = _linear_grads(p_proj_w, p_proj_b, da, o, Mo, D, D)
+        d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, Mo, D, D)
         do = _empty((Mo, D), x)
         ops.gemm_nt(da, wpT, do, Mo, D, D)
         dqkv = _empty((M1, 3 * D), x)
@@ -518,18 +546,8 @@ class SpaceAttnFn(torch.autograd.Function):
         ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, B * T, P + 1, heads, hd, hd ** -0.5, B, T, P,
                      dqkv_cls=dqkv_cls)
         ops.cls_qkv_reduce(dqkv_cls, dqkv, B, T, 3 * D, N1)
-        d_qkv_w, d_qkv_b = _linear_grads(p_qkv_w, p_qkv_b, dqkv, xn, M1, 3 * D, D)
-        dxn = _empty((M1, D), x)
-        ops.gemm_nt(dqkv, wqT, dxn, M1, D, 3 * D)
-        dx = torch.empty_like(x)
-        g32 = _grad_stream(dout, x_stream)
-        dx32 = torch.empty_like(g32) if g32 is not None else None
-        d_ln_w, d_ln_b, direct = _ln_grad_buffers(p_ln_w, p_ln_b, D, x.device)
-        _ln_bwd_res(dxn, x_stream, IDENT, M1, D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
-        if direct:
-            _fire(p_ln_w, p_ln_b)
-            d_ln_w = d_ln_b = None
-        _hand_on(dx, dx32)
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M1, D)
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
         return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
 
 
@@ -543,19 +561,9 @@ class SelfAttnFn(torch.autograd.Function):
         Bn, L, D = x.shape
         M = Bn * L
         hd = D // heads
-        dtp = x.dtype
-        xn = _empty((M, D), x)
-        mean = _empty((M,), x, torch.float32)
-        rstd = _empty((M,), x, torch.float32)
-        x32 = None
-        if exact:
-            x32 = torch.empty(Bn, L, D, dtype=torch.float32, device=x.device)
-            ops.layernorm_acc_fwd(xs, x, M, D, D, IDENT, x32, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        else:
-            ops.layernorm_fwd(x, M, D, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        wq, wqT = weights(qkv_w, dtp, any(ctx.needs_input_grad))
-        qkv = _empty((M, 3 * D), x)
-        ops.gemm_nt(xn, wq, qkv, M, 3 * D, D, bias=qkv_b)
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, IDENT)
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t)
         o = _empty((M, D), x)
         lse = _empty((Bn * heads * L,), x, torch.float32)
         probs = _empty((Bn, heads, L, L), x, torch.float32) if want_probs else None
@@ -563,18 +571,11 @@ class SelfAttnFn(torch.autograd.Function):
         if want_probs:
             ctx.mark_non_differentiable(probs)
             return probs
-        wp, wpT = weights(proj_w, dtp, any(ctx.needs_input_grad))
+        wp, wpT = weights(proj_w, x.dtype, need_t)
         out = torch.empty_like(x)
-        ops.gemm_nt(o, wp, out, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(L, 1, 1, 0), R=None if exact else x)
-        ctx.save_for_backward(x32 if exact else x, ln_w, mean, rstd, xn, qkv, o, lse,
-                              scale_vec if scale_vec is not None else x.new_empty(0),
-                              *[t for t in (wqT, wpT) if t is not None])
+        ops.gemm_nt(o, wp, out, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(L, 1, 1, 0), R=res)
         ctx.cfg = (heads, scale_vec is not None)
-        if exact:
-            ctx.mark_non_differentiable(x32)
-            ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
-            return out, x32
-        return out
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
 
     @staticmethod
     def backward(ctx, dout, _dstream=None):
@@ -584,28 +585,21 @@ class SelfAttnFn(torch.autograd.Function):
         Bn, L, D = x.shape
         M = Bn * L
         hd = D // heads
-        dtp = dout.dtype
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
         if has_scale:
             da = _empty((M, D), x)
             ops.row_scale_copy(dout, da, M, D, s=sv, rs=(L, 1, 1, 0))
         else:
             da = dout
-        d_proj_w, d_proj_b = ops.gemm_tn(da, o, M, D, D, want_colsum=True)
+        # params None (three times): this Function hands every gradient to autograd even with direct gradients on, and its
+        # LayerNorm sums start from fresh zeros -- the status quo, not a decision
+        d_proj_w, d_proj_b = _weight_grads(None, da, o, M, D, D)
         do = _empty((M, D), x)
         ops.gemm_nt(da, wpT, do, M, D, D)
         dqkv = _empty((M, 3 * D), x)
         ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, Bn, L, heads, hd, hd ** -0.5)
-        d_qkv_w, d_qkv_b = ops.gemm_tn(dqkv, xn, M, 3 * D, D, want_colsum=True)
-        dxn = _empty((M, D), x)
-        ops.gemm_nt(dqkv, wqT, dxn, M, D, 3 * D)
-        dx = torch.empty_like(x)
-        d_ln_w = torch.zeros(D, dtype=torch.float32, device=x.device)
-        d_ln_b = torch.zeros(D, dtype=torch.float32, device=x.device)
-        g32 = _grad_stream(dout, x_stream)
-        dx32 = torch.empty_like(g32) if g32 is not None else None
-        _ln_bwd_res(dxn, x_stream, IDENT, M, D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
-        _hand_on(dx, dx32)
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd(None, dqkv, xn, wqT, M, D)
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, None)
         return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None)
 
 
@@ -669,39 +663,24 @@ class FFNFn(torch.autograd.Function):
         M = x.numel() // D
         rows_per = M // x.shape[0]
         Hd = w1.shape[0]
-        dtp = x.dtype
         plan = _compaction_plan(scale_vec, x.shape[0], rows_per, x.device)
         if plan is not None:
             return FFNFn._forward_compact(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, plan, rows_per, xs, exact)
-        xn = _empty((M, D), x)
-        mean = _empty((M,), x, torch.float32)
-        rstd = _empty((M,), x, torch.float32)
-        x32 = None
-        if exact:
-            x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-            ops.layernorm_acc_fwd(xs, x, M, D, D, IDENT, x32, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        else:
-            ops.layernorm_fwd(x, M, D, D, IDENT, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-        w1c, w1T = weights(w1, dtp, any(ctx.needs_input_grad))
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, IDENT)
+        w1c, w1T = weights(w1, x.dtype, need_t)
         # the second output is gelu'(pre-activation), not the pre-activation: it is all the backward needs of it
         # (transformer.py:503 nn.GELU), computed from the same erf / exp evaluation, and the backward's epilogue
         # becomes one multiply instead of an erf + exp per element
         h = _empty((M, Hd), x)
         g = _empty((M, Hd), x)
         ops.gemm_nt(xn, w1c, g, M, Hd, D, bias=b1, act=2, C2=h)
-        w2c, w2T = weights(w2, dtp, any(ctx.needs_input_grad))
+        w2c, w2T = weights(w2, x.dtype, need_t)
         out = torch.empty_like(x)
-        ops.gemm_nt(g, w2c, out, M, D, Hd, bias=b2, row_scale=scale_vec, rs=(rows_per, 1, 1, 0), R=None if exact else x)
-        ctx.save_for_backward(x32 if exact else x, ln_w, mean, rstd, xn, h, g,
-                              scale_vec if scale_vec is not None else x.new_empty(0),
-                              *[t for t in (w1T, w2T) if t is not None])
-        ctx.cfg = (rows_per, scale_vec is not None, w1.shape[0])
+        ops.gemm_nt(g, w2c, out, M, D, Hd, bias=b2, row_scale=scale_vec, rs=(rows_per, 1, 1, 0), R=res)
+        ctx.cfg = (rows_per, scale_vec is not None, Hd)
         ctx.params = (ln_w, ln_b, w1, b1, w2, b2)
-        if exact:
-            ctx.mark_non_differentiable(x32)
-            ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
-            return out, x32
-        return out
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, h, g), scale_vec, (w1T, w2T))
 
     @staticmethod
     def _forward_compact(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, plan, rows_per, xs=None, exact=False):
@@ -710,42 +689,30 @@ class FFNFn(torch.autograd.Function):
         kmap, dmap, sv_k = _plan_maps(plan, rows_per)
         D = x.shape[-1]
         Hd = w1.shape[0]
-        dtp = x.dtype
         Mk = nk * rows_per
         out = torch.empty_like(x)
         need_t = any(ctx.needs_input_grad)
-        w1c, w1T = weights(w1, dtp, need_t)
-        w2c, w2T = weights(w2, dtp, need_t)
-        x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if exact else None
+        w1c, w1T = weights(w1, x.dtype, need_t)
+        w2c, w2T = weights(w2, x.dtype, need_t)
         if nk > 0:
-            xn = _empty((Mk, D), x)
-            mean = _empty((Mk,), x, torch.float32)
-            rstd = _empty((Mk,), x, torch.float32)
-            if exact:
-                ops.layernorm_acc_fwd(xs, x, Mk, D, D, kmap, x32, D, kmap, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
-            else:
-                ops.layernorm_fwd(x, Mk, D, D, kmap, ln_w, ln_b, eps, xn, D, IDENT, mean, rstd)
+            xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, Mk, kmap)
             h = _empty((Mk, Hd), x)
             g = _empty((Mk, Hd), x)
             ops.gemm_nt(xn, w1c, g, Mk, Hd, D, bias=b1, act=2, C2=h)
-            ops.gemm_nt(g, w2c, out, Mk, D, Hd, cmap=kmap, bias=b2, row_scale=sv_k, rs=(rows_per, 1, 1, 0),
-                        R=None if exact else x, rmap=kmap)
-        else:
+            ops.gemm_nt(g, w2c, out, Mk, D, Hd, cmap=kmap, bias=b2, row_scale=sv_k, rs=(rows_per, 1, 1, 0), R=res, rmap=kmap)
+        else:                                        # every clip dropped: nothing to normalise
             xn = mean = rstd = h = g = x.new_empty(0)
+            x32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if exact else None
         if exact:                                    # the dropped clips: the stream moves on, the block contributes nothing
             ops.layernorm_acc_fwd(xs, x, nd * rows_per, D, D, dmap, x32, D, dmap)
             _zero_rows(x, out, nd * rows_per, D, dmap)
         else:
             ops.row_scale_copy(x, out, nd * rows_per, D, smap=dmap, dmap=dmap)
-        ctx.save_for_backward(x32 if exact else x, ln_w, mean, rstd, xn, h, g, buf, *[t for t in (w1T, w2T) if t is not None])
         ctx.cfg = (rows_per, True, Hd)
         ctx.plan = (nk, nd, step_k, step_d)
         ctx.params = (ln_w, ln_b, w1, b1, w2, b2)
-        if exact:
-            ctx.mark_non_differentiable(x32)
-            ctx.set_materialize_grads(False)         # no zero-filled 'gradient' of the float32 stream (0.46 GB per sub-block at 96 clips)
-            return out, x32
-        return out
+        # (the plan's buffer takes the scale vector's place: it holds the scales of the kept clips)
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, h, g), buf, (w1T, w2T))
 
     @staticmethod
     def _backward_compact(ctx, dout):
@@ -758,6 +725,7 @@ class FFNFn(torch.autograd.Function):
         D = x.shape[-1]
         Mk = nk * rows_per
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
+        # (not _prenorm_bwd: the gradient stream is fetched up front, both branches below need it, and one has no LayerNorm)
         dx = torch.empty_like(x)
         g32 = _grad_stream(dout, x_stream)
         dx32 = torch.empty_like(g32) if g32 is not None else None
@@ -765,13 +733,13 @@ class FFNFn(torch.autograd.Function):
         if nk > 0:
             dz = _empty((Mk, D), x)
             ops.row_scale_copy(dout, dz, Mk, D, smap=kmap, s=sv_k, rs=(rows_per, 1, 1, 0))
-            d_w2, d_b2 = _linear_grads(p_w2, p_b2, dz, g, Mk, D, Hd)
+            d_w2, d_b2 = _weight_grads((p_w2, p_b2), dz, g, Mk, D, Hd)
             dh = _empty((Mk, Hd), x)
             ops.gemm_nt(dz, w2T, dh, Mk, Hd, D, dgelu_in=h, dgelu_kind=1)
-            d_w1, d_b1 = _linear_grads(p_w1, p_b1, dh, xn, Mk, Hd, D)
+            d_w1, d_b1 = _weight_grads((p_w1, p_b1), dh, xn, Mk, Hd, D)
             dxn = _empty((Mk, D), x)
             ops.gemm_nt(dh, w1T, dxn, Mk, D, Hd)
-            d_ln_w, d_ln_b, direct = _ln_grad_buffers(p_ln_w, p_ln_b, D, x.device)
+            d_ln_w, d_ln_b, direct = _ln_grad_buffers((p_ln_w, p_ln_b), D, x.device)
             _ln_bwd_res(dxn, x_stream, kmap, Mk, D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
             if direct:
                 _fire(p_ln_w, p_ln_b)
@@ -796,28 +764,19 @@ class FFNFn(torch.autograd.Function):
         dout = _chk(dout)
         D = x.shape[-1]
         M = x.numel() // D
-        dtp = dout.dtype
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
         if has_scale:
             dz = _empty((M, D), x)
             ops.row_scale_copy(dout, dz, M, D, s=sv, rs=(rows_per, 1, 1, 0))
         else:
             dz = dout
-        d_w2, d_b2 = _linear_grads(p_w2, p_b2, dz, g, M, D, Hd)
+        d_w2, d_b2 = _weight_grads((p_w2, p_b2), dz, g, M, D, Hd)
         dh = _empty((M, Hd), x)
         ops.gemm_nt(dz, w2T, dh, M, Hd, D, dgelu_in=h, dgelu_kind=1)
-        d_w1, d_b1 = _linear_grads(p_w1, p_b1, dh, xn, M, Hd, D)
+        d_w1, d_b1 = _weight_grads((p_w1, p_b1), dh, xn, M, Hd, D)
         dxn = _empty((M, D), x)
         ops.gemm_nt(dh, w1T, dxn, M, D, Hd)
-        dx = torch.empty_like(x)
-        g32 = _grad_stream(dout, x_stream)
-        dx32 = torch.empty_like(g32) if g32 is not None else None
-        d_ln_w, d_ln_b, direct = _ln_grad_buffers(p_ln_w, p_ln_b, D, x.device)
-        _ln_bwd_res(dxn, x_stream, IDENT, M, D, mean, rstd, ln_w, dout, dx, d_ln_w, d_ln_b, g32, dx32)
-        if direct:
-            _fire(p_ln_w, p_ln_b)
-            d_ln_w = d_ln_b = None
-        _hand_on(dx, dx32)
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
         return (dx, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, None, None, None, None)
 
 
@@ -894,7 +853,8 @@ class TokensFn(torch.autograd.Function):
             N, nseq = P * Tq, B
         else:
             N, nseq = P, B * Tq
-        d_w = ops.gemm_tn(dx, rows, nseq * N, D, K, amap=ops.tokmap(N)).reshape(w_shape)
+        d_w, _ = _weight_grads(None, dx, rows, nseq * N, D, K, bias=False, amap=ops.tokmap(N))   # (params None: as in PatchEmbedFn)
+        d_w = d_w.reshape(w_shape)
         # dE[n,:] = sum over sequences of dx[s, 1+n, :]
         dE = ops.reduce_rows(dx, N, nseq, D, D, 1, 1 + N, 1)
         d_b = ops.reduce_rows(dE, 1, N, D, D, 0, 1, 0).reshape(D)
@@ -938,7 +898,8 @@ class PatchEmbedFn(torch.autograd.Function):
         (rows,) = ctx.saved_tensors
         M, D, K, w_shape = ctx.cfg
         dy = _chk(dy).reshape(M, D)
-        d_w, d_b = ops.gemm_tn(dy, rows, M, D, K, want_colsum=True)
+        # (params None: the gradients go to autograd even with direct gradients on -- the status quo, not a decision)
+        d_w, d_b = _weight_grads(None, dy, rows, M, D, K)
         d_w = d_w.reshape(w_shape)
         return None, d_w, d_b, None
 
@@ -1045,11 +1006,10 @@ class LinearFn(torch.autograd.Function):
         if N8 != N:
             dy = torch.nn.functional.pad(dy, (0, N8 - N))
         dy = _chk(dy)
-        if ctx.has_bias:
-            d_w, d_b = ops.gemm_tn(dy, x, M, N8, K, want_colsum=True)
+        # (params None: the gradients go to autograd even with direct gradients on -- the status quo, not a decision)
+        d_w, d_b = _weight_grads(None, dy, x, M, N8, K, bias=ctx.has_bias)
+        if d_b is not None:
             d_b = d_b[:N]
-        else:
-            d_w, d_b = ops.gemm_tn(dy, x, M, N8, K), None
         dx = torch.empty_like(x)
         ops.gemm_nt(dy, wT, dx, M, K, N8)
         return dx, d_w[:N], d_b
@@ -1431,7 +1391,8 @@ class ConvStemFn(torch.autograd.Function):
         (rows,) = ctx.saved_tensors
         M, D, K, Kp, w_shape = ctx.cfg
         dy = _chk(dy).reshape(M, D)
-        d_w, d_b = ops.gemm_tn(dy, rows, M, D, Kp, want_colsum=True)
+        # (params None: the gradients go to autograd even with direct gradients on -- the status quo, not a decision)
+        d_w, d_b = _weight_grads(None, dy, rows, M, D, Kp)
         return None, d_w[:, :K].reshape(w_shape), d_b, None, None, None
 
 
@@ -1470,10 +1431,8 @@ class LinearActResFn(torch.autograd.Function):
             ops.gelu_grad_mul(dy, h, dz)
         else:
             dz = dy
-        if has_bias:
-            d_w, d_b = ops.gemm_tn(dz, x, M, N, K, want_colsum=True)
-        else:
-            d_w, d_b = ops.gemm_tn(dz, x, M, N, K), None
+        # (params None: the gradients go to autograd even with direct gradients on -- the status quo, not a decision)
+        d_w, d_b = _weight_grads(None, dz, x, M, N, K, bias=has_bias)
         dx = torch.empty_like(x)
         ops.gemm_nt(dz, wT, dx, M, K, N)
         return dx, d_w, d_b, None, (dy.reshape(x.shape[:-1] + (N,)) if has_res else None)
@@ -1511,16 +1470,11 @@ class MlpFn(torch.autograd.Function):
         K = x.shape[-1]
         M = x.numel() // K
         dy = _chk(dy).reshape(M, N)
-        if has_b2:
-            d_w2, d_b2 = ops.gemm_tn(dy, g, M, N, Hd, want_colsum=True)
-        else:
-            d_w2, d_b2 = ops.gemm_tn(dy, g, M, N, Hd), None
+        # (params None, twice: the gradients go to autograd even with direct gradients on -- the status quo, not a decision)
+        d_w2, d_b2 = _weight_grads(None, dy, g, M, N, Hd, bias=has_b2)
         dh = _empty((M, Hd), x)
         ops.gemm_nt(dy, w2T, dh, M, Hd, N, dgelu_in=gp, dgelu_kind=1)
-        if has_b1:
-            d_w1, d_b1 = ops.gemm_tn(dh, x, M, Hd, K, want_colsum=True)
-        else:
-            d_w1, d_b1 = ops.gemm_tn(dh, x, M, Hd, K), None
+        d_w1, d_b1 = _weight_grads(None, dh, x, M, Hd, K, bias=has_b1)
         dx = torch.empty_like(x)
         ops.gemm_nt(dh, w1T, dx, M, K, Hd)
         return dx, d_w1, d_b1, d_w2, d_b2, (dy.reshape(x.shape[:-1] + (N,)) if has_res else None)
