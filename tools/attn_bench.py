@@ -5,6 +5,10 @@
                                                                 joint space-time (contig, S = clips, L = 1569) and the spatial
                                                                 attention of a 448^2, 16-frame model (space, T = 16, P = 784),
                                                                 e.g.  python tools/attn_bench.py long 8 attn_long=0
+    python tools/attn_bench.py long f32 [clips] [option=value ...]  the same shapes with fp32 tensors (the path outside autocast)
+                                                                plus the 224^2 spatial attention of 96 clips (S = 768, L = 197);
+                                                                share of the fp32 matrix roof (157.3 TFLOP/s),
+                                                                e.g.  python tools/attn_bench.py long f32 8 attn_f32=valu
 """
 import os
 import sys
@@ -33,10 +37,11 @@ def timeit(fn, iters=20, warm=3):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
-def long_shapes(B, H=12, hd=64):
+def long_shapes(B, H=12, hd=64, f32=False):
     """Time and achieved TFLOP/s (forward 4 S H L^2 hd, backward 10 S H L^2 hd: the formulas of vtx/ops.py) and the share of the
-    dense bf16 roof bench.py uses (2500 TFLOP/s)."""
-    bf, D = torch.bfloat16, H * hd
+    dense bf16 roof bench.py uses (2500 TFLOP/s) -- fp32 tensors: of the fp32 matrix roof (157.3 TFLOP/s)."""
+    bf, D = torch.float32 if f32 else torch.bfloat16, H * hd
+    roof = 157.3 if f32 else 2500.0
     r = lambda *s: (torch.randn(*s, device=DEV) * 0.5).to(bf)   # noqa: E731
     rows = []
     S, L = B, 1569
@@ -59,8 +64,21 @@ def long_shapes(B, H=12, hd=64):
     rows.append((f'attn fwd spatial S={S} L={L}', t, 4.0 * S * H * L * L * hd))
     t = timeit(lambda: ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, S, L, H, hd, hd ** -0.5, B, T, P, dqkv_cls=dcls), iters=10)
     rows.append((f'attn bwd spatial S={S} L={L}', t, 10.0 * S * H * L * L * hd))
+    if f32:                                                      # the 224^2 model: 96 clips of 8 frames, 197 tokens per frame
+        del qkv, o, do, lse, dqkv, dcls
+        B2, T, P = 96, 8, 196
+        S, L, N = B2 * T, P + 1, P * T
+        M1, Mo = B2 * (N + 1), B2 * N + B2 * T
+        qkv, o, do = r(M1, 3 * D), torch.empty(Mo, D, device=DEV, dtype=bf), r(Mo, D)
+        lse = torch.empty(S * H * L, device=DEV)
+        dqkv = torch.empty(M1, 3 * D, device=DEV, dtype=bf)
+        dcls = torch.empty(B2 * T, 3 * D, device=DEV, dtype=bf)
+        t = timeit(lambda: ops.attn_fwd(qkv, o, lse, ATTN_SPACE, S, L, H, hd, hd ** -0.5, B2, T, P), iters=10)
+        rows.append((f'attn fwd spatial S={S} L={L}', t, 4.0 * S * H * L * L * hd))
+        t = timeit(lambda: ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, S, L, H, hd, hd ** -0.5, B2, T, P, dqkv_cls=dcls), iters=10)
+        rows.append((f'attn bwd spatial S={S} L={L}', t, 10.0 * S * H * L * L * hd))
     for name, t, fl in rows:
-        print(f'{name:30s} {t * 1e3:9.3f} ms  {fl / t / 1e12:7.1f} TFLOP/s  {fl / t / 1e12 / 2500.0 * 100:5.2f} % of 2500', flush=True)
+        print(f'{name:30s} {t * 1e3:9.3f} ms  {fl / t / 1e12:7.1f} TFLOP/s  {fl / t / 1e12 / roof * 100:5.2f} % of {roof:g}', flush=True)
 
 
 def main():
@@ -71,9 +89,12 @@ def main():
             vtx.set_option(k, v)
     if 'long' in args:
         args.remove('long')
+        f32 = 'f32' in args
+        if f32:
+            args.remove('f32')
         B = int(args[0]) if args else 8
-        print(f'clips {B}; options ' + ' '.join(a for a in sys.argv[1:] if '=' in a))
-        long_shapes(B)
+        print(f'clips {B}; {"fp32" if f32 else "bf16"} tensors; options ' + ' '.join(a for a in sys.argv[1:] if '=' in a))
+        long_shapes(B, f32=f32)
         return
     B = int(args[0]) if args else 96
     T, P, D, H = 8, 196, 768, 12

@@ -140,9 +140,70 @@ def check_plain(obj, names):
     return bad
 
 
+F32_ATTENTION = {'attn_fwd_f32_kernel': 128, 'attn_bwd_dq_f32_kernel': 192, 'attn_bwd_dkv_f32_kernel': 256}
+READELF = '/opt/rocm/lib/llvm/bin/llvm-readelf'
+
+
+def spill_counts(obj):
+    """{kernel symbol: (spilled scalar registers, spilled vector registers, scratch bytes)} from the code object's metadata."""
+    tmp = tempfile.mkdtemp()
+    try:
+        local = os.path.join(tmp, 'k.o')
+        shutil.copy(obj, local)
+        subprocess.run([OBJDUMP, '--offloading', local], cwd=tmp, capture_output=True, check=False)
+        dev = [f for f in os.listdir(tmp) if 'amdgcn' in f]
+        if not dev:
+            raise RuntimeError('no device code object found in ' + obj)
+        notes = subprocess.run([READELF, '--notes', os.path.join(tmp, dev[0])], capture_output=True, text=True, check=True).stdout
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    out = {}
+    for block in notes.split('- .agpr_count:')[1:]:
+        f = dict((k, v) for k, v in re.findall(r'\.(name|sgpr_spill_count|vgpr_spill_count|private_segment_fixed_size):\s*(\S+)', block))
+        out[f['name']] = (int(f['sgpr_spill_count']), int(f['vgpr_spill_count']), int(f['private_segment_fixed_size']))
+    return out
+
+
+def check_f32_attention(obj):
+    """The exact-fp32 attention kernels (csrc/attn_f32.hip): the three kernels are there, every matrix instruction is
+    v_mfma_f32_32x32x2_f32 (fp32 operands: no bf16, no reduced-precision form) and there are at least the MFMAs of one unrolled
+    chunk of two 32-row tiles (forward 2 x 64, dq 2 x 96, dk / dv 2 x 128; the compiler may peel a copy, in whole tiles of 32),
+    no scratch traffic, no spilled register, no instruction of the scalar unit that writes memory."""
+    ks = dict((n, b) for n, b in kernels(disassemble(obj)))
+    spills = spill_counts(obj) if os.path.exists(READELF) else {}
+    bad = []
+    writes = re.compile(r'\bs_\w*(?:store|atomic|dcache)\w*')
+    for want, n_min in F32_ATTENTION.items():
+        hit = [n for n in ks if want in n]
+        if not hit:
+            bad.append(f'{want}: kernel not found')
+            continue
+        text = '\n'.join(ks[hit[0]])
+        mfma = re.findall(r'\bv_mfma_\w+', text)
+        n_f32 = sum(1 for m in mfma if m == 'v_mfma_f32_32x32x2_f32')
+        mine = []
+        if 'scratch_' in text:
+            mine.append('scratch traffic')
+        if n_f32 != len(mfma):
+            mine.append(f'{len(mfma) - n_f32} matrix instructions other than v_mfma_f32_32x32x2_f32')
+        if n_f32 < n_min or n_f32 % 32:
+            mine.append(f'{n_f32} MFMAs, expected a multiple of 32 and at least {n_min}')
+        m = writes.search(text)
+        if m:
+            mine.append(f'scalar memory write {m.group(0)}')
+        sp = [v for k, v in spills.items() if want in k]
+        if sp and any(sp[0]):
+            mine.append(f'spills (sgpr, vgpr, scratch bytes) = {sp[0]}')
+        print(f'{want}: {len(ks[hit[0]])} lines, {n_f32} MFMA, spills {sp[0] if sp else "n/a"}: {"ok" if not mine else "FAIL"}')
+        bad += [f'{want}: {x}' for x in mine]
+    return bad
+
+
 if __name__ == '__main__':
     obj = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'gemm_nt.o')
-    if os.path.basename(obj) == 'attn_long.o':
+    if os.path.basename(obj) == 'attn_f32.o':
+        bad = check_f32_attention(obj)
+    elif os.path.basename(obj) == 'attn_long.o':
         bad = check_plain(obj, ['attn_fwd_long_kernel', 'attn_bwd_dq_long_kernel', 'attn_bwd_dkv_long_kernel'])
     else:
         bad = check(obj)
@@ -150,6 +211,7 @@ if __name__ == '__main__':
         bad += check_tn_w4(os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'gemm_tn.o'))
         bad += check_plain(os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'attn_long.o'),
                            ['attn_fwd_long_kernel', 'attn_bwd_dq_long_kernel', 'attn_bwd_dkv_long_kernel'])
+        bad += check_f32_attention(os.path.join(ROOT, 'videotransformer-pytorch_amd', 'csrc', '_obj', 'attn_f32.o'))
     for b in bad:
         print('VIOLATION', b)
     sys.exit(1 if bad else 0)

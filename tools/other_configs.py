@@ -23,11 +23,11 @@ import video_transformer as V
 DEV = torch.device('cuda', 0)
 
 
-def train(name, model, batch, frames, flops_per_clip, steps=6, warmup=2, recompute=False):
+def train(name, model, batch, frames, flops_per_clip, steps=6, warmup=2, recompute=False, precision='bf16'):
     """fwd + cross-entropy + bwd + fused SGD-nesterov exactly as bench.py does it (gradient buckets with direct
     parameter gradients), bf16 path, synthetic clips resident in HBM."""
     from vtx import dp, optim
-    vtx.set_precision('bf16')
+    vtx.set_precision(precision)                     # 'fp32': the path outside torch.autocast
     vtx.set_recompute(recompute)
     torch.manual_seed(0)
     torch.cuda.reset_peak_memory_stats()
@@ -64,6 +64,7 @@ def train(name, model, batch, frames, flops_per_clip, steps=6, warmup=2, recompu
     finally:
         buckets.remove()
         vtx.set_recompute(False)
+        vtx.set_precision('auto')
         del m, head, params, opt, x
         torch.cuda.empty_cache()
 
@@ -125,12 +126,13 @@ def hog(frames_n=1024, iters=10):
     print(json.dumps(res), flush=True)
 
 
-def timesformer_joint(batch=8):
+def timesformer_joint(batch=8, precision='bf16'):
     # TimeSformer-B joint_space_time: one sequence of 1 + 196 * 8 = 1569 tokens per clip (csrc/attn_long.hip).  Per clip,
     # 12 layers: linear layers 2 * 1569 * 12 * 768^2 * 12 = 0.267 TFLOP, attention core 4 * 1569^2 * 64 * 12 * 12 = 0.091 TFLOP
-    # forward; x 3 for forward + backward.
-    train('TimeSformer-B joint_space_time, 8x3x224x224, bf16, fwd+CE+bwd+SGD',
-          V.TimeSformer(num_frames=8, attention_type='joint_space_time'), batch, 8, 3 * (0.267e12 + 0.091e12))
+    # forward; x 3 for forward + backward.  `tsfjoint fp32`: the same step in fp32 (csrc/attn_f32.hip; mfma_frac stays relative to
+    # the bf16 roof).
+    train(f'TimeSformer-B joint_space_time, 8x3x224x224, {precision}, fwd+CE+bwd+SGD',
+          V.TimeSformer(num_frames=8, attention_type='joint_space_time'), batch, 8, 3 * (0.267e12 + 0.091e12), precision=precision)
 
 
 if __name__ == '__main__':
@@ -138,7 +140,7 @@ if __name__ == '__main__':
         vtx.set_option(*a.split('='))
     which = [a for a in sys.argv[1:] if '=' not in a] or ['hog', 'vivit', 'tsf16', 'tsfl96']
     if 'tsfjoint' in which:
-        timesformer_joint()
+        timesformer_joint(precision='fp32' if 'fp32' in which else 'bf16')
     if 'hog' in which:
         hog()
     if 'vivit' in which:

@@ -28,6 +28,7 @@ int check_launch(const char* what) {
 
 // ---- options -------------------------------------------------------------------------
 static const char* const kNtNames[] = {"auto", "pp256", "dma2", "ring128x3", "ring128x4k32", "ring256x3", "ring256x3k32", "ring256x4k32"};
+static const char* const kAttnF32Names[] = {"valu", "mfma"};
 static const char* const kTnNames[] = {"auto", "pp256", "ring", "dma2", "w4"};
 
 static int parse_enum(const char* v, const char* const* names, int n) {
@@ -45,6 +46,7 @@ static int set_option(Options& o, const char* name, const char* value) {
   if (strcmp(name, "tn_cus") == 0) { const int g = atoi(value); if (g < 32 || g > 1024) return VTX_EINVAL; o.tn_cus = g; return VTX_OK; }
   if (strcmp(name, "attn_valu") == 0) { o.attn_valu = atoi(value) != 0; return VTX_OK; }
   if (strcmp(name, "attn_long") == 0) { o.attn_long = atoi(value) != 0; return VTX_OK; }
+  if (strcmp(name, "attn_f32") == 0) { const int e = parse_enum(value, kAttnF32Names, 2); if (e < 0) return VTX_EINVAL; o.attn_f32 = e; return VTX_OK; }
   if (strcmp(name, "attn_hw_fwd") == 0) { const int g = atoi(value); if (g < 0) return VTX_EINVAL; o.attn_hw_fwd = g; return VTX_OK; }
   if (strcmp(name, "attn_hw_bwd") == 0) { const int g = atoi(value); if (g < 0) return VTX_EINVAL; o.attn_hw_bwd = g; return VTX_OK; }
   if (strcmp(name, "attn_fused") == 0) { const int v = atoi(value); o.attn_fused = v < 0 ? 0 : v > 2 ? 2 : v; return VTX_OK; }
@@ -63,7 +65,7 @@ Options& options() {
   static Options o = [] {
     Options d;
     static const char* const env[][2] = {{"VTX_GEMM_NT", "gemm_nt"}, {"VTX_GEMM_TN", "gemm_tn"}, {"VTX_GEMM_NODMA", "gemm_nodma"},
-                                         {"VTX_TN_SAFE", "tn_safe"}, {"VTX_TN_CUS", "tn_cus"}, {"VTX_ATTN_VALU", "attn_valu"}, {"VTX_ATTN_LONG", "attn_long"}, {"VTX_GEMM_PP_GRID", "pp_grid"},
+                                         {"VTX_TN_SAFE", "tn_safe"}, {"VTX_TN_CUS", "tn_cus"}, {"VTX_ATTN_VALU", "attn_valu"}, {"VTX_ATTN_LONG", "attn_long"}, {"VTX_ATTN_F32", "attn_f32"}, {"VTX_GEMM_PP_GRID", "pp_grid"},
                                          {"VTX_GEMM_PP_CG", "pp_cg"}, {"VTX_GEMM_PP_EPI", "pp_epi"},
                                          {"VTX_GEMM_PP_CONT", "pp_cont"}, {"VTX_LN_ROWS", "ln_rows"}, {"VTX_ATTN_HW_FWD", "attn_hw_fwd"}, {"VTX_ATTN_HW_BWD", "attn_hw_bwd"}, {"VTX_ATTN_DKV", "attn_dkv"}, {"VTX_ATTN_FWD_STREAM", "attn_fwd_stream"},
                                          {"VTX_ATTN_FUSED", "attn_fused"}};
@@ -116,7 +118,7 @@ int hog_selftest(int* bad_mag, int* bad_bin);     // hog.hip
 
 using namespace vtx;
 
-extern "C" int vtx_version(void) { return 220; }  // 0.2.2: vtx_layernorm_acc_fwd / VTX_BF16_X32 (exact residual stream); 0.2.1: vtx_hog_fwd takes the size of the table blob
+extern "C" int vtx_version(void) { return 230; }  // 0.2.3: option attn_f32 (exact-fp32 MFMA attention, csrc/attn_f32.hip); 0.2.2: vtx_layernorm_acc_fwd / VTX_BF16_X32 (exact residual stream); 0.2.1: vtx_hog_fwd takes the size of the table blob
 
 extern "C" int vtx_set_option(const char* name, const char* value) {
   const int rc = set_option(options(), name, value);

@@ -12,8 +12,9 @@
 // workgroup; long ones use one sequence per workgroup and 64-key tiles.  bf16 with
 // head_dim 64 never gets here by default: <= 32 and 33..256 tokens (L = 197 spatial)
 // run the MFMA kernels of attn_mfma.hip, more than 256 (785 spatial at 448^2, 1569
-// joint) those of attn_long.hip; these kernels are the fp32 path, the `probs` pass
-// and what attn_valu=1 / attn_long=0 select.  Algorithmic bytes per (sequence, head):
+// joint) those of attn_long.hip; fp32 with head_dim 64 and more than 32 tokens runs the exact-fp32 MFMA kernels of
+// attn_f32.hip.  These kernels are the fp32 path of up to 32 tokens, the `probs` pass (and the forward in front of it)
+// and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  Algorithmic bytes per (sequence, head):
 // read 3*L*hd, write L*hd elements (+ L fp32 lse).
 #include <stdlib.h>
 #include "attn_common.h"
@@ -312,6 +313,13 @@ static bool use_long(int dtype, int L, int hd) {
   return attn_long_eligible(dtype, L, hd);
 }
 
+// fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu (or attn_valu=1) sends them
+// back here, and so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
+static bool use_f32(int dtype, int L, int hd, bool probs) {
+  if (options().attn_valu || !options().attn_f32 || probs) return false;
+  return attn_f32_eligible(dtype, L, hd);
+}
+
 static bool use_small(int dtype, int mode, int L, int hd) {
   if (options().attn_valu) return false;
   return attn_small_eligible(dtype, mode, L, hd);
@@ -363,6 +371,8 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
     rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st);
   } else if (use_long(d->dtype, d->L, d->hd)) {
     rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st);
+  } else if (use_f32(d->dtype, d->L, d->hd, d->probs != nullptr)) {
+    rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st);
   } else {
     if (d->dtype == VTX_F32)
       hipLaunchKernelGGL((attn_fwd_kernel<float, 64, 0>), grid, block, lds, st, p, (const float*)d->qkv, (float*)d->out, d->lse, nullptr);
@@ -396,6 +406,8 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
     return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
   if (use_long(d->f.dtype, d->f.L, d->f.hd))
     return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+  if (use_f32(d->f.dtype, d->f.L, d->f.hd, false))
+    return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
   if (d->f.dtype == VTX_F32) {
     hipLaunchKernelGGL((attn_bwd_dq_kernel<float, 64>), grid, block, lds_a, st, p, (const float*)d->f.qkv, (const float*)d->f.out,
                        (const float*)d->dout, d->f.lse, d->delta, (float*)d->dqkv, (float*)d->dqkv_cls);

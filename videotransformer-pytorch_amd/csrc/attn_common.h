@@ -1,4 +1,4 @@
-// attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip and attn_long.hip,
+// attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip, attn_long.hip and attn_f32.hip,
 // and the swizzled-LDS / MFMA fragment helpers of the two bf16 MFMA families.
 #pragma once
 #include "common.h"
@@ -247,5 +247,10 @@ bool attn_long_eligible(int dtype, int L, int hd);
 int attn_fwd_long_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_long_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                          float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);
+// attn_f32.hip
+bool attn_f32_eligible(int dtype, int L, int hd);
+int attn_fwd_f32_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
+int attn_bwd_f32_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
+                        float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);
 
 }  // namespace vtx
