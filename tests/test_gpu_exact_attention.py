@@ -71,7 +71,7 @@ def _dt(dtype):
 
 
 def _mfma_path(c, dtype, valu):
-    """Whether vtx_attn_* takes the bf16 MFMA kernels (attn.hip: use_small / use_mfma)."""
+    """Whether vtx_attn_* takes the bf16 MFMA kernels (attn.hip: attn_route, SMALL / MFMA)."""
     if dtype != BF16 or valu:
         return False
     return c.L <= 256 and (c.layout == 'contig' or c.L > 32)

@@ -1,6 +1,6 @@
-"""The exact-fp32 MFMA attention kernels (csrc/attn_f32.hip: attn_fwd_f32_kernel, attn_bwd_dq_f32_kernel,
-attn_bwd_dkv_f32_kernel): fp32 inputs, head_dim 64, more than 32 tokens, VTX_ATTN_CONTIG and VTX_ATTN_SPACE; option
-attn_f32 = mfma (default) | valu.
+"""The exact-fp32 MFMA attention kernels (attn_fwd_f32_kernel, attn_bwd_dq_f32_kernel, attn_bwd_dkv_f32_kernel: the
+chunk-streaming kernels of csrc/attn_stream.h with the fp32 tile policy of csrc/attn_f32.hip): fp32 inputs, head_dim 64,
+more than 32 tokens, VTX_ATTN_CONTIG and VTX_ATTN_SPACE; option attn_f32 = mfma (default) | valu.
 
   1. exact arithmetic (tests/exact_attn.py, runners of tests/test_gpu_exact_attention.py) by that module's standard for
      kernels whose probabilities stay in fp32: out equals the exact value bit for bit, lse exactly 0 for one winner and within
@@ -12,23 +12,19 @@ attn_f32 = mfma (default) | valu.
   3. random data against the float64 restatement of tests/test_gpu_kernels.py at the joint (8 x 1569 x 12), the 448^2 spatial
      (2 x 4 x 784) and the 224^2 spatial (4 x 8 x 196) shapes with the metric and the fp32 bars that module holds the fp32 VALU
      attention to: TOL[fp32] on out, 1e-4 on lse, 2 TOL[fp32] on dqkv and the per-frame cls rows;
-  4. attn_f32=mfma against attn_f32=valu on those shapes within the same bars, and attn_f32=valu bit-identical to a build of
-     the parent commit when VTX_PARENT_LIB names one (skipped otherwise);
+  4. attn_f32=mfma against attn_f32=valu on those shapes within the same bars, and attn_f32=valu as well as attn_f32=mfma
+     bit-identical to a build of the parent commit when VTX_PARENT_LIB names one (skipped otherwise);
   5. a joint space-time TimeSformer and a divided one, fp32 forward + backward, mfma against valu within the fp32 model bars
      of tests/helpers.py;
   6. one bf16 case of each existing route (<= 32 tokens, 197, 1569, attn_valu=1) is bit-identical with attn_f32 at either value.
 """
-import os
-import subprocess
-import sys
-
 import pytest
 import torch
 
 import test_gpu_exact_attention as E
-from helpers import ROOT, TOL_F32, check, l2err, report
+from helpers import TOL_F32, check, l2err, report
 from test_gpu_kernels import TOL, _attn_ref, dev, q, rnd
-from test_gpu_long_attention import _ref_lse
+from test_gpu_long_attention import _ref_lse, assert_parent_bit_for_bit
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -48,7 +44,7 @@ def attn_f32():
 
 
 def run_f32(c):
-    assert c.hd == 64 and c.L > 32                                      # attn.hip: use_f32
+    assert c.hd == 64 and c.L > 32                                      # attn.hip: attn_route
     qkv, out, lse = E.run_fwd(c, F32)
     res = (out, lse)
     if c.bwd:
@@ -193,50 +189,30 @@ def test_f32_space_vs_float64_and_valu(B, T, P, attn_f32):
         check(f'attn f32 {tag} bwd {name} vs f64', full.cpu(), qq.grad.cpu(), 2 * TOL[F32])
 
 
-# what a build of the parent commit computes for the shapes below, in a child process (a process loads one library)
-_PARENT_JOB = r'''
-import sys, torch
-sys.path[:0] = sys.argv[1:4]
-import test_gpu_f32_attention as F
-res = {}
-for S, L, H in F.PARENT_CONTIG:
-    qkv, do = F._contig_inputs(S, L, H)
-    res[f'contig {S} {L} {H}'] = [t.cpu() for t in F._run_contig(F.dev(qkv, F.F32), F.dev(do, F.F32), S, L, H)]
-for B, T, P, H in F.PARENT_SPACE:
-    qkv, dt, dc = F._space_inputs(B, T, P, H)
-    dout = torch.cat([dt.reshape(B * P * T, H * 64), dc], 0)
-    res[f'space {B} {T} {P} {H}'] = [t.cpu() for t in F._run_space(F.dev(qkv, F.F32), F.dev(dout, F.F32), B, T, P, H)]
-torch.save(res, sys.argv[4])
-'''
 PARENT_CONTIG = [(2, 197, 3), (2, 1569, 3)]
 PARENT_SPACE = [(2, 2, 196, 3), (1, 2, 784, 3)]
 
 
 def test_f32_valu_is_the_parent_bit_for_bit(attn_f32, tmp_path):
-    """attn_f32=valu against a libvtx.so built from the parent commit, named by VTX_PARENT_LIB."""
-    parent = os.environ.get('VTX_PARENT_LIB', '')
-    if not parent or not os.path.isfile(parent):
-        print('skipped: VTX_PARENT_LIB does not name a library built from the parent commit')
-        pytest.skip('VTX_PARENT_LIB does not name a library built from the parent commit')
-    out = str(tmp_path / 'parent.pt')
-    env = dict(os.environ, VTX_LIB=os.path.abspath(parent))
-    env.pop('VTX_ATTN_F32', None)
-    subprocess.run([sys.executable, '-c', _PARENT_JOB, ROOT, os.path.join(ROOT, 'videotransformer-pytorch_amd'),
-                    os.path.join(ROOT, 'tests'), out], check=True, env=env, timeout=600)
-    want = torch.load(out)
-    attn_f32('valu')
-    for S, L, H in PARENT_CONTIG:
-        qkv, do = _contig_inputs(S, L, H)
-        got = _run_contig(dev(qkv, F32), dev(do, F32), S, L, H)
-        for a, b in zip(got, want[f'contig {S} {L} {H}']):
-            assert torch.equal(_bits(a.cpu()), _bits(b)), f'contig {S}x{L}x{H}: attn_f32=valu differs from the parent'
-    for B, T, P, H in PARENT_SPACE:
-        qkv, dt, dc = _space_inputs(B, T, P, H)
-        dout = torch.cat([dt.reshape(B * P * T, H * 64), dc], 0)
-        got = _run_space(dev(qkv, F32), dev(dout, F32), B, T, P, H)
-        for a, b in zip(got, want[f'space {B} {T} {P} {H}']):
-            assert torch.equal(_bits(a.cpu()), _bits(b)), f'space {B}x{T}x{P}x{H}: attn_f32=valu differs from the parent'
-    report(f'ok   attn_f32=valu bit-identical to {os.path.basename(parent)} on {len(PARENT_CONTIG) + len(PARENT_SPACE)} shapes')
+    """attn_f32=valu against a libvtx.so built from the parent commit, named by VTX_PARENT_LIB (both builds are told
+    attn_f32=valu: the parent's default is the MFMA route as well)."""
+    spec = dict(dtype='float32', options={'attn_f32': 'valu'}, contig=PARENT_CONTIG, space=PARENT_SPACE)
+    try:
+        assert_parent_bit_for_bit(spec, tmp_path, 'attn_f32=valu')
+    finally:
+        attn_f32('mfma')
+
+
+def test_f32_mfma_is_the_parent_bit_for_bit(attn_f32, tmp_path):
+    """The default fp32 route (attn_f32=mfma) against a libvtx.so built from the parent commit, named by VTX_PARENT_LIB:
+    one ragged chunk (33), full chunks only (128), several + a tail (197), 24 chunks + a tail and an idle wave (1569), and the
+    cls row of the space layout."""
+    spec = dict(dtype='float32', options={'attn_f32': 'mfma'}, contig=[(2, 33, 3), (2, 128, 3), (2, 197, 3), (2, 1569, 3)],
+                space=[(1, 2, 784, 3), (2, 2, 196, 3)])
+    try:
+        assert_parent_bit_for_bit(spec, tmp_path, 'attn_f32=mfma')
+    finally:
+        attn_f32('mfma')
 
 
 # ------------------------------------------------------------------------------------------------ 5. models

@@ -1,5 +1,6 @@
-"""The bf16 MFMA attention kernels for more than 256 tokens (csrc/attn_long.hip: attn_fwd_long_kernel,
-attn_bwd_dq_long_kernel, attn_bwd_dkv_long_kernel), VTX_ATTN_CONTIG and VTX_ATTN_SPACE.
+"""The bf16 MFMA attention kernels for more than 256 tokens (attn_fwd_long_kernel, attn_bwd_dq_long_kernel,
+attn_bwd_dkv_long_kernel: the chunk-streaming kernels of csrc/attn_stream.h with the bf16 tile policy of csrc/attn_long.hip),
+VTX_ATTN_CONTIG and VTX_ATTN_SPACE.
 
   1. exact arithmetic (tests/exact_attn.py, runners of tests/test_gpu_exact_attention.py): every output equals RNE(exact) --
      the MFMA standard of that module, which its own _mfma_path only grants up to 256 tokens; lse exactly 0 for one winner,
@@ -11,16 +12,22 @@ attn_bwd_dq_long_kernel, attn_bwd_dkv_long_kernel), VTX_ATTN_CONTIG and VTX_ATTN
      spatial (2 x 4 x 784, 12 heads) shapes, with the metric and bars that module holds the <= 256-token MFMA kernels to:
      TOL[bf16] on out, 1e-4 on lse, 2 TOL[bf16] on dqkv and the per-frame cls rows;
   4. attn_long=1 against attn_long=0 (two implementations of one op: 1e-2 / 1e-4 / 2e-2), and attn_long=0 bit-identical to
-     attn_valu=1 (the fallback is the old path);
+     attn_valu=1 (the fallback is the old path); attn_long=1 bit-identical to a build of the parent commit when VTX_PARENT_LIB
+     names one (skipped otherwise): out, lse, dqkv and the per-frame cls rows;
   5. a joint space-time TimeSformer and a divided one whose spatial sequence has 401 tokens, bf16 forward + backward,
      attn_long=1 against attn_long=0 within the bf16 model bars of tests/helpers.py.
 """
+import json
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
 import exact_attn as A
 import test_gpu_exact_attention as E
-from helpers import TOL_BF16, TOL_BF16_GRAD, check, l2err, report
+from helpers import ROOT, TOL_BF16, TOL_BF16_GRAD, check, l2err, report
 from test_gpu_kernels import TOL, _attn_ref, dev, q, rnd
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +47,7 @@ def attn_long():
 
 
 def _long_mfma_path(c, dtype):
-    """Whether vtx_attn_* takes the kernels of attn_long.hip at default options (attn.hip: use_long)."""
+    """Whether vtx_attn_* takes the kernels of attn_long.hip at default options (attn.hip: attn_route)."""
     return dtype == BF16 and c.hd == 64 and c.L > 256
 
 
@@ -159,28 +166,29 @@ def test_long_space_vs_float64_at_448_scale():
 
 
 # ------------------------------------------------------------------------------------------------ 4. long vs VALU
-def _run_contig(qkv, do, S, L, H):
+def _run_contig(qkv, do, S, L, H, dtype=BF16):
     from vtx import ops
     from vtx._lib import ATTN_CONTIG
     hd, D = 64, H * 64
-    o = torch.full((S, L, D), float('nan'), dtype=BF16, device=DEV)
+    o = torch.full((S, L, D), float('nan'), dtype=dtype, device=DEV)
     lse = torch.full((S * H * L,), float('nan'), device=DEV)
     ops.attn_fwd(qkv, o, lse, ATTN_CONTIG, S, L, H, hd, hd ** -0.5)
-    dqkv = torch.full((S, L, 3 * D), float('nan'), dtype=BF16, device=DEV)
+    dqkv = torch.full((S, L, 3 * D), float('nan'), dtype=dtype, device=DEV)
     ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, S, L, H, hd, hd ** -0.5)
     torch.cuda.synchronize()
     return o, lse, dqkv
 
 
-def _run_space(qkv, do, B, T, P, H):
+def _run_space(qkv, do, B, T, P, H, dtype=BF16):
+    """(out, lse, dqkv before cls_qkv_reduce, per-frame cls rows)"""
     from vtx import ops
     from vtx._lib import ATTN_SPACE
     hd, D, N, L = 64, H * 64, P * T, P + 1
-    o = torch.full((B * N + B * T, D), float('nan'), dtype=BF16, device=DEV)
+    o = torch.full((B * N + B * T, D), float('nan'), dtype=dtype, device=DEV)
     lse = torch.full((B * T * H * L,), float('nan'), device=DEV)
     ops.attn_fwd(qkv, o, lse, ATTN_SPACE, B * T, L, H, hd, hd ** -0.5, B, T, P)
-    dqkv = torch.zeros(B, 1 + N, 3 * D, dtype=BF16, device=DEV)
-    dcls = torch.full((B * T, 3 * D), float('nan'), dtype=BF16, device=DEV)
+    dqkv = torch.zeros(B, 1 + N, 3 * D, dtype=dtype, device=DEV)
+    dcls = torch.full((B * T, 3 * D), float('nan'), dtype=dtype, device=DEV)
     ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, B * T, L, H, hd, hd ** -0.5, B, T, P, dqkv_cls=dcls)
     torch.cuda.synchronize()
     return o, lse, dqkv, dcls
@@ -212,6 +220,72 @@ def test_long_matches_valu_and_fallback_is_the_old_path(shape, attn_long, vtx_op
     bars = (1e-2, 1e-4, 2e-2, 2e-2)
     for what, a, b, bar in zip(('out', 'lse', 'dqkv', 'dqkv_cls'), new, old, bars):
         check(f'attn long vs valu {what} {name}', a.float().cpu(), b.float().cpu(), bar)
+
+
+# ---- against a build of the parent commit ----
+# What a library computes for a list of shapes: {case: (out, lse, dqkv[, dqkv_cls])} on the CPU.  spec = {'dtype': name of a
+# torch dtype, 'options': {option: value} set first, 'contig': [(S, L, H)], 'space': [(B, T, P, H)]}.
+def parent_cases(spec):
+    import vtx
+    dtype = getattr(torch, spec['dtype'])
+    for k, v in spec['options'].items():
+        vtx.set_option(k, v)
+    res = {}
+    for S, L, H in spec['contig']:
+        qkv, do = rnd(S, L, 3 * H * 64, seed=L) * 1.5, rnd(S, L, H * 64, seed=L + 1)
+        res[f'contig {S} {L} {H}'] = [t.cpu() for t in _run_contig(dev(qkv, dtype), dev(do, dtype), S, L, H, dtype)]
+    for B, T, P, H in spec['space']:
+        qkv, do = rnd(B, 1 + P * T, 3 * H * 64, seed=1) * 1.5, rnd(B * P * T + B * T, H * 64, seed=2)
+        res[f'space {B} {T} {P} {H}'] = [t.cpu() for t in _run_space(dev(qkv, dtype), dev(do, dtype), B, T, P, H, dtype)]
+    return res
+
+
+# the same in a child process that loads the library VTX_LIB names (a process loads one library)
+_PARENT_JOB = r'''
+import json, sys, torch
+sys.path[:0] = sys.argv[1:4]
+import test_gpu_long_attention as T
+torch.save(T.parent_cases(json.loads(sys.argv[5])), sys.argv[4])
+'''
+
+
+def assert_parent_bit_for_bit(spec, tmp_path, what):
+    """Every tensor of parent_cases(spec) from this build equals, bit for bit, what the library named by VTX_PARENT_LIB (built
+    from the parent commit) computes; skipped when VTX_PARENT_LIB names no file."""
+    import vtx
+    parent = os.environ.get('VTX_PARENT_LIB', '')
+    if not parent or not os.path.isfile(parent):
+        print('skipped: VTX_PARENT_LIB does not name a library built from the parent commit')
+        pytest.skip('VTX_PARENT_LIB does not name a library built from the parent commit')
+    out = str(tmp_path / 'parent.pt')
+    env = dict(os.environ, VTX_LIB=os.path.abspath(parent))
+    for k in ('VTX_ATTN_F32', 'VTX_ATTN_LONG', 'VTX_ATTN_VALU'):
+        env.pop(k, None)
+    subprocess.run([sys.executable, '-c', _PARENT_JOB, ROOT, os.path.join(ROOT, 'videotransformer-pytorch_amd'),
+                    os.path.join(ROOT, 'tests'), out, json.dumps(spec)], check=True, env=env, timeout=600)
+    want = torch.load(out)
+    assert os.path.realpath(vtx.load()._name) != os.path.realpath(parent), 'this process runs the parent library itself'
+    got = parent_cases(spec)
+    assert sorted(got) == sorted(want) and len(got) == len(spec['contig']) + len(spec['space'])
+    names = ('out', 'lse', 'dqkv', 'dqkv_cls')
+    for case in got:
+        assert len(got[case]) == len(want[case]) == (4 if case.startswith('space') else 3)
+        for name, a, b in zip(names, got[case], want[case]):
+            assert a.dtype == b.dtype and a.shape == b.shape
+            assert torch.isfinite(a.float()).any(), f'{case}: {name} was never written'
+            assert torch.equal(_bits(a), _bits(b)), f'{case}: {name} of {what} differs from the parent'
+    report(f'ok   {what} bit-identical to {os.path.basename(parent)} on {len(got)} shapes: ' + ', '.join(got))
+
+
+def test_long_is_the_parent_bit_for_bit(attn_long, tmp_path):
+    """The default bf16 route (attn_long=1) against a libvtx.so built from the parent commit, named by VTX_PARENT_LIB:
+    one ragged chunk past two full ones (257), full chunks + one key (385), 12 chunks + a tail and an idle wave (1569), and
+    the cls row of the space layout."""
+    spec = dict(dtype='bfloat16', options={'attn_long': '1'}, contig=[(2, 257, 3), (2, 385, 3), (2, 1569, 3)], space=[(1, 2, 784, 3)])
+    try:
+        assert_parent_bit_for_bit(spec, tmp_path, 'attn_long=1')
+    finally:
+        attn_long('1')
 
 
 # ------------------------------------------------------------------------------------------------ 5. models

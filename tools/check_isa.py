@@ -118,8 +118,8 @@ def check_tn_w4(obj):
 
 
 def check_plain(obj, names):
-    """A compiled object whose kernels take no special care (csrc/attn_long.hip): every kernel of `names` is there, uses the
-    32x32x16 bf16 MFMA, and has neither scratch (spill) traffic nor an instruction of the scalar unit that writes memory."""
+    """A compiled object whose kernels take no special care (csrc/attn_long.hip, the bf16 instances of csrc/attn_stream.h):
+    every kernel of `names` is there, uses the 32x32x16 bf16 MFMA, and has neither scratch (spill) traffic nor an instruction of the scalar unit that writes memory."""
     ks = dict((n, b) for n, b in kernels(disassemble(obj)))
     bad = []
     writes = re.compile(r'\bs_\w*(?:store|atomic|dcache)\w*')
@@ -165,7 +165,8 @@ def spill_counts(obj):
 
 
 def check_f32_attention(obj):
-    """The exact-fp32 attention kernels (csrc/attn_f32.hip): the three kernels are there, every matrix instruction is
+    """The exact-fp32 attention kernels (csrc/attn_f32.hip, the fp32 instances of csrc/attn_stream.h): the three kernels are
+    there, every matrix instruction is
     v_mfma_f32_32x32x2_f32 (fp32 operands: no bf16, no reduced-precision form) and there are at least the MFMAs of one unrolled
     chunk of two 32-row tiles (forward 2 x 64, dq 2 x 96, dk / dv 2 x 128; the compiler may peel a copy, in whole tiles of 32),
     no scratch traffic, no spilled register, no instruction of the scalar unit that writes memory."""

@@ -301,28 +301,20 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
   }
 }
 
-// bf16, head_dim 64, 33..256 tokens -> MFMA kernels (attn_mfma.hip); VTX_ATTN_VALU=1 forces the VALU path.
-static bool use_mfma(int dtype, int L, int hd) {
-  if (options().attn_valu) return false;
-  return attn_mfma_eligible(dtype, L, hd);
-}
-
-// bf16, head_dim 64, more than 256 tokens -> chunk-streaming MFMA kernels (attn_long.hip); VTX_ATTN_LONG=0 sends them back here.
-static bool use_long(int dtype, int L, int hd) {
-  if (options().attn_valu || !options().attn_long) return false;
-  return attn_long_eligible(dtype, L, hd);
-}
-
-// fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu (or attn_valu=1) sends them
-// back here, and so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
-static bool use_f32(int dtype, int L, int hd, bool probs) {
-  if (options().attn_valu || !options().attn_f32 || probs) return false;
-  return attn_f32_eligible(dtype, L, hd);
-}
-
-static bool use_small(int dtype, int mode, int L, int hd) {
-  if (options().attn_valu) return false;
-  return attn_small_eligible(dtype, mode, L, hd);
+// Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins:
+enum Route { SMALL, MFMA, LONG, F32, VALU };
+static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
+  // VTX_ATTN_VALU=1 forces the VALU path.
+  if (options().attn_valu) return VALU;
+  if (attn_small_eligible(dtype, mode, L, hd)) return SMALL;
+  // bf16, head_dim 64, 33..256 tokens -> MFMA kernels (attn_mfma.hip).
+  if (attn_mfma_eligible(dtype, L, hd)) return MFMA;
+  // bf16, head_dim 64, more than 256 tokens -> chunk-streaming MFMA kernels (attn_long.hip); VTX_ATTN_LONG=0 sends them back here.
+  if (options().attn_long && attn_long_eligible(dtype, L, hd)) return LONG;
+  // fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu sends them back here, and
+  // so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
+  if (options().attn_f32 && !probs && attn_f32_eligible(dtype, L, hd)) return F32;
+  return VALU;
 }
 
 static int make_params(const vtx_attn_desc* d, AttnP& p, const char* who) {
@@ -352,6 +344,26 @@ static size_t attn_lds(const AttnP& p, int hd, bool with_stats) {
   return b;
 }
 
+// The VALU launches, once per element type.  PROBS = 1 recomputes the probabilities from the lse that a forward left.
+template <typename T, int PROBS>
+static int valu_fwd_launch(const AttnP& p, const vtx_attn_desc* d, hipStream_t st) {
+  hipLaunchKernelGGL((attn_fwd_kernel<T, 64, PROBS>), attn_grid(p), attn_block(p), attn_lds(p, 64, false), st, p, (const T*)d->qkv,
+                     (T*)d->out, d->lse, PROBS ? d->probs : nullptr);
+  return check_launch(PROBS ? "attn_probs" : "attn_fwd");
+}
+template <typename T>
+static int valu_bwd_launch(const AttnP& p, const vtx_attn_bwd_desc* d, hipStream_t st) {
+  const dim3 grid = attn_grid(p), block = attn_block(p);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 64>), grid, block, attn_lds(p, 64, false), st, p, (const T*)d->f.qkv, (const T*)d->f.out,
+                     (const T*)d->dout, d->f.lse, d->delta, (T*)d->dqkv, (T*)d->dqkv_cls);
+  const int rc = check_launch("attn_bwd_dq");
+  if (rc) return rc;
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 64>), grid, block, attn_lds(p, 64, true), st, p, (const T*)d->f.qkv, (const T*)d->dout,
+                     d->f.lse, d->delta, (T*)d->dqkv, (T*)d->dqkv_cls);
+  return check_launch("attn_bwd_dkv");
+}
+
+
 }  // namespace vtx
 
 using namespace vtx;
@@ -363,29 +375,16 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
   if (rc) return rc;
   VTX_REQUIRE(d->out && d->lse && aligned16(d->out), VTX_EINVAL, "attn_fwd: out/lse required");
   hipStream_t st = as_stream(stream);
-  const dim3 grid = attn_grid(p), block = attn_block(p);
-  const size_t lds = attn_lds(p, 64, false);
-  if (use_small(d->dtype, d->mode, d->L, d->hd)) {
-    rc = attn_fwd_small_launch(p, d->qkv, d->out, d->lse, st);
-  } else if (use_mfma(d->dtype, d->L, d->hd)) {
-    rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st);
-  } else if (use_long(d->dtype, d->L, d->hd)) {
-    rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st);
-  } else if (use_f32(d->dtype, d->L, d->hd, d->probs != nullptr)) {
-    rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st);
-  } else {
-    if (d->dtype == VTX_F32)
-      hipLaunchKernelGGL((attn_fwd_kernel<float, 64, 0>), grid, block, lds, st, p, (const float*)d->qkv, (float*)d->out, d->lse, nullptr);
-    else
-      hipLaunchKernelGGL((attn_fwd_kernel<bf16raw, 64, 0>), grid, block, lds, st, p, (const bf16raw*)d->qkv, (bf16raw*)d->out, d->lse, nullptr);
-    rc = check_launch("attn_fwd");
+  const bool f32 = d->dtype == VTX_F32;
+  switch (attn_route(d->dtype, d->mode, d->L, d->hd, d->probs != nullptr)) {
+    case SMALL: rc = attn_fwd_small_launch(p, d->qkv, d->out, d->lse, st); break;
+    case MFMA: rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st); break;
+    case LONG: rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st); break;
+    case F32: rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st); break;
+    case VALU: rc = f32 ? valu_fwd_launch<float, 0>(p, d, st) : valu_fwd_launch<bf16raw, 0>(p, d, st); break;
   }
   if (rc || !d->probs) return rc;
-  if (d->dtype == VTX_F32)
-    hipLaunchKernelGGL((attn_fwd_kernel<float, 64, 1>), grid, block, lds, st, p, (const float*)d->qkv, (float*)d->out, d->lse, d->probs);
-  else
-    hipLaunchKernelGGL((attn_fwd_kernel<bf16raw, 64, 1>), grid, block, lds, st, p, (const bf16raw*)d->qkv, (bf16raw*)d->out, d->lse, d->probs);
-  return check_launch("attn_probs");
+  return f32 ? valu_fwd_launch<float, 1>(p, d, st) : valu_fwd_launch<bf16raw, 1>(p, d, st);
 }
 
 extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
@@ -398,30 +397,12 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
   VTX_REQUIRE(aligned16(d->dout) && aligned16(d->dqkv), VTX_EALIGN, "attn_bwd: alignment");
   p.ld_dout = d->ld_dout; p.ld_dqkv = d->ld_dqkv;
   hipStream_t st = as_stream(stream);
-  const dim3 grid = attn_grid(p), block = attn_block(p);
-  const size_t lds_a = attn_lds(p, 64, false), lds_b = attn_lds(p, 64, true);
-  if (use_small(d->f.dtype, d->f.mode, d->f.L, d->f.hd))
-    return attn_bwd_small_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, st);
-  if (use_mfma(d->f.dtype, d->f.L, d->f.hd))
-    return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
-  if (use_long(d->f.dtype, d->f.L, d->f.hd))
-    return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
-  if (use_f32(d->f.dtype, d->f.L, d->f.hd, false))
-    return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
-  if (d->f.dtype == VTX_F32) {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<float, 64>), grid, block, lds_a, st, p, (const float*)d->f.qkv, (const float*)d->f.out,
-                       (const float*)d->dout, d->f.lse, d->delta, (float*)d->dqkv, (float*)d->dqkv_cls);
-    rc = check_launch("attn_bwd_dq");
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<float, 64>), grid, block, lds_b, st, p, (const float*)d->f.qkv, (const float*)d->dout,
-                       d->f.lse, d->delta, (float*)d->dqkv, (float*)d->dqkv_cls);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<bf16raw, 64>), grid, block, lds_a, st, p, (const bf16raw*)d->f.qkv, (const bf16raw*)d->f.out,
-                       (const bf16raw*)d->dout, d->f.lse, d->delta, (bf16raw*)d->dqkv, (bf16raw*)d->dqkv_cls);
-    rc = check_launch("attn_bwd_dq");
-    if (rc) return rc;
-    hipLaunchKernelGGL((attn_bwd_dkv_kernel<bf16raw, 64>), grid, block, lds_b, st, p, (const bf16raw*)d->f.qkv, (const bf16raw*)d->dout,
-                       d->f.lse, d->delta, (bf16raw*)d->dqkv, (bf16raw*)d->dqkv_cls);
+  switch (attn_route(d->f.dtype, d->f.mode, d->f.L, d->f.hd, false)) {
+    case SMALL: return attn_bwd_small_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, st);
+    case MFMA: return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case VALU: break;
   }
-  return check_launch("attn_bwd_dkv");
+  return d->f.dtype == VTX_F32 ? valu_bwd_launch<float>(p, d, st) : valu_bwd_launch<bf16raw>(p, d, st);
 }

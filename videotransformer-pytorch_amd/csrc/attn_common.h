@@ -1,5 +1,6 @@
-// attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip, attn_long.hip and attn_f32.hip,
-// and the swizzled-LDS / MFMA fragment helpers of the two bf16 MFMA families.
+// attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip and the chunk-streaming kernels
+// (attn_stream.h with its two tile policies, attn_long.hip and attn_f32.hip), and the swizzled-LDS / MFMA fragment helpers of the
+// two bf16 MFMA families.
 #pragma once
 #include "common.h"
 
