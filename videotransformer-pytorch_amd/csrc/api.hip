@@ -1,4 +1,5 @@
 // api.hip -- error plumbing, version, and the instruction-layout self-test.
+#include <limits.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <string.h>
@@ -31,47 +32,57 @@ static const char* const kNtNames[] = {"auto", "pp256", "dma2", "ring128x3", "ri
 static const char* const kAttnF32Names[] = {"valu", "mfma"};
 static const char* const kTnNames[] = {"auto", "pp256", "ring", "dma2", "w4"};
 
-static int parse_enum(const char* v, const char* const* names, int n) {
-  for (int i = 0; i < n; ++i)
-    if (strcmp(v, names[i]) == 0) return i;
-  return -1;
-}
+// One row per option: {environment variable (none: not settable from the environment), name}, how the value parses, the field.
+// FLAG: any integer, stored as 0 / 1.  INT: an integer in lo .. hi that is a multiple of mult, anything else is rejected.
+// CLAMP: an integer, clamped to lo .. hi.  ENUM: one of names[0 .. hi].  ADDR: a device address (pp_trace).
+enum OptKind { OPT_FLAG, OPT_INT, OPT_CLAMP, OPT_ENUM, OPT_ADDR };
+struct OptRow { const char* id[2]; OptKind kind; int Options::*field; int lo, hi, mult; const char* const* names; };
+#define VTX_ENUM(names) 0, (int)(sizeof(names) / sizeof(*names)) - 1, 1, names
+static const OptRow kOptions[] = {
+    {{"VTX_GEMM_NT", "gemm_nt"}, OPT_ENUM, &Options::gemm_nt, VTX_ENUM(kNtNames)},
+    {{"VTX_GEMM_TN", "gemm_tn"}, OPT_ENUM, &Options::gemm_tn, VTX_ENUM(kTnNames)},
+    {{"VTX_GEMM_NODMA", "gemm_nodma"}, OPT_FLAG, &Options::gemm_nodma},
+    {{"VTX_TN_SAFE", "tn_safe"}, OPT_FLAG, &Options::tn_safe},
+    {{"VTX_TN_CUS", "tn_cus"}, OPT_INT, &Options::tn_cus, 32, 1024, 1},
+    {{"VTX_ATTN_VALU", "attn_valu"}, OPT_FLAG, &Options::attn_valu},
+    {{"VTX_ATTN_LONG", "attn_long"}, OPT_FLAG, &Options::attn_long},
+    {{"VTX_ATTN_F32", "attn_f32"}, OPT_ENUM, &Options::attn_f32, VTX_ENUM(kAttnF32Names)},
+    {{"VTX_ATTN_HW_FWD", "attn_hw_fwd"}, OPT_INT, &Options::attn_hw_fwd, 0, INT_MAX, 1},
+    {{"VTX_ATTN_HW_BWD", "attn_hw_bwd"}, OPT_INT, &Options::attn_hw_bwd, 0, INT_MAX, 1},
+    {{"VTX_ATTN_FUSED", "attn_fused"}, OPT_CLAMP, &Options::attn_fused, 0, 2},
+    {{"VTX_ATTN_FWD_STREAM", "attn_fwd_stream"}, OPT_FLAG, &Options::attn_fwd_stream},
+    {{"VTX_ATTN_DKV", "attn_dkv"}, OPT_INT, &Options::attn_dkv, 0, 4, 1},
+    {{"VTX_GEMM_PP_GRID", "pp_grid"}, OPT_INT, &Options::pp_grid, 8, 4096, 8},
+    {{"VTX_GEMM_PP_CG", "pp_cg"}, OPT_INT, &Options::pp_cg, 0, INT_MAX, 1},
+    {{"VTX_GEMM_PP_EPI", "pp_epi"}, OPT_INT, &Options::pp_epi, INT_MIN, INT_MAX, 1},
+    {{"VTX_GEMM_PP_CONT", "pp_cont"}, OPT_FLAG, &Options::pp_cont},
+    {{"VTX_LN_ROWS", "ln_rows"}, OPT_INT, &Options::ln_rows, 1, 4, 1},
+    {{nullptr, "pp_trace"}, OPT_ADDR, nullptr}};
+#undef VTX_ENUM
 
 static int set_option(Options& o, const char* name, const char* value) {
   if (!name || !value) return VTX_EINVAL;
-  if (strcmp(name, "gemm_nt") == 0) { const int e = parse_enum(value, kNtNames, 8); if (e < 0) return VTX_EINVAL; o.gemm_nt = e; return VTX_OK; }
-  if (strcmp(name, "gemm_tn") == 0) { const int e = parse_enum(value, kTnNames, 5); if (e < 0) return VTX_EINVAL; o.gemm_tn = e; return VTX_OK; }
-  if (strcmp(name, "gemm_nodma") == 0) { o.gemm_nodma = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "tn_safe") == 0) { o.tn_safe = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "tn_cus") == 0) { const int g = atoi(value); if (g < 32 || g > 1024) return VTX_EINVAL; o.tn_cus = g; return VTX_OK; }
-  if (strcmp(name, "attn_valu") == 0) { o.attn_valu = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "attn_long") == 0) { o.attn_long = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "attn_f32") == 0) { const int e = parse_enum(value, kAttnF32Names, 2); if (e < 0) return VTX_EINVAL; o.attn_f32 = e; return VTX_OK; }
-  if (strcmp(name, "attn_hw_fwd") == 0) { const int g = atoi(value); if (g < 0) return VTX_EINVAL; o.attn_hw_fwd = g; return VTX_OK; }
-  if (strcmp(name, "attn_hw_bwd") == 0) { const int g = atoi(value); if (g < 0) return VTX_EINVAL; o.attn_hw_bwd = g; return VTX_OK; }
-  if (strcmp(name, "attn_fused") == 0) { const int v = atoi(value); o.attn_fused = v < 0 ? 0 : v > 2 ? 2 : v; return VTX_OK; }
-  if (strcmp(name, "attn_fwd_stream") == 0) { o.attn_fwd_stream = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "attn_dkv") == 0) { const int g = atoi(value); if (g < 0 || g > 4) return VTX_EINVAL; o.attn_dkv = g; return VTX_OK; }
-  if (strcmp(name, "pp_grid") == 0) { const int g = atoi(value); if (g < 8 || g > 4096 || g % 8) return VTX_EINVAL; o.pp_grid = g; return VTX_OK; }
-  if (strcmp(name, "pp_cg") == 0) { const int g = atoi(value); if (g < 0) return VTX_EINVAL; o.pp_cg = g; return VTX_OK; }
-  if (strcmp(name, "pp_epi") == 0) { o.pp_epi = atoi(value); return VTX_OK; }
-  if (strcmp(name, "pp_cont") == 0) { o.pp_cont = atoi(value) != 0; return VTX_OK; }
-  if (strcmp(name, "ln_rows") == 0) { const int g = atoi(value); if (g < 1 || g > 4) return VTX_EINVAL; o.ln_rows = g; return VTX_OK; }
-  if (strcmp(name, "pp_trace") == 0) { o.pp_trace = strtoull(value, nullptr, 0); return VTX_OK; }
+  for (const OptRow& r : kOptions) {
+    if (strcmp(name, r.id[1]) != 0) continue;
+    if (r.kind == OPT_ADDR) { o.pp_trace = strtoull(value, nullptr, 0); return VTX_OK; }
+    int v = atoi(value);
+    if (r.kind == OPT_ENUM)
+      for (v = r.hi; v >= 0 && strcmp(value, r.names[v]) != 0;) --v;
+    if (r.kind == OPT_FLAG) v = v != 0;
+    if (r.kind == OPT_CLAMP) v = v < r.lo ? r.lo : v > r.hi ? r.hi : v;
+    if ((r.kind == OPT_INT || r.kind == OPT_ENUM) && (v < r.lo || v > r.hi || v % r.mult)) return VTX_EINVAL;
+    o.*r.field = v;
+    return VTX_OK;
+  }
   return VTX_EINVAL;
 }
 
 Options& options() {
   static Options o = [] {
     Options d;
-    static const char* const env[][2] = {{"VTX_GEMM_NT", "gemm_nt"}, {"VTX_GEMM_TN", "gemm_tn"}, {"VTX_GEMM_NODMA", "gemm_nodma"},
-                                         {"VTX_TN_SAFE", "tn_safe"}, {"VTX_TN_CUS", "tn_cus"}, {"VTX_ATTN_VALU", "attn_valu"}, {"VTX_ATTN_LONG", "attn_long"}, {"VTX_ATTN_F32", "attn_f32"}, {"VTX_GEMM_PP_GRID", "pp_grid"},
-                                         {"VTX_GEMM_PP_CG", "pp_cg"}, {"VTX_GEMM_PP_EPI", "pp_epi"},
-                                         {"VTX_GEMM_PP_CONT", "pp_cont"}, {"VTX_LN_ROWS", "ln_rows"}, {"VTX_ATTN_HW_FWD", "attn_hw_fwd"}, {"VTX_ATTN_HW_BWD", "attn_hw_bwd"}, {"VTX_ATTN_DKV", "attn_dkv"}, {"VTX_ATTN_FWD_STREAM", "attn_fwd_stream"},
-                                         {"VTX_ATTN_FUSED", "attn_fused"}};
-    for (const auto& e : env) {
-      const char* v = getenv(e[0]);
-      if (v && *v) set_option(d, e[1], v);       // an unparsable value keeps the default
+    for (const OptRow& r : kOptions) {
+      const char* v = r.id[0] ? getenv(r.id[0]) : nullptr;
+      if (v && *v) set_option(d, r.id[1], v);     // an unparsable value keeps the default
     }
     return d;
   }();

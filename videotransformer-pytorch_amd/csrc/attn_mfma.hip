@@ -1555,10 +1555,7 @@ int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const 
   if (options().attn_hw_bwd > 0) {
     const int w = hw_waves(options().attn_hw_bwd, p.H);
     const size_t lds = (size_t)w * SM_WAVE_LDS_BWD;
-    static std::atomic<unsigned long long> attr_set{0};
-    if (first_launch_on_device(attr_set)) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_small_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    }
+    allow_lds<attn_bwd_small_kernel<true>>(lds);
     hipLaunchKernelGGL(attn_bwd_small_kernel<true>, dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), lds, st, p, ntiles,
                        (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv);
   } else {
@@ -1568,22 +1565,12 @@ int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const 
   return check_launch("attn_bwd_small");
 }
 
-template <auto Kernel>
-static void allow_lds(size_t lds) {
-  // > 64 KB of dynamic LDS needs an explicit opt-in (Lp = 224: 56 KB of tiles + 16 KB of staging), once per kernel
-  // instantiation (the template argument: one static per kernel) and device
-  static std::atomic<unsigned long long> seen{0};
-  if (lds > 65536 && first_launch_on_device(seen))
-    hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 int attn_fwd_mfma_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
   const int nt = (p.L + 31) >> 5, Lp = nt * 32;
   // (mg_div splits item -> (sequence, head) -> (clip, frame) with reciprocal multiplies that are exact below 2^24 items)
   if (nt == 7 && options().attn_fwd_stream && (long)p.S * p.H < (1L << 24)) {      // one persistent workgroup per CU, K / V of the next item streamed in by LDS-DMA
     allow_lds<attn_fwd_stream_mfma_kernel<7>>(MGF_LDS_BYTES);
-    const int items = p.S * p.H, cus = device_cus();
-    hipLaunchKernelGGL(attn_fwd_stream_mfma_kernel<7>, dim3(items < cus ? items : cus), dim3(MF_THREADS), MGF_LDS_BYTES, st, p,
+    hipLaunchKernelGGL(attn_fwd_stream_mfma_kernel<7>, dim3(persistent_grid(p.S * p.H)), dim3(MF_THREADS), MGF_LDS_BYTES, st, p,
                        (const bf16raw*)qkv, (bf16raw*)out, lse);
     return check_launch("attn_fwd_stream_mfma");
   }
@@ -1620,8 +1607,8 @@ static int attn_bwd_fused_launch_t(const AttnP& p, const void* qkv, const void* 
   const int Lp = ((p.L + 31) >> 5) * 32;
   const size_t lds = (size_t)4 * Lp * 64 * 2 + 8 * MA_STAGE_ELEMS * 2 + (size_t)2 * Lp * 4;
   allow_lds<attn_bwd_fused_mfma_kernel<NT_>>(lds);
-  const int items = p.S * p.H, cus = device_cus();          // one workgroup per CU (its LDS holds one item), persistent
-  hipLaunchKernelGGL(attn_bwd_fused_mfma_kernel<NT_>, dim3(items < cus ? items : cus), dim3(MF_THREADS), lds, st, p, (const bf16raw*)qkv,
+  // one workgroup per CU (its LDS holds one item), persistent
+  hipLaunchKernelGGL(attn_bwd_fused_mfma_kernel<NT_>, dim3(persistent_grid(p.S * p.H)), dim3(MF_THREADS), lds, st, p, (const bf16raw*)qkv,
                      (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
   return check_launch("attn_bwd_fused_mfma");
 }
@@ -1629,8 +1616,8 @@ static int attn_bwd_fused_launch_t(const AttnP& p, const void* qkv, const void* 
 static int attn_bwd_stream_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
                                   void* dqkv_cls, hipStream_t st) {
   allow_lds<attn_bwd_stream_mfma_kernel<7>>(MG_LDS_BYTES);
-  const int items = p.S * p.H, cus = device_cus();          // one workgroup per CU, persistent over the items (heads fastest)
-  hipLaunchKernelGGL(attn_bwd_stream_mfma_kernel<7>, dim3(items < cus ? items : cus), dim3(MF_THREADS), MG_LDS_BYTES, st, p,
+  // one workgroup per CU, persistent over the items (heads fastest)
+  hipLaunchKernelGGL(attn_bwd_stream_mfma_kernel<7>, dim3(persistent_grid(p.S * p.H)), dim3(MF_THREADS), MG_LDS_BYTES, st, p,
                      (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls,
                      reinterpret_cast<long long*>(options().pp_trace));
   return check_launch("attn_bwd_stream_mfma");

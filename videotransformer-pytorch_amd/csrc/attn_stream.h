@@ -319,14 +319,10 @@ template <class E> constexpr size_t stream_lds_dkv() { return stream_lds_kv<E>()
 
 inline dim3 stream_grid(const AttnP& p) { return dim3((unsigned)p.S * (unsigned)cdiv(p.L, AS_ROWS), p.H); }
 
-// One launch.  More than 64 KiB (the default limit) of dynamic LDS needs an explicit opt-in, once per kernel and device.
+// One launch.
 template <auto Kernel, class... Args>
 int stream_launch(const char* what, size_t lds, const AttnP& p, hipStream_t st, Args... args) {
-  if (lds > 64 * 1024) {
-    static std::atomic<unsigned long long> seen{0};
-    if (first_launch_on_device(seen))
-      hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
+  allow_lds<Kernel>(lds);
   hipLaunchKernelGGL(Kernel, stream_grid(p), dim3(AS_THREADS), lds, st, p, args...);
   return check_launch(what);
 }

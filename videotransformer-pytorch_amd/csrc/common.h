@@ -162,7 +162,8 @@ __device__ inline void gelu_erf_both(float x, float& val, float& grad) {
 // ---- tuning / diagnostic switches ----------------------------------------------------
 // Process-wide, set through vtx_set_option() (initial values come from the VTX_* environment
 // variables, read ONCE when the library is first used -- never on the launch path).
-enum { NT_AUTO = 0, NT_PP256, NT_DMA2, NT_RING128X3, NT_RING128X4K32, NT_RING256X3, NT_RING256X3K32, NT_RING256X4K32 };
+enum { NT_AUTO = 0, NT_PP256, NT_DMA2, NT_RING128X3, NT_RING128X4K32, NT_RING256X3, NT_RING256X3K32, NT_RING256X4K32,
+       NT_REG, NT_F32 };       // (the last two are no option values: the kernels vtx_gemm_nt picks without LDS-DMA / for fp32)
 enum { TN_AUTO = 0, TN_PP256, TN_RING, TN_DMA2, TN_W4 };
 struct Options {
   int gemm_nt = NT_AUTO;     // VTX_GEMM_NT: kernel family override of vtx_gemm_nt (bf16)
@@ -222,6 +223,15 @@ inline bool first_launch_on_device(std::atomic<unsigned long long>& seen) {
   return (seen.fetch_or(bit, std::memory_order_relaxed) & bit) == 0;
 }
 
+// The opt-in to more than 64 KB of dynamic LDS for one kernel instantiation (the template argument: one mask each): a launch
+// that needs `needed` bytes raises the kernel's limit to `cap` once per device; a kernel within 64 KB needs none.
+template <auto Kernel>
+static void allow_lds(size_t needed, size_t cap = 160 * 1024) {
+  static std::atomic<unsigned long long> seen{0};
+  if (needed > 64 * 1024 && first_launch_on_device(seen))
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)cap);
+}
+
 // compute units of the current device (asked once per device)
 inline int device_cus() {
   static std::atomic<int> cached[64];
@@ -234,6 +244,8 @@ inline int device_cus() {
   }
   return v;
 }
+// grid of a persistent kernel that keeps one workgroup per CU walking `items`
+inline unsigned persistent_grid(int items) { const int cus = device_cus(); return (unsigned)(items < cus ? items : cus); }
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

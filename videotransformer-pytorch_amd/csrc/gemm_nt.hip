@@ -358,11 +358,7 @@ static int launch_ring(const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t 
   const size_t ring_bytes = (size_t)NBUF * (RBM + BN) * BK * 2;
   const size_t stage_bytes = (size_t)WM * 2 * 32 * STAGE_LD * 4;
   const size_t lds = ring_bytes > stage_bytes ? ring_bytes : stage_bytes;
-  static std::atomic<unsigned long long> attr_set{0};
-  if (first_launch_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_bf16_ring_kernel<WM, NBUF, BK>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  }
+  allow_lds<gemm_nt_bf16_ring_kernel<WM, NBUF, BK>>(lds, lds);
   const int tiles_m = cdiv(d->M, RBM), tiles_n = cdiv(d->N, BN);
   hipLaunchKernelGGL((gemm_nt_bf16_ring_kernel<WM, NBUF, BK>), dim3(tiles_m * tiles_n), dim3(WM * 128), lds, st, d->M, d->N,
                      d->K, (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, tiles_n, ep);
@@ -1407,11 +1403,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
 
 template <bool EPI2, int PRE, bool HAS_SC, bool HAS_ACT, bool CONT, bool ROLL = false>
 static int launch_pp_t(const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t st, const Options& cfg) {
-  static std::atomic<unsigned long long> attr_set{0};
-  if (first_launch_on_device(attr_set)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_bf16_pp_kernel<EPI2, PRE, HAS_SC, HAS_ACT, CONT, ROLL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        PP_LDS_BYTES);
-  }
+  allow_lds<gemm_nt_bf16_pp_kernel<EPI2, PRE, HAS_SC, HAS_ACT, CONT, ROLL>>(PP_LDS_BYTES, PP_LDS_BYTES);
   const int tiles_m = cdiv(d->M, PP_BM), tiles_n = cdiv(d->N, PP_BN);
   // column tiles per group (tools/gemm_cg.py, M = 100352: 1 is 15 % slower at N = 3072, 3..8 are within noise;
   // K = 3072 wants >= 3): about 6 MB of weight panels, between 3 and 6 tiles
@@ -1430,7 +1422,7 @@ static int launch_pp(const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t st
   if (cfg.pp_epi == 1) return launch_pp_t<false, PRE_NONE, false, false, false>(d, ep, st, cfg);   // generic epilogue: any combination
   // specialised on what the epilogue has to read, so that a plain GEMM carries no prefetch registers and no branch
   // sits inside the passes; the activation and the GELU' / multiplier inputs are only instantiated without
-  // residual / row scale (the FFN's Linears: vtx_gemm_nt routes other combinations to the non-persistent kernels)
+  // residual / row scale (the FFN's Linears: nt_family routes other combinations to the non-persistent kernels)
   const bool sc = d->row_scale != nullptr;
   // continuous flow: row maps that cross a group boundary at most once per 256-row tile (what its 32-bit row
   // offsets assume)
@@ -1573,6 +1565,49 @@ using namespace vtx;
 
 extern "C" size_t vtx_gemm_nt_workspace(void) { return 9 * 64; }   // 8 per-XCD tile counters + 1 check-out counter, one 64-B line each
 
+static EpiParams make_epi(const vtx_gemm_desc* d) {
+  EpiParams ep;
+  ep.M = d->M; ep.N = d->N;
+  ep.C = d->C; ep.ldc = d->ldc; ep.cmap = d->cmap;
+  ep.bias = d->bias; ep.act = d->act; ep.C2 = d->C2; ep.ldc2 = d->ldc2;
+  ep.dgelu_in = d->dgelu_in; ep.ld_dgelu = d->ld_dgelu; ep.dgelu_kind = d->dgelu_kind;
+  ep.row_scale = d->row_scale; ep.rs_d1 = d->rs_d1; ep.rs_m1 = d->rs_m1; ep.rs_d2 = d->rs_d2; ep.rs_m2 = d->rs_m2;
+  ep.R = d->R; ep.ldr = d->ldr; ep.rmap = d->rmap; ep.r_period = d->r_period;
+  ep.split_row = d->split_row; ep.Csplit = d->Csplit; ep.ldsplit = d->ldsplit;
+  const FastDiv f1 = make_fast_div(d->row_scale ? (unsigned)d->rs_d1 : 1u), f2 = make_fast_div(d->row_scale ? (unsigned)d->rs_d2 : 1u);
+  ep.rs_magic1 = f1.magic; ep.rs_shift1 = f1.shift; ep.rs_magic2 = f2.magic; ep.rs_shift2 = f2.shift;
+  return ep;
+}
+
+// Which kernel family runs a (validated) GEMM: an NT_* value, never NT_AUTO (launch_pp picks the ping-pong instantiation).
+static int nt_family(const vtx_gemm_desc* d, const Options& o) {
+  if (d->dtype != VTX_BF16) return NT_F32;
+  if (d->K % BK16 != 0 || o.gemm_nodma) return NT_REG;         // register-staged: no LDS-DMA
+  // default: the persistent 256x256 ping-pong kernel for the big activations GEMMs; the 256x128 ring (72 KB of
+  // LDS, two co-resident workgroups per CU) for 1024 <= M < 2048; the two-buffer 128x128 kernel below that
+  const int variant = o.gemm_nt != NT_AUTO ? o.gemm_nt : (d->M >= 2048 ? NT_PP256 : d->M >= 1024 ? NT_RING256X3K32 : NT_DMA2);
+  const int nkt = d->K / BK16;
+  // the ping-pong kernel prefetches the residual and the GELU' input into the same registers, and keeps its
+  // tile counters in the caller's workspace
+  const bool combo_ok = o.pp_epi == 1 || ((!d->act || !(d->R || d->dgelu_in || d->row_scale)) &&
+                                          (!d->dgelu_in || !(d->R || d->row_scale)));
+  // 32-bit byte offsets inside a tile: its 256 rows (plus the rows a row map skips inside it) must span < 2 GB
+  const long span_rows = 256 + (d->amap.grp > 0 ? (256 / d->amap.grp + 2) * (long)(d->amap.skip > 0 ? d->amap.skip : 0) : 0);
+  const bool span_ok = span_rows * d->lda * 2 < (1L << 31) && 256L * d->ldb * 2 < (1L << 31) && d->amap.skip >= 0;
+  const bool pp_ok = nkt >= 2 && combo_ok && span_ok && d->workspace && d->ws_bytes >= vtx_gemm_nt_workspace();
+  if (variant == NT_PP256) return pp_ok ? NT_PP256 : nkt >= 3 ? NT_RING256X3K32 : NT_DMA2;   // falls back to the default ring
+  return nkt >= 3 ? variant : NT_DMA2;                         // the rings keep three K tiles in flight
+}
+
+// the kernels with one 128 x 128 tile per workgroup
+template <typename T, typename Kernel>
+static int launch_tile(Kernel kernel, size_t need, const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t st) {
+  const int tiles_m = cdiv(d->M, BM), tiles_n = cdiv(d->N, BN);
+  hipLaunchKernelGGL(kernel, dim3(tiles_m * tiles_n), dim3(NT_THREADS), STAGE_BYTES > need ? STAGE_BYTES : need, st, d->M, d->N, d->K,
+                     (const T*)d->A, d->lda, d->amap, (const T*)d->B, d->ldb, tiles_n, ep);
+  return check_launch("gemm_nt");
+}
+
 extern "C" int vtx_gemm_nt(const vtx_gemm_desc* d, void* stream) {
   VTX_REQUIRE(d != nullptr, VTX_EINVAL, "gemm_nt: null descriptor");
   VTX_REQUIRE(d->M >= 0 && d->N > 0 && d->K > 0, VTX_EINVAL, "gemm_nt: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
@@ -1597,55 +1632,17 @@ extern "C" int vtx_gemm_nt(const vtx_gemm_desc* d, void* stream) {
   VTX_REQUIRE((closed_form(d->cmap) || d->cmap.grp > 0) && (closed_form(d->rmap) || d->rmap.grp > 0), VTX_EINVAL,
               "gemm_nt: a table row map needs grp > 0");
 
-  EpiParams ep;
-  ep.M = d->M; ep.N = d->N;
-  ep.C = d->C; ep.ldc = d->ldc; ep.cmap = d->cmap;
-  ep.bias = d->bias; ep.act = d->act; ep.C2 = d->C2; ep.ldc2 = d->ldc2;
-  ep.dgelu_in = d->dgelu_in; ep.ld_dgelu = d->ld_dgelu; ep.dgelu_kind = d->dgelu_kind;
-  ep.row_scale = d->row_scale; ep.rs_d1 = d->rs_d1; ep.rs_m1 = d->rs_m1; ep.rs_d2 = d->rs_d2; ep.rs_m2 = d->rs_m2;
-  ep.R = d->R; ep.ldr = d->ldr; ep.rmap = d->rmap; ep.r_period = d->r_period;
-  ep.split_row = d->split_row; ep.Csplit = d->Csplit; ep.ldsplit = d->ldsplit;
-  {
-    const FastDiv f1 = make_fast_div(d->row_scale ? (unsigned)d->rs_d1 : 1u), f2 = make_fast_div(d->row_scale ? (unsigned)d->rs_d2 : 1u);
-    ep.rs_magic1 = f1.magic; ep.rs_shift1 = f1.shift; ep.rs_magic2 = f2.magic; ep.rs_shift2 = f2.shift;
-  }
-
-  const int tiles_m = cdiv(d->M, BM), tiles_n = cdiv(d->N, BN);
-  dim3 grid(tiles_m * tiles_n), block(NT_THREADS);
+  const EpiParams ep = make_epi(d);
   hipStream_t st = as_stream(stream);
-  if (d->dtype == VTX_BF16) {
-    const size_t lds = STAGE_BYTES > 4 * BM * BK16 * 2 ? STAGE_BYTES : 4 * BM * BK16 * 2;
-    const Options& o = options();
-    const bool dma_ok = d->K % BK16 == 0 && !o.gemm_nodma;
-    // default: the persistent 256x256 ping-pong kernel for the big activations GEMMs; the 256x128 ring (72 KB of
-    // LDS, two co-resident workgroups per CU) for 1024 <= M < 2048; the two-buffer 128x128 kernel below that
-    const int variant = o.gemm_nt != NT_AUTO ? o.gemm_nt : (d->M >= 2048 ? NT_PP256 : d->M >= 1024 ? NT_RING256X3K32 : NT_DMA2);
-    const int nkt = d->K / BK16;
-    // the ping-pong kernel prefetches the residual and the GELU' input into the same registers, and keeps its
-    // tile counters in the caller's workspace
-    const bool combo_ok = o.pp_epi == 1 || ((!d->act || !(d->R || d->dgelu_in || d->row_scale)) &&
-                                            (!d->dgelu_in || !(d->R || d->row_scale)));
-    // 32-bit byte offsets inside a tile: its 256 rows (plus the rows a row map skips inside it) must span < 2 GB
-    const long span_rows = 256 + (d->amap.grp > 0 ? (256 / d->amap.grp + 2) * (long)(d->amap.skip > 0 ? d->amap.skip : 0) : 0);
-    const bool span_ok = span_rows * d->lda * 2 < (1L << 31) && 256L * d->ldb * 2 < (1L << 31) && d->amap.skip >= 0;
-    const bool pp_ok = dma_ok && nkt >= 2 && combo_ok && span_ok && d->workspace && d->ws_bytes >= vtx_gemm_nt_workspace();
-    if (variant == NT_PP256 && pp_ok) return launch_pp(d, ep, st);
-    if (dma_ok && nkt >= 3 && (variant == NT_RING256X3)) return launch_ring<4, 3, 64>(d, ep, st);
-    if (dma_ok && nkt >= 3 && (variant == NT_RING256X3K32 || variant == NT_PP256)) return launch_ring<4, 3, 32>(d, ep, st);
-    if (dma_ok && nkt >= 3 && variant == NT_RING256X4K32) return launch_ring<4, 4, 32>(d, ep, st);
-    if (dma_ok && nkt >= 3 && variant == NT_RING128X3) return launch_ring<2, 3, 64>(d, ep, st);
-    if (dma_ok && nkt >= 3 && variant == NT_RING128X4K32) return launch_ring<2, 4, 32>(d, ep, st);
-    if (dma_ok)
-      hipLaunchKernelGGL(gemm_nt_bf16_dma_kernel, grid, block, lds, st, d->M, d->N, d->K, (const bf16raw*)d->A, d->lda,
-                         d->amap, (const bf16raw*)d->B, d->ldb, tiles_n, ep);
-    else
-      hipLaunchKernelGGL(gemm_nt_bf16_kernel, grid, block, lds, st, d->M, d->N, d->K, (const bf16raw*)d->A, d->lda,
-                         d->amap, (const bf16raw*)d->B, d->ldb, tiles_n, ep);
-  } else {
-    const size_t need = (size_t)4 * BM * LD32 * 4;
-    const size_t lds = STAGE_BYTES > need ? STAGE_BYTES : need;
-    hipLaunchKernelGGL(gemm_nt_f32_kernel, grid, block, lds, st, d->M, d->N, d->K, (const float*)d->A, d->lda,
-                       d->amap, (const float*)d->B, d->ldb, tiles_n, ep);
+  switch (nt_family(d, options())) {
+    case NT_PP256: return launch_pp(d, ep, st);
+    case NT_RING256X3: return launch_ring<4, 3, 64>(d, ep, st);
+    case NT_RING256X3K32: return launch_ring<4, 3, 32>(d, ep, st);
+    case NT_RING256X4K32: return launch_ring<4, 4, 32>(d, ep, st);
+    case NT_RING128X3: return launch_ring<2, 3, 64>(d, ep, st);
+    case NT_RING128X4K32: return launch_ring<2, 4, 32>(d, ep, st);
+    case NT_DMA2: return launch_tile<bf16raw>(gemm_nt_bf16_dma_kernel, (size_t)4 * BM * BK16 * 2, d, ep, st);
+    case NT_REG: return launch_tile<bf16raw>(gemm_nt_bf16_kernel, (size_t)4 * BM * BK16 * 2, d, ep, st);
+    default: return launch_tile<float>(gemm_nt_f32_kernel, (size_t)4 * BM * LD32 * 4, d, ep, st);
   }
-  return check_launch("gemm_nt");
 }

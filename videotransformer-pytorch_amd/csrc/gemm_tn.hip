@@ -1448,15 +1448,91 @@ static int colsum_blocks(int M) {
   return b > 256 ? 256 : (b < 1 ? 1 : b);
 }
 
+// ---- one plan per launch: kernel, tile / slab partition and workspace layout, decided in one place -------------------
+enum TnKernel { TK_F32, TK_SAFE, TK_NODMA, TK_DMA2, TK_RING, TK_PP256, TK_PP256_TRACE, TK_W4 };   // from TK_RING on: > 64 KB of LDS
+struct TnPlan {
+  TnKernel kernel;
+  unsigned grid, block;      // grid = tiles12 * slabs
+  size_t lds;
+  int tiles2, tiles12;       // column tiles, tiles per slab (kernel arguments)
+  int slabs, m_per;          // partition of the M rows: slabs and rows per slab
+  int cs_fold;               // column-sum copies per slab
+  long slab_stride;          // floats per slab: [N1 * N2 weight partials | cs_fold x N1 column sums]
+  long red_n; int red_fold;  // what the reduction sums per slab: the weight partials (+ N1 column sums, folded over red_fold copies)
+};
+
+static size_t tn_slab_bytes(int slabs, long slab_stride) { return (size_t)slabs * (size_t)slab_stride * sizeof(float); }
+// slabs the workspace holds: the most that the 128 x 128 kernels' or the ping-pong partition asks for; the ring takes what is there
+static int tn_ws_slabs(int M, int N1, int N2) {
+  const int s = tn_splits(M, N1, N2), s_p = tp_eligible(M, N1, N2) ? tp_splits(M, N1, N2) : 0;
+  return s_p > s ? s_p : s;
+}
+
+static TnPlan tn_plan(int dtype, int M, int N1, int N2, const vtx_rowmap& amap, const vtx_rowmap& bmap, bool has_colsum,
+                      const Options& o) {
+  TnPlan p;
+  const int tiles2 = cdiv(N2, 128);
+  // 128 x 128 tiles, tn_splits slabs of whole K tiles, one column-sum copy per slab
+  auto small = [&](TnKernel k, int tile_m, size_t need) {
+    p.kernel = k; p.block = NT_THREADS; p.lds = STAGE_BYTES > need ? STAGE_BYTES : need;
+    p.tiles2 = tiles2; p.tiles12 = cdiv(N1, 128) * tiles2; p.cs_fold = 1;
+    p.slabs = tn_splits(M, N1, N2);
+    p.m_per = cdiv(cdiv(M, p.slabs), tile_m) * tile_m;
+  };
+  // Default: the 256x256 ping-pong kernel wherever it is eligible (M >= 4096, N1 and N2 multiples of 256, row-map
+  // groups > 64 rows), the 256x128 ring (2 workgroups per CU) otherwise.  tools/tn_compare.py at M = 150528 with the
+  // fused bias-gradient sums, ring / ping-pong: 768x3072 974 / 731 us, 3072x768 791 / 708, 2304x768 603 / 551,
+  // 768x768 219 / 208.  gemm_tn=pp256 / ring force one of them; "pp256" and "w4" fall back to the ring when ineligible.
+  const bool pp_fits = tp_eligible(M, N1, N2) && tp_map_ok(amap) && tp_map_ok(bmap);
+  if (dtype != VTX_BF16) {
+    small(TK_F32, TN_BKM32, (size_t)2 * TN_BKM32 * TN_LD32 * 4);
+  } else if (o.tn_safe || o.gemm_nodma) {
+    small(o.tn_safe ? TK_SAFE : TK_NODMA, TN_BKM, (size_t)2 * TN_BKM * TN_LD * 2);
+  } else if (pp_fits && (o.gemm_tn == TN_W4 || o.gemm_tn == TN_PP256 || o.gemm_tn == TN_AUTO)) {
+    // w4 (one wave per SIMD, 128 x 128 wave tiles) takes the same tile / slab partition as the ping-pong kernel: bit-identical
+    // slabs.  Every slab spans >= 2 K tiles: M >= 4096 (tp_eligible) and tp_splits <= M / 128, so M / slabs >= 128 = 2 * TP_BK.
+    static_assert(TP_BK == 64, "tp_splits caps the slab count at M / 128 = M / (2 * TP_BK)");
+    const bool w4 = o.gemm_tn == TN_W4;
+    p.kernel = w4 ? TK_W4 : o.pp_trace ? TK_PP256_TRACE : TK_PP256;   // (trace: the phase stamps of tools/tn_timeline.py)
+    p.block = w4 ? TW_THREADS : TP_THREADS; p.lds = w4 ? TW_LDS_BYTES : TP_LDS_BYTES;
+    p.tiles2 = cdiv(N2, 256); p.tiles12 = cdiv(N1, 256) * p.tiles2; p.cs_fold = p.tiles2;
+    p.slabs = tp_splits(M, N1, N2);
+    p.m_per = (M / p.slabs) / TP_BK * TP_BK;                   // the last slab also takes the remainder
+  } else if (o.gemm_tn != TN_DMA2 && M >= 1024) {
+    const size_t ring_bytes = (size_t)TR_NBUF * TR_STAGE * 2, stage_bytes = (size_t)8 * 32 * STAGE_LD * 4;
+    p.kernel = TK_RING; p.block = 512; p.lds = ring_bytes > stage_bytes ? ring_bytes : stage_bytes;
+    p.tiles2 = tiles2; p.tiles12 = cdiv(N1, 256) * tiles2; p.cs_fold = tiles2;
+    // one resident round: 2 workgroups per CU x 256 CUs = 512 slots, as full as the workspace allows
+    int s = 512 / p.tiles12;
+    if (s > tn_ws_slabs(M, N1, N2)) s = tn_ws_slabs(M, N1, N2);
+    if (s > M / (2 * TR_BKM)) s = M / (2 * TR_BKM);
+    p.slabs = s < 1 ? 1 : s;
+    p.m_per = cdiv(cdiv(M, p.slabs), TR_BKM) * TR_BKM;
+  } else {
+    small(TK_DMA2, TN_BKM, (size_t)4 * TN_BKM * TN_DLD * 2);
+  }
+  p.grid = (unsigned)(p.tiles12 * p.slabs);
+  p.slab_stride = (long)N1 * N2 + (long)p.cs_fold * N1;
+  p.red_n = (long)N1 * N2 + (has_colsum ? N1 : 0);
+  p.red_fold = has_colsum ? p.cs_fold : 1;
+  return p;
+}
+
 }  // namespace vtx
 
 using namespace vtx;
 
+// Every plan of tn_plan fits: no kernel asks for more slabs than tn_ws_slabs, none keeps more column-sum copies per slab than the
+// ring's one per 128-column tile.  vtx_gemm_tn checks the plan it chose against the caller's bytes.
 extern "C" size_t vtx_gemm_tn_workspace(int M, int N1, int N2) {
-  size_t s = (size_t)tn_splits(M, N1, N2);
-  if (tp_eligible(M, N1, N2) && (size_t)tp_splits(M, N1, N2) > s) s = (size_t)tp_splits(M, N1, N2);
-  // slabs + column-sum slabs (the ring and ping-pong kernels keep one partial copy per column tile)
-  return s * (size_t)N1 * (size_t)N2 * sizeof(float) + s * (size_t)N1 * (size_t)cdiv(N2, 128) * sizeof(float);
+  return tn_slab_bytes(tn_ws_slabs(M, N1, N2), (long)N1 * N2 + (long)cdiv(N2, 128) * N1);
+}
+
+template <auto Kernel, typename T, typename... Extra>
+static void tn_launch(const TnPlan& p, const vtx_gemm_tn_desc* d, const TnOut& out, hipStream_t st, Extra... extra) {
+  if (p.kernel >= TK_RING) allow_lds<Kernel>(p.lds, p.lds);    // (the 128 x 128 kernels have always run their 68 KB without the opt-in)
+  hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.block), p.lds, st, d->M, p.m_per, (const T*)d->A, d->lda, d->amap,
+                     (const T*)d->B, d->ldb, d->bmap, p.tiles2, p.tiles12, out, extra...);
 }
 
 extern "C" int vtx_gemm_tn(const vtx_gemm_tn_desc* d, void* stream) {
@@ -1472,129 +1548,31 @@ extern "C" int vtx_gemm_tn(const vtx_gemm_tn_desc* d, void* stream) {
                   d->lda % vec == 0 && d->ldb % vec == 0, VTX_EALIGN, "gemm_tn: 16-byte alignment required");
   VTX_REQUIRE(d->ws_bytes >= vtx_gemm_tn_workspace(d->M, d->N1, d->N2), VTX_EWS, "gemm_tn: workspace too small");
 
-  const int splits = tn_splits(d->M, d->N1, d->N2);
-  const int tile_m = d->dtype == VTX_BF16 ? TN_BKM : TN_BKM32;
-  int m_per = cdiv(d->M, splits);
-  m_per = cdiv(m_per, tile_m) * tile_m;
-  const int tiles1 = cdiv(d->N1, 128), tiles2 = cdiv(d->N2, 128);
-  TnOut out;
-  // per-split slab = [N1*N2 weight partials | N1 column-sum partials]
+  const TnPlan p = tn_plan(d->dtype, d->M, d->N1, d->N2, d->amap, d->bmap, d->colsum != nullptr, options());
+  VTX_REQUIRE(tn_slab_bytes(p.slabs, p.slab_stride) <= d->ws_bytes, VTX_EWS, "gemm_tn: the plan's %d slabs of %ld floats outgrow the workspace",
+              p.slabs, p.slab_stride);
   const long w_elems = (long)d->N1 * d->N2;
-  out.slab = (float*)d->workspace; out.slab_stride = w_elems + d->N1; out.N1 = d->N1; out.N2 = d->N2;
-  out.cslab = d->colsum ? out.slab + w_elems : nullptr; out.cs_fold = 1;
-  dim3 grid(tiles1 * tiles2 * splits), block(NT_THREADS);
+  TnOut out;
+  out.slab = (float*)d->workspace; out.slab_stride = p.slab_stride; out.N1 = d->N1; out.N2 = d->N2;
+  out.cslab = d->colsum ? out.slab + w_elems : nullptr; out.cs_fold = p.cs_fold;
   hipStream_t st = as_stream(stream);
-  if (d->dtype == VTX_BF16) {
-    const size_t need = (size_t)2 * TN_BKM * TN_LD * 2;
-    const size_t lds = STAGE_BYTES > need ? STAGE_BYTES : need;
-    const Options& o = options();
-    const bool safe = o.tn_safe != 0, nodma = o.gemm_nodma != 0;
-    const bool want_ring = o.gemm_tn != TN_DMA2 && d->M >= 1024;   // "pp256" falls back to the ring when ineligible
-    // Default: the 256x256 ping-pong kernel wherever it is eligible (M >= 4096, N1 and N2 multiples of 256, row-map
-    // groups > 64 rows), the 256x128 ring (2 workgroups per CU) otherwise.  tools/tn_compare.py at M = 150528 with the
-    // fused bias-gradient sums, ring / ping-pong: 768x3072 974 / 731 us, 3072x768 791 / 708, 2304x768 603 / 551,
-    // 768x768 219 / 208.  gemm_tn=pp256 / ring force one of them.
-    const bool pp_fits = tp_eligible(d->M, d->N1, d->N2) && tp_map_ok(d->amap) && tp_map_ok(d->bmap);
-    const bool want_pp = pp_fits && (o.gemm_tn == TN_PP256 || o.gemm_tn == TN_AUTO);
-    if (!safe && !nodma && pp_fits && o.gemm_tn == TN_W4) {
-      // one wave per SIMD, 128 x 128 wave tiles: the same tile / slab partition as the ping-pong kernel (bit-identical slabs)
-      const int t1p = cdiv(d->N1, 256), t2p = cdiv(d->N2, 256);
-      const int s_p = tp_splits(d->M, d->N1, d->N2);
-      const int m_per_p = (d->M / s_p) / TP_BK * TP_BK;
-      static std::atomic<unsigned long long> attr_set_w{0};
-      if (first_launch_on_device(attr_set_w))
-      {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_bf16_w4_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_bf16_w4_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_LDS_BYTES);
-      }
-      if (m_per_p >= 2 * TP_BK) {
-        out.slab_stride = w_elems + (long)t2p * d->N1; out.cs_fold = t2p;
-        if (out.cslab)
-          hipLaunchKernelGGL(gemm_tn_bf16_w4_kernel<true>, dim3(t1p * t2p * s_p), dim3(TW_THREADS), TW_LDS_BYTES, st, d->M, m_per_p,
-                             (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, t2p, t1p * t2p, out);
-        else
-          hipLaunchKernelGGL(gemm_tn_bf16_w4_kernel<false>, dim3(t1p * t2p * s_p), dim3(TW_THREADS), TW_LDS_BYTES, st, d->M, m_per_p,
-                             (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, t2p, t1p * t2p, out);
-        int rc_w = check_launch("gemm_tn_w4");
-        if (rc_w) return rc_w;
-        if (!d->colsum) return launch_reduce_partials(out.slab, s_p, out.slab_stride, w_elems, d->C, d->accumulate, 1.0f, st);
-        return launch_reduce_partials(out.slab, s_p, out.slab_stride, w_elems + d->N1, d->C, d->accumulate, 1.0f, st,
-                                      d->colsum, w_elems, d->colsum_accumulate, t2p, d->N1);
-      }
-    }
-    if (!safe && !nodma && want_pp) {
-      const int t1p = cdiv(d->N1, 256), t2p = cdiv(d->N2, 256);
-      const int s_p = tp_splits(d->M, d->N1, d->N2);
-      const int m_per_p = (d->M / s_p) / TP_BK * TP_BK;        // the last split also takes the remainder
-      const int s_eff = s_p;
-      static std::atomic<unsigned long long> attr_set_p{0};
-      if (first_launch_on_device(attr_set_p)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_bf16_pp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_BYTES);
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_bf16_pp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TP_LDS_BYTES);
-      }
-      if (m_per_p >= 2 * TP_BK) {
-        out.slab_stride = w_elems + (long)t2p * d->N1; out.cs_fold = t2p;
-        long long* trace_p = reinterpret_cast<long long*>(o.pp_trace);
-        if (trace_p)                                 // diagnostic instantiation with the phase stamps (tools/tn_timeline.py)
-          hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<true>, dim3(t1p * t2p * s_eff), dim3(TP_THREADS), TP_LDS_BYTES, st, d->M, m_per_p,
-                             (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, t2p, t1p * t2p, out, trace_p);
-        else
-          hipLaunchKernelGGL(gemm_tn_bf16_pp_kernel<false>, dim3(t1p * t2p * s_eff), dim3(TP_THREADS), TP_LDS_BYTES, st, d->M, m_per_p,
-                             (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, t2p, t1p * t2p, out, nullptr);
-        int rc_p = check_launch("gemm_tn_pp");
-        if (rc_p) return rc_p;
-        if (!d->colsum) return launch_reduce_partials(out.slab, s_eff, out.slab_stride, w_elems, d->C, d->accumulate, 1.0f, st);
-        return launch_reduce_partials(out.slab, s_eff, out.slab_stride, w_elems + d->N1, d->C, d->accumulate, 1.0f, st,
-                                      d->colsum, w_elems, d->colsum_accumulate, t2p, d->N1);
-      }
-      out.slab_stride = w_elems + d->N1; out.cs_fold = 1;
-    }
-    if (!safe && !nodma && want_ring) {
-      const int tiles1r = cdiv(d->N1, 256);
-      // one resident round: 2 workgroups per CU x 256 CUs = 512 slots, as full as the workspace allows
-      int s_r = 512 / (tiles1r * tiles2);
-      const int ws_splits = (tp_eligible(d->M, d->N1, d->N2) && tp_splits(d->M, d->N1, d->N2) > splits)
-                                ? tp_splits(d->M, d->N1, d->N2) : splits;   // slabs vtx_gemm_tn_workspace sized
-      if (s_r > ws_splits) s_r = ws_splits;
-      if (s_r > d->M / (2 * TR_BKM)) s_r = d->M / (2 * TR_BKM);
-      if (s_r < 1) s_r = 1;
-      int m_per_r = cdiv(cdiv(d->M, s_r), TR_BKM) * TR_BKM;
-      const size_t ring_bytes = (size_t)TR_NBUF * TR_STAGE * 2;
-      const size_t lds_r = ring_bytes > (size_t)8 * 32 * STAGE_LD * 4 ? ring_bytes : (size_t)8 * 32 * STAGE_LD * 4;
-      static std::atomic<unsigned long long> attr_set{0};
-      if (first_launch_on_device(attr_set)) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_bf16_ring_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-      }
-      out.slab_stride = w_elems + (long)tiles2 * d->N1; out.cs_fold = tiles2;
-      hipLaunchKernelGGL(gemm_tn_bf16_ring_kernel, dim3(tiles1r * tiles2 * s_r), dim3(512), lds_r, st, d->M, m_per_r,
-                         (const bf16raw*)d->A, d->lda, d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, tiles2, tiles1r * tiles2, out);
-      int rc_r = check_launch("gemm_tn_ring");
-      if (rc_r) return rc_r;
-      if (!d->colsum) return launch_reduce_partials(out.slab, s_r, out.slab_stride, w_elems, d->C, d->accumulate, 1.0f, st);
-      return launch_reduce_partials(out.slab, s_r, out.slab_stride, w_elems + d->N1, d->C, d->accumulate, 1.0f, st,
-                                    d->colsum, w_elems, d->colsum_accumulate, tiles2, d->N1);
-    } else if (!safe && !nodma) {
-      const size_t need_d = (size_t)4 * TN_BKM * TN_DLD * 2;
-      const size_t lds_d = STAGE_BYTES > need_d ? STAGE_BYTES : need_d;
-      hipLaunchKernelGGL(gemm_tn_bf16_dma_kernel, grid, block, lds_d, st, d->M, m_per, (const bf16raw*)d->A, d->lda,
-                         d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, tiles2, tiles1 * tiles2, out);
-    } else if (safe)
-      hipLaunchKernelGGL(gemm_tn_bf16_kernel<true>, grid, block, lds, st, d->M, m_per, (const bf16raw*)d->A, d->lda,
-                         d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, tiles2, tiles1 * tiles2, out);
-    else
-      hipLaunchKernelGGL(gemm_tn_bf16_kernel<false>, grid, block, lds, st, d->M, m_per, (const bf16raw*)d->A, d->lda,
-                         d->amap, (const bf16raw*)d->B, d->ldb, d->bmap, tiles2, tiles1 * tiles2, out);
-  } else {
-    const size_t need = (size_t)2 * TN_BKM32 * TN_LD32 * 4;
-    const size_t lds = STAGE_BYTES > need ? STAGE_BYTES : need;
-    hipLaunchKernelGGL(gemm_tn_f32_kernel, grid, block, lds, st, d->M, m_per, (const float*)d->A, d->lda, d->amap,
-                       (const float*)d->B, d->ldb, d->bmap, tiles2, tiles1 * tiles2, out);
+  switch (p.kernel) {
+    case TK_F32: tn_launch<gemm_tn_f32_kernel, float>(p, d, out, st); break;
+    case TK_SAFE: tn_launch<gemm_tn_bf16_kernel<true>, bf16raw>(p, d, out, st); break;
+    case TK_NODMA: tn_launch<gemm_tn_bf16_kernel<false>, bf16raw>(p, d, out, st); break;
+    case TK_DMA2: tn_launch<gemm_tn_bf16_dma_kernel, bf16raw>(p, d, out, st); break;
+    case TK_RING: tn_launch<gemm_tn_bf16_ring_kernel, bf16raw>(p, d, out, st); break;
+    case TK_PP256: tn_launch<gemm_tn_bf16_pp_kernel<false>, bf16raw>(p, d, out, st, (long long*)nullptr); break;
+    case TK_PP256_TRACE: tn_launch<gemm_tn_bf16_pp_kernel<true>, bf16raw>(p, d, out, st, reinterpret_cast<long long*>(options().pp_trace)); break;
+    case TK_W4:
+      if (out.cslab) tn_launch<gemm_tn_bf16_w4_kernel<true>, bf16raw>(p, d, out, st);
+      else tn_launch<gemm_tn_bf16_w4_kernel<false>, bf16raw>(p, d, out, st);
+      break;
   }
-  int rc = check_launch("gemm_tn");
+  const int rc = check_launch("gemm_tn");
   if (rc) return rc;
-  if (!d->colsum) return launch_reduce_partials(out.slab, splits, out.slab_stride, w_elems, d->C, d->accumulate, 1.0f, st);
-  return launch_reduce_partials(out.slab, splits, out.slab_stride, w_elems + d->N1, d->C, d->accumulate, 1.0f, st,
-                                d->colsum, w_elems, d->colsum_accumulate);
+  return launch_reduce_partials(out.slab, p.slabs, p.slab_stride, p.red_n, d->C, d->accumulate, 1.0f, st,
+                                d->colsum, w_elems, d->colsum_accumulate, p.red_fold, d->N1);
 }
 
 extern "C" size_t vtx_colsum_workspace(int M, int N) {

@@ -432,20 +432,18 @@ extern "C" int vtx_hog_fwd(const uint8_t* frames, int F, int H, int W, const dou
   // W <= 256: the three channels side by side (768 threads); wider frames: one channel at a time (256 threads, one magnitude tile)
   const int cp = W <= 256 ? 3 : 1;
   const size_t lds = (size_t)HOG_EXC_WORDS * 4 + (size_t)30 * W + (size_t)cp * 8 * W * 8 + (size_t)cp * (W / 8) * 18 * 4 + (size_t)(W / 8) * 27 * 8;
-  static std::atomic<unsigned long long> attr_set{0};
-  if (first_launch_on_device(attr_set)) {
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&hog_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(&hog_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  }
   // persistent: as many workgroups as fit at once (LDS- and wave-limited), each walks strips with stride gridDim
   const long items = (long)F * (H / 8);
   long per_cu = (long)(160 * 1024) / (long)lds; if (per_cu < 1) per_cu = 1;
   const long wave_cap = 32 / (4 * cp); if (per_cu > wave_cap) per_cu = wave_cap;
   long grid = per_cu * device_cus(); if (grid > items) grid = items;
-  if (cp == 3)
+  if (cp == 3) {
+    allow_lds<hog_kernel<3>>(lds);
     hipLaunchKernelGGL(hog_kernel<3>, dim3((unsigned)grid), dim3(768), lds, as_stream(stream), frames, F, H, W, exc, out, bins);
-  else
+  } else {
+    allow_lds<hog_kernel<1>>(lds);
     hipLaunchKernelGGL(hog_kernel<1>, dim3((unsigned)grid), dim3(256), lds, as_stream(stream), frames, F, H, W, exc, out, bins);
+  }
   return check_launch("hog_fwd");
 }
 

@@ -416,12 +416,6 @@ __global__ __launch_bounds__(THREADS, 2) void bwd_dkv_kernel(int Lq, int Lk, int
 template <int HD> constexpr size_t lds_fwd() { return (size_t)(2 * CHUNK * HD + 4 * 32 * HD) * 2; }
 template <int HD> constexpr size_t lds_dkv() { return (size_t)(2 * CHUNK * HD) * 2 + 2 * CHUNK * 4; }
 
-template <auto Kernel> static void allow(size_t lds) {
-  static std::atomic<unsigned long long> seen{0};
-  if (lds > 65536 && first_launch_on_device(seen))
-    hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
 }  // namespace xa
 
 bool xattn_mfma_eligible(int dtype, int hd) { return dtype == VTX_BF16 && (hd == 96 || hd == 64); }
@@ -440,7 +434,7 @@ int xattn_mfma_splits(int B, int Lq, int Lk, int heads) {
 template <int HD>
 static int xattn_fwd_t(const vtx_xattn_desc* d, hipStream_t st) {
   const dim3 g(cdiv(d->Lq, 128), d->heads, d->B), blk(xa::THREADS);
-  xa::allow<xa::fwd_kernel<HD>>(xa::lds_fwd<HD>());
+  allow_lds<xa::fwd_kernel<HD>>(xa::lds_fwd<HD>());
   hipLaunchKernelGGL((xa::fwd_kernel<HD>), g, blk, xa::lds_fwd<HD>(), st, d->Lq, d->Lk, d->heads, d->scale, (const bf16raw*)d->q,
                      (const bf16raw*)d->k, (const bf16raw*)d->v, (bf16raw*)d->out, d->lse);
   return check_launch("xattn_fwd_mfma");
@@ -454,7 +448,7 @@ template <int HD>
 static int xattn_bwd_t(const vtx_xattn_desc* d, const void* dout, float* delta, void* dq, int nsplit, float* part_k, float* part_v,
                        long part_stride, hipStream_t st) {
   const dim3 gq(cdiv(d->Lq, 128), d->heads, d->B), blk(xa::THREADS);
-  xa::allow<xa::bwd_dq_kernel<HD>>(xa::lds_fwd<HD>());
+  allow_lds<xa::bwd_dq_kernel<HD>>(xa::lds_fwd<HD>());
   hipLaunchKernelGGL((xa::bwd_dq_kernel<HD>), gq, blk, xa::lds_fwd<HD>(), st, d->Lq, d->Lk, d->heads, d->scale, (const bf16raw*)d->q,
                      (const bf16raw*)d->k, (const bf16raw*)d->v, (const bf16raw*)d->out, (const bf16raw*)dout, d->lse, delta,
                      (bf16raw*)dq);
@@ -463,7 +457,7 @@ static int xattn_bwd_t(const vtx_xattn_desc* d, const void* dout, float* delta, 
   const int kgroups = cdiv(cdiv(d->Lk, 32), 4);
   const int q_per = cdiv(cdiv(d->Lq, nsplit), xa::CHUNK) * xa::CHUNK;
   const dim3 gk(kgroups * nsplit, d->heads, d->B);
-  xa::allow<xa::bwd_dkv_kernel<HD>>(xa::lds_dkv<HD>());
+  allow_lds<xa::bwd_dkv_kernel<HD>>(xa::lds_dkv<HD>());
   hipLaunchKernelGGL((xa::bwd_dkv_kernel<HD>), gk, blk, xa::lds_dkv<HD>(), st, d->Lq, d->Lk, d->heads, d->scale, (const bf16raw*)d->q,
                      (const bf16raw*)d->k, (const bf16raw*)d->v, (const bf16raw*)dout, d->lse, delta, kgroups, q_per, part_k, part_v,
                      part_stride);
