@@ -204,15 +204,27 @@ int vtx_colsum(int dtype, int M, int N, const void* A, long lda, vtx_rowmap amap
  *   order [B, 1+P*T, 3D]; sequence s=(b,t) has L = 1+P tokens: i=0 is the cls
  *   row of clip b, i>=1 is token 1+(i-1)*T+t.  out is [B*P*T + B*T, D]: token
  *   rows first (clip-major, (p t) order, no cls), then one cls row per (b,t).
+ * mode VTX_ATTN_TIME_CLS : divided temporal attention over the cls token (the
+ *   space-then-time operator order, transformer.py:250-258).  qkv as in SPACE;
+ *   sequence s=(b,p), S = B*P, has L = 1+T tokens: i=0 is the cls row of clip b,
+ *   i>=1 is row 1+p*T+(i-1) of clip b (consecutive rows).  out is
+ *   [B*P*T + B*P, D]: token rows first (clip-major, (p t), no cls), then one cls
+ *   row per (b,p).
+ * mode VTX_ATTN_SPACE_NOCLS : divided spatial attention without the cls token
+ *   (transformer.py:345-350).  qkv as in SPACE; sequence s=(b,t), S = B*T, has
+ *   L = P tokens: token i is row 1+i*T+t of clip b.  out is [B*P*T, D],
+ *   clip-major (p t) order.  The cls rows of qkv are not read.
  * lse: [S,H,L] fp32 log-sum-exp (saved for backward).  probs (optional,
  *   fp32 [S,H,L,L]) materialises the softmax for get_last_selfattention
  *   (video_transformer.py:258-261). */
 #define VTX_ATTN_CONTIG 0
 #define VTX_ATTN_SPACE 1
+#define VTX_ATTN_TIME_CLS 2
+#define VTX_ATTN_SPACE_NOCLS 3
 typedef struct {
   int dtype, mode;
   int S, L, H, hd;
-  int B, T, P;                  /* VTX_ATTN_SPACE only */
+  int B, T, P;                  /* every mode but VTX_ATTN_CONTIG */
   const void* qkv; long ld_qkv;
   void* out; long ld_out;
   float* lse;
@@ -224,7 +236,10 @@ int vtx_attn_fwd(const vtx_attn_desc* d, void* stream);
 /* dqkv from (qkv, out, dout, lse).  dout/out share the forward `out` layout.
  * VTX_ATTN_SPACE: token rows of dqkv in natural order; the T per-frame
  * gradients of each clip's cls row go to dqkv_cls [B*T, 3D] (same dtype) and
- * are summed over t by vtx_cls_qkv_reduce.  delta: [S,H,L] fp32 scratch. */
+ * are summed over t by vtx_cls_qkv_reduce.  VTX_ATTN_TIME_CLS: the same with
+ * the P per-sequence gradients of the cls row in dqkv_cls [B*P, 3D] (summed by
+ * vtx_cls_qkv_reduce called with P).  VTX_ATTN_SPACE_NOCLS: the cls rows of
+ * dqkv are written as zeros; dqkv_cls is not used.  delta: [S,H,L] fp32 scratch. */
 typedef struct {
   vtx_attn_desc f;
   const void* dout; long ld_dout;
@@ -245,7 +260,9 @@ int vtx_fact_glue_fwd(int dtype, int B, int T, int P, int D, const void* x, cons
 int vtx_fact_glue_bwd(int dtype, int B, int T, int P, int D, const void* dh, void* dx, float* d_time_embed, int accumulate,
                       void* stream);
 /* da[0:B*N]   = dout[b,1+n] * s[b*T + n%T];  da[B*N + b*T+t] = dout[b,0] * s[b*T+t] / T
- * (backward of transformer.py:367-377; s may be NULL = 1) */
+ * (backward of transformer.py:367-377; s may be NULL = 1).
+ * P < 0: T sequences per clip of -P CONSECUTIVE tokens each (temporal attention over the cls token, transformer.py:265-277,
+ * called with T = patches, P = -frames): da[0:B*N] = dout[b,1+n] * s[b*T + n/(-P)], the cls rows as above. */
 int vtx_space_grad_prep(int dtype, int B, int T, int P, int D, const void* dout, long ld,
                         const float* s, void* da, long ldda, void* stream);
 /* dqkv[b,0,:] = sum_t dqkv_cls[b*T+t,:]  (cls row replicated per frame, transformer.py:354-356) */

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(AttnP p, const 
   if (w.active) {
 #pragma unroll
     for (int e = 0; e < HD; ++e) dq[e] *= p.scale;
-    T* dst = (p.mode == VTX_ATTN_SPACE && w.i == 0) ? dqkv_cls + (long)s * p.ld_dqkv + h * HD
+    T* dst = attn_cls_row(p, w.i) ? dqkv_cls + (long)s * p.ld_dqkv + h * HD
                                                     : dqkv + in_row(p, s, w.i) * p.ld_dqkv + h * HD;
     store_vec<T, HD>(dst, dq);
   }
@@ -294,21 +294,23 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
   if (w.active) {
 #pragma unroll
     for (int e = 0; e < HD; ++e) dk[e] *= p.scale;
-    T* base = (p.mode == VTX_ATTN_SPACE && w.i == 0) ? dqkv_cls + (long)s * p.ld_dqkv
+    T* base = attn_cls_row(p, w.i) ? dqkv_cls + (long)s * p.ld_dqkv
                                                      : dqkv + in_row(p, s, w.i) * p.ld_dqkv;
     store_vec<T, HD>(base + D + h * HD, dk);
     store_vec<T, HD>(base + 2 * D + h * HD, dv);
   }
 }
 
-// Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins:
+// Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins.  The mode matters
+// up to 32 tokens only: CONTIG and TIME_CLS are packed, SPACE_NOCLS runs the one-workgroup kernels at one tile, SPACE (no model
+// has P < 32) the VALU kernels as before.
 enum Route { SMALL, MFMA, LONG, F32, VALU };
 static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // VTX_ATTN_VALU=1 forces the VALU path.
   if (options().attn_valu) return VALU;
   if (attn_small_eligible(dtype, mode, L, hd)) return SMALL;
-  // bf16, head_dim 64, 33..256 tokens -> MFMA kernels (attn_mfma.hip).
-  if (attn_mfma_eligible(dtype, L, hd)) return MFMA;
+  // bf16, head_dim 64, 33..256 tokens (SPACE_NOCLS: 1..256) -> MFMA kernels (attn_mfma.hip).
+  if (attn_mfma_eligible(dtype, mode, L, hd)) return MFMA;
   // bf16, head_dim 64, more than 256 tokens -> chunk-streaming MFMA kernels (attn_long.hip); VTX_ATTN_LONG=0 sends them back here.
   if (options().attn_long && attn_long_eligible(dtype, L, hd)) return LONG;
   // fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu sends them back here, and
@@ -320,11 +322,17 @@ static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
 static int make_params(const vtx_attn_desc* d, AttnP& p, const char* who) {
   VTX_REQUIRE(d->S > 0 && d->L > 0 && d->H > 0, VTX_EINVAL, "%s: bad shape S=%d L=%d H=%d", who, d->S, d->L, d->H);
   VTX_REQUIRE(d->hd == 64, VTX_EINVAL, "%s: head_dim %d unsupported (64 only)", who, d->hd);
-  VTX_REQUIRE(d->mode == VTX_ATTN_CONTIG || d->mode == VTX_ATTN_SPACE, VTX_EINVAL, "%s: bad mode", who);
+  VTX_REQUIRE(d->mode == VTX_ATTN_CONTIG || d->mode == VTX_ATTN_SPACE || d->mode == VTX_ATTN_TIME_CLS ||
+                  d->mode == VTX_ATTN_SPACE_NOCLS,
+              VTX_EINVAL, "%s: bad mode", who);
   VTX_REQUIRE(d->dtype == VTX_F32 || d->dtype == VTX_BF16, VTX_EINVAL, "%s: bad dtype", who);
+  const bool btp = d->B > 0 && d->T > 0 && d->P > 0;
   if (d->mode == VTX_ATTN_SPACE)
-    VTX_REQUIRE(d->B > 0 && d->T > 0 && d->P > 0 && d->S == d->B * d->T && d->L == d->P + 1, VTX_EINVAL,
-                "%s: SPACE mode needs S == B*T and L == P+1", who);
+    VTX_REQUIRE(btp && d->S == d->B * d->T && d->L == d->P + 1, VTX_EINVAL, "%s: SPACE mode needs S == B*T and L == P+1", who);
+  if (d->mode == VTX_ATTN_TIME_CLS)
+    VTX_REQUIRE(btp && d->S == d->B * d->P && d->L == d->T + 1, VTX_EINVAL, "%s: TIME_CLS mode needs S == B*P and L == T+1", who);
+  if (d->mode == VTX_ATTN_SPACE_NOCLS)
+    VTX_REQUIRE(btp && d->S == d->B * d->T && d->L == d->P, VTX_EINVAL, "%s: SPACE_NOCLS mode needs S == B*T and L == P", who);
   const long vec = d->dtype == VTX_BF16 ? 8 : 4;
   VTX_REQUIRE(d->qkv && aligned16(d->qkv) && d->ld_qkv % vec == 0, VTX_EALIGN, "%s: qkv alignment", who);
   p.mode = d->mode; p.S = d->S; p.L = d->L; p.H = d->H; p.B = d->B; p.T = d->T; p.P = d->P;
@@ -394,11 +402,18 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
   if (rc) return rc;
   VTX_REQUIRE(d->f.out && d->f.lse && d->dout && d->dqkv && d->delta, VTX_EINVAL, "attn_bwd: null pointer");
   VTX_REQUIRE(d->f.mode != VTX_ATTN_SPACE || d->dqkv_cls, VTX_EINVAL, "attn_bwd: SPACE mode needs dqkv_cls");
+  VTX_REQUIRE(d->f.mode != VTX_ATTN_TIME_CLS || d->dqkv_cls, VTX_EINVAL, "attn_bwd: TIME_CLS mode needs dqkv_cls");
   VTX_REQUIRE(aligned16(d->dout) && aligned16(d->dqkv), VTX_EALIGN, "attn_bwd: alignment");
   p.ld_dout = d->ld_dout; p.ld_dqkv = d->ld_dqkv;
   hipStream_t st = as_stream(stream);
+  if (d->f.mode == VTX_ATTN_SPACE_NOCLS) {           // no sequence holds the cls rows: their gradient is zero
+    const size_t es = d->f.dtype == VTX_F32 ? 4 : 2;
+    const hipError_t e = hipMemset2DAsync(d->dqkv, (size_t)(1 + (long)d->f.P * d->f.T) * d->ld_dqkv * es, 0,
+                                          (size_t)3 * d->f.H * d->f.hd * es, (size_t)d->f.B, st);
+    VTX_REQUIRE(e == hipSuccess, VTX_EINVAL, "attn_bwd: zeroing the cls rows of dqkv: %s", hipGetErrorString(e));
+  }
   switch (attn_route(d->f.dtype, d->f.mode, d->f.L, d->f.hd, false)) {
-    case SMALL: return attn_bwd_small_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, st);
+    case SMALL: return attn_bwd_small_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
     case MFMA: return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);

@@ -13,14 +13,29 @@ struct AttnP {
   int G;                        // sequences per workgroup
 };
 
+// Row addressing of the four layouts (include/vtx.h).  Every layout but CONTIG reads qkv in the natural token order
+// [B, 1 + P*T, 3D], tokens in (p t) order:
+//   SPACE        s = (b, t), i = 0 the clip's cls row, i >= 1 token row 1 + (i-1)*T + t;   out: tokens, then a cls row per s
+//   TIME_CLS     s = (b, p), i = 0 the clip's cls row, i >= 1 token row 1 + p*T + (i-1);   out: tokens, then a cls row per s
+//   SPACE_NOCLS  s = (b, t), token row 1 + i*T + t for every i (no cls row);               out: tokens
+__device__ inline bool attn_has_cls(int mode) { return mode == VTX_ATTN_SPACE || mode == VTX_ATTN_TIME_CLS; }
+// the gradient of row i of sequence s goes to dqkv_cls[s] (one row per sequence, summed by vtx_cls_qkv_reduce), not to dqkv
+__device__ inline bool attn_cls_row(const AttnP& p, int i) { return i == 0 && attn_has_cls(p.mode); }
 __device__ inline long in_row(const AttnP& p, int s, int i) {
   if (p.mode == VTX_ATTN_CONTIG) return (long)s * p.L + i;
+  if (p.mode == VTX_ATTN_TIME_CLS) {
+    const int b = s / p.P;                          // token rows of (b, p): b * (1 + P*T) + 1 + p*T + (i-1) = s*T + b + i
+    return i == 0 ? (long)b * (1 + (long)p.P * p.T) : (long)s * p.T + b + i;
+  }
   const int b = s / p.T, t = s - b * p.T;
+  if (p.mode == VTX_ATTN_SPACE_NOCLS) return (long)b * (1 + (long)p.P * p.T) + 1 + (long)i * p.T + t;
   return (long)b * (1 + (long)p.P * p.T) + (i == 0 ? 0 : 1 + (long)(i - 1) * p.T + t);
 }
 __device__ inline long out_row(const AttnP& p, int s, int i) {
   if (p.mode == VTX_ATTN_CONTIG) return (long)s * p.L + i;
+  if (p.mode == VTX_ATTN_TIME_CLS) return i == 0 ? (long)p.B * p.P * p.T + s : (long)s * p.T + (i - 1);
   const int b = s / p.T, t = s - b * p.T;
+  if (p.mode == VTX_ATTN_SPACE_NOCLS) return (long)b * p.P * p.T + (long)i * p.T + t;
   return i == 0 ? (long)p.B * p.P * p.T + s : (long)b * p.P * p.T + (long)(i - 1) * p.T + t;
 }
 
@@ -122,24 +137,41 @@ __device__ inline bf16x8 frag_cols_o(const bf16raw* lds, int row0, int n2, const
 
 // Row addressing of one sequence in closed form: row(i) = i == 0 ? row0 : base + i * stride (contiguous sequences:
 // row0 = base, stride 1; divided spatial attention: row 0 is the clip's cls row / its per-frame copy, token i >= 1 sits
-// i * T rows further).  in_row / out_row (attn_common.h) compute the same rows with a division per call; per lane and row
-// that was ~40 vector instructions around every fragment load and row store of kernels bound by vector-ALU issue.
+// i * T rows further; temporal attention over the cls token: the same row 0, tokens on consecutive rows; spatial attention
+// without the cls token: every row on the line, T rows apart).  in_row / out_row (attn_common.h) compute the same rows with
+// a division per call; per lane and row that was ~40 vector instructions around every fragment load and row store of
+// kernels bound by vector-ALU issue.
 struct RowLin { long row0, base, stride; };
 __device__ inline RowLin lin_in(const AttnP& p, int s) {
   RowLin r;
   if (p.mode == VTX_ATTN_CONTIG) { r.base = (long)s * p.L; r.stride = 1; r.row0 = r.base; return r; }
+  if (p.mode == VTX_ATTN_TIME_CLS) {
+    const int b = s / p.P;
+    r.row0 = (long)b * (1 + (long)p.P * p.T);
+    r.stride = 1;
+    r.base = (long)s * p.T + b;                 // row(i) = b * (1 + P*T) + 1 + p*T + (i - 1)
+    return r;
+  }
   const int b = s / p.T, t = s - b * p.T;
   r.row0 = (long)b * (1 + (long)p.P * p.T);
   r.stride = p.T;
+  if (p.mode == VTX_ATTN_SPACE_NOCLS) { r.base = r.row0 + 1 + t; r.row0 = r.base; return r; }
   r.base = r.row0 + 1 + t - r.stride;           // row(i) = row0 + 1 + (i - 1) * T + t
   return r;
 }
 __device__ inline RowLin lin_out(const AttnP& p, int s) {
   RowLin r;
   if (p.mode == VTX_ATTN_CONTIG) { r.base = (long)s * p.L; r.stride = 1; r.row0 = r.base; return r; }
+  if (p.mode == VTX_ATTN_TIME_CLS) {
+    r.row0 = (long)p.B * p.P * p.T + s;
+    r.stride = 1;
+    r.base = (long)s * p.T - 1;                 // row(i) = (b*P + p) * T + (i - 1)
+    return r;
+  }
   const int b = s / p.T, t = s - b * p.T;
-  r.row0 = (long)p.B * p.P * p.T + s;
   r.stride = p.T;
+  if (p.mode == VTX_ATTN_SPACE_NOCLS) { r.base = (long)b * p.P * p.T + t; r.row0 = r.base; return r; }
+  r.row0 = (long)p.B * p.P * p.T + s;
   r.base = (long)b * p.P * p.T + t - r.stride;  // row(i) = b * P * T + (i - 1) * T + t
   return r;
 }
@@ -235,11 +267,11 @@ __device__ inline void store_rows_T(bf16raw* stg, const f32x16 (&acc)[2], float 
 
 
 // attn_mfma.hip
-bool attn_mfma_eligible(int dtype, int L, int hd);
+bool attn_mfma_eligible(int dtype, int mode, int L, int hd);
 bool attn_small_eligible(int dtype, int mode, int L, int hd);
 int attn_fwd_small_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                          hipStream_t st);
+                          void* dqkv_cls, hipStream_t st);
 int attn_fwd_mfma_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_mfma_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                          float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dq_mfma_kernel(AttnP p
     store_rows_T(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
       const int qq = qt * 32 + r;
       if (qq >= p.L) return nullptr;
-      return (p.mode == VTX_ATTN_SPACE && qq == 0) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
+      return attn_cls_row(p, qq) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
                                                     : dqkv + lin_row(li, qq) * p.ld_dqkv + h * 64;
     });
 #pragma unroll
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dkv_mfma_kernel(AttnP 
     auto base_of = [&](int r) -> bf16raw* {
       const int kk = kt * 32 + r;
       if (kk >= p.L) return nullptr;
-      return (p.mode == VTX_ATTN_SPACE && kk == 0) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
+      return attn_cls_row(p, kk) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
     };
     store_rows_T(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * 64 : nullptr; });
     store_rows_T(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * 64 : nullptr; });
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
       store_rows_T(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
         const int qq = wave * 32 + r;
         if (qq >= p.L) return nullptr;
-        return (p.mode == VTX_ATTN_SPACE && qq == 0) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
+        return attn_cls_row(p, qq) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
                                                       : dqkv + lin_row(li, qq) * p.ld_dqkv + h * 64;
       });
     }
@@ -584,7 +584,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
       auto base_of = [&](int r) -> bf16raw* {
         const int kk = wave * 32 + r;
         if (kk >= p.L) return nullptr;
-        return (p.mode == VTX_ATTN_SPACE && kk == 0) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
+        return attn_cls_row(p, kk) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
       };
       store_rows_T(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * 64 : nullptr; });
       store_rows_T(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * 64 : nullptr; });
@@ -1322,10 +1322,41 @@ __device__ inline void load_frags(bf16x8 (&f)[4], const bf16raw* base, long ld, 
   }
 }
 
+// Rows of a packed tile.  Tile row j < used belongs to sequence sq = tile * G + j / L, token i = j % L.  CONTIG: all tensors
+// hold it at row0 + j.  CLS (VTX_ATTN_TIME_CLS, sequence (b, p) = the clip's cls row + T consecutive token rows): qkv holds
+// token i >= 1 at sq * T + b + i and the cls row at b * (1 + P*T); out / dout hold it at sq * T + i - 1, the sequence's cls
+// row behind the B*P*T token rows; the gradient of the gathered cls row goes to dqkv_cls[sq], the P of them of a clip are
+// summed by vtx_cls_qkv_reduce.  lse / delta are [S, H, L] in every layout: index (sq * H + h) * L + i.
+template <bool CLS> struct SmallRows {
+  long in, out;          // rows of qkv / of out and dout
+  long grad;             // row of dqkv, or -1 - (row of dqkv_cls)
+  long lse;              // sq * H * L + i (without the head)
+};
+template <bool CLS>
+__device__ inline SmallRows<CLS> small_rows(const AttnP& p, int tile, int G, int j) {
+  SmallRows<CLS> r;
+  const int L = p.L;
+  if (!CLS) {
+    const long row = (long)tile * (G * L) + j;
+    const long sq = row / L;
+    r.in = r.out = r.grad = row;
+    r.lse = sq * p.H * L + (row - sq * L);
+    return r;
+  }
+  const int g = j / L, i = j - g * L;
+  const long sq = (long)tile * G + g;
+  const long b = sq / p.P;
+  r.in = i == 0 ? b * (1 + (long)p.P * p.T) : sq * p.T + b + i;
+  r.out = i == 0 ? (long)p.B * p.P * p.T + sq : sq * p.T + (i - 1);
+  r.grad = i == 0 ? -1 - sq : r.in;
+  r.lse = sq * p.H * L + i;
+  return r;
+}
+
 // HW (heads in the workgroup): wave w of a workgroup works on head w of ONE row tile, so that the workgroup as a whole
 // reads the tile's rows contiguously (32 x 3 H x 128 B) at one moment -- instead of one 128-B line out of every
 // 4.6 KB row per workgroup, with the other heads' lines of the same rows requested by other CUs at other times.
-template <bool HW>
+template <bool HW, bool CLS>
 __global__ __launch_bounds__(HW ? 1024 : MA_THREADS) void attn_fwd_small_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
                                                                     bf16raw* __restrict__ out, float* __restrict__ lse) {
   extern __shared__ __attribute__((aligned(16))) char sm_raw[];
@@ -1342,10 +1373,11 @@ __global__ __launch_bounds__(HW ? 1024 : MA_THREADS) void attn_fwd_small_kernel(
   const long row0 = (long)tile * used, total = (long)p.S * L;
   const int i = lane & 31;
   const bool valid = i < used && row0 + i < total;
+  const SmallRows<CLS> me = small_rows<CLS>(p, tile, G, valid ? i : 0);
   bf16x8 qf[4], kf[4], vf[4];
-  load_frags(qf, qkv, p.ld_qkv, h * 64, row0 + i, valid, lane);
-  load_frags(kf, qkv, p.ld_qkv, D + h * 64, row0 + i, valid, lane);
-  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, row0 + i, valid, lane);
+  load_frags(qf, qkv, p.ld_qkv, h * 64, me.in, valid, lane);
+  load_frags(kf, qkv, p.ld_qkv, D + h * 64, me.in, valid, lane);
+  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, me.in, valid, lane);
   put_tile(Vs, vf, lane);
   f32x16 st;
   zero16(st);
@@ -1384,18 +1416,16 @@ __global__ __launch_bounds__(HW ? 1024 : MA_THREADS) void attn_fwd_small_kernel(
   // whole 128-B rows through the (now idle) V tile: the direct store writes 8-byte pieces of 32 different rows per
   // instruction, and the vector memory pipeline handles those one line at a time
   store_rows_T(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
-    return (r < used && row0 + r < total) ? out + (row0 + r) * p.ld_out + h * 64 : nullptr;
+    return (r < used && row0 + r < total) ? out + small_rows<CLS>(p, tile, G, r).out * p.ld_out + h * 64 : nullptr;
   });
-  if (valid && lane < 32) {
-    const long sq = (row0 + i) / L;
-    lse[(sq * p.H + h) * L + (row0 + i - sq * L)] = m * LN2 + __logf(l);
-  }
+  if (valid && lane < 32) lse[me.lse + (long)h * L] = m * LN2 + __logf(l);
 }
 
-template <bool HW>
+template <bool HW, bool CLS>
 __global__ __launch_bounds__(HW ? 1024 : MA_THREADS, HW ? 1 : 4) void attn_bwd_small_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
                                                                     const bf16raw* __restrict__ o, const bf16raw* __restrict__ dout,
-                                                                    const float* __restrict__ lse, bf16raw* __restrict__ dqkv) {
+                                                                    const float* __restrict__ lse, bf16raw* __restrict__ dqkv,
+                                                                    bf16raw* __restrict__ dqkv_cls) {
   extern __shared__ __attribute__((aligned(16))) char sm_raw[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   // HW: the head groups of a row tile are CONSECUTIVE workgroups (blockIdx.x = head group): they run at the same time and read
@@ -1417,24 +1447,28 @@ __global__ __launch_bounds__(HW ? 1024 : MA_THREADS, HW ? 1 : 4) void attn_bwd_s
   const long row0 = (long)tile * used, total = (long)p.S * L;
   const int i = lane & 31;
   const bool valid = i < used && row0 + i < total;
+  const SmallRows<CLS> me = small_rows<CLS>(p, tile, G, valid ? i : 0);
   bf16x8 qf[4], kf[4], vf[4], df[4];
-  load_frags(qf, qkv, p.ld_qkv, h * 64, row0 + i, valid, lane);
-  load_frags(kf, qkv, p.ld_qkv, D + h * 64, row0 + i, valid, lane);
-  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, row0 + i, valid, lane);
-  load_frags(df, dout, p.ld_dout, h * 64, row0 + i, valid, lane);
+  load_frags(qf, qkv, p.ld_qkv, h * 64, me.in, valid, lane);
+  load_frags(kf, qkv, p.ld_qkv, D + h * 64, me.in, valid, lane);
+  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, me.in, valid, lane);
+  load_frags(df, dout, p.ld_dout, h * 64, me.out, valid, lane);
   float dl = 0.f;
   {
     bf16x8 of[4];
-    load_frags(of, o, p.ld_out, h * 64, row0 + i, valid, lane);
+    load_frags(of, o, p.ld_out, h * 64, me.out, valid, lane);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) dl += frag_dot(df[ks], of[ks]);
   }
   dl += __shfl_xor(dl, 32, 64);
   float l2 = 1e30f;
-  if (valid) {
-    const long sq = (row0 + i) / L;
-    l2 = lse[(sq * p.H + h) * L + (row0 + i - sq * L)] * LOG2E;
-  }
+  if (valid) l2 = lse[me.lse + (long)h * L] * LOG2E;
+  // destination of tile row r's gradient (column origin col of the [3D] row)
+  auto dst = [&](int r, int col) -> bf16raw* {
+    if (!(r < used && row0 + r < total)) return nullptr;
+    const long g = small_rows<CLS>(p, tile, G, r).grad;
+    return (CLS && g < 0 ? dqkv_cls + (-1 - g) * p.ld_dqkv : dqkv + g * p.ld_dqkv) + col + h * 64;
+  };
   put_tile(Ks, kf, lane);
   put_tile(Os, df, lane);
   if (lane < 32) { Ls[i] = l2; Ds[i] = dl; }
@@ -1470,9 +1504,7 @@ __global__ __launch_bounds__(HW ? 1024 : MA_THREADS, HW ? 1 : 4) void attn_bwd_s
         acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Ks, 16 * s2, n2 * 32, lane), db, acc[n2], 0, 0, 0);
     }
     // K tile: its last reader was the MFMA chain above
-    store_rows_T(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* {
-      return (r < used && row0 + r < total) ? dqkv + (row0 + r) * p.ld_dqkv + h * 64 : nullptr;
-    });
+    store_rows_T(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
   }
   // ---- phase 2: lanes = keys.  dV^T = dO^T P, dK^T = Q^T dS
   {
@@ -1517,58 +1549,71 @@ __global__ __launch_bounds__(HW ? 1024 : MA_THREADS, HW ? 1 : 4) void attn_bwd_s
         dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Qs, 16 * s2, n2 * 32, lane), db, dk[n2], 0, 0, 0);
       }
     }
-    auto dst = [&](int r, int col) -> bf16raw* {
-      return (r < used && row0 + r < total) ? dqkv + (row0 + r) * p.ld_dqkv + col + h * 64 : nullptr;
-    };
     store_rows_T(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
     store_rows_T(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
   }
 }
 
 // host-side launchers used by attn.hip's entry points --------------------------------------
-bool attn_mfma_eligible(int dtype, int L, int hd) {
-  return dtype == VTX_BF16 && hd == 64 && L > 32 && L <= 32 * MA_MAXT;
+// 33..256 tokens; and the one layout of up to 32 tokens that the packed kernels do not take: SPACE_NOCLS (rows of a sequence
+// T apart, so a 32-row tile of packed sequences is not a run of consecutive rows) runs here at one tile per sequence
+bool attn_mfma_eligible(int dtype, int mode, int L, int hd) {
+  return dtype == VTX_BF16 && hd == 64 && L <= 32 * MA_MAXT && (L > 32 || (mode == VTX_ATTN_SPACE_NOCLS && L >= 1));
 }
 bool attn_small_eligible(int dtype, int mode, int L, int hd) {
-  return dtype == VTX_BF16 && hd == 64 && mode == VTX_ATTN_CONTIG && L >= 1 && L <= 32;
+  return dtype == VTX_BF16 && hd == 64 && (mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_TIME_CLS) && L >= 1 && L <= 32;
 }
+// The persistent 7-tile kernels (attn_fwd_stream_mfma_kernel / attn_bwd_stream_mfma_kernel) address rows through mg_lin_in /
+// mg_lin_out, which know the two layouts of the default operator order; the other layouts of 193..224 tokens (SPACE_NOCLS at
+// 196) run the one-workgroup-per-(sequence, head) kernels, whose addressing is lin_in / lin_out.
+static bool mg_mode(int mode) { return mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_SPACE; }
 // heads per workgroup in the HW variants: option value n > 0, capped at 16 waves (1024 threads) and at H
 static int hw_waves(int n, int H) { n = n < H ? n : H; return n < 16 ? n : 16; }
 
-int attn_fwd_small_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+template <bool CLS>
+static int attn_fwd_small_launch_t(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
   const int G = 32 / p.L;
   const int ntiles = (p.S + G - 1) / G;
   if (options().attn_hw_fwd > 0) {
     const int w = hw_waves(options().attn_hw_fwd, p.H);
-    hipLaunchKernelGGL(attn_fwd_small_kernel<true>, dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), w * SM_WAVE_LDS_FWD, st, p, ntiles,
+    hipLaunchKernelGGL((attn_fwd_small_kernel<true, CLS>), dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), w * SM_WAVE_LDS_FWD, st, p, ntiles,
                        (const bf16raw*)qkv, (bf16raw*)out, lse);
   } else {
-    hipLaunchKernelGGL(attn_fwd_small_kernel<false>, dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_FWD, st, p, ntiles,
+    hipLaunchKernelGGL((attn_fwd_small_kernel<false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_FWD, st, p, ntiles,
                        (const bf16raw*)qkv, (bf16raw*)out, lse);
   }
   return check_launch("attn_fwd_small");
 }
-int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                          hipStream_t st) {
+int attn_fwd_small_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+  return p.mode == VTX_ATTN_TIME_CLS ? attn_fwd_small_launch_t<true>(p, qkv, out, lse, st) : attn_fwd_small_launch_t<false>(p, qkv, out, lse, st);
+}
+template <bool CLS>
+static int attn_bwd_small_launch_t(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                                   void* dqkv_cls, hipStream_t st) {
   const int G = 32 / p.L;
   const int ntiles = (p.S + G - 1) / G;
   if (options().attn_hw_bwd > 0) {
     const int w = hw_waves(options().attn_hw_bwd, p.H);
     const size_t lds = (size_t)w * SM_WAVE_LDS_BWD;
-    allow_lds<attn_bwd_small_kernel<true>>(lds);
-    hipLaunchKernelGGL(attn_bwd_small_kernel<true>, dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), lds, st, p, ntiles,
-                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv);
+    allow_lds<attn_bwd_small_kernel<true, CLS>>(lds);
+    hipLaunchKernelGGL((attn_bwd_small_kernel<true, CLS>), dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), lds, st, p, ntiles,
+                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
   } else {
-    hipLaunchKernelGGL(attn_bwd_small_kernel<false>, dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_BWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv);
+    hipLaunchKernelGGL((attn_bwd_small_kernel<false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_BWD, st, p, ntiles,
+                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
   }
   return check_launch("attn_bwd_small");
+}
+int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                          void* dqkv_cls, hipStream_t st) {
+  return p.mode == VTX_ATTN_TIME_CLS ? attn_bwd_small_launch_t<true>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st)
+                                     : attn_bwd_small_launch_t<false>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
 }
 
 int attn_fwd_mfma_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
   const int nt = (p.L + 31) >> 5, Lp = nt * 32;
   // (mg_div splits item -> (sequence, head) -> (clip, frame) with reciprocal multiplies that are exact below 2^24 items)
-  if (nt == 7 && options().attn_fwd_stream && (long)p.S * p.H < (1L << 24)) {      // one persistent workgroup per CU, K / V of the next item streamed in by LDS-DMA
+  if (nt == 7 && options().attn_fwd_stream && mg_mode(p.mode) && (long)p.S * p.H < (1L << 24)) {      // one persistent workgroup per CU, K / V of the next item streamed in by LDS-DMA
     allow_lds<attn_fwd_stream_mfma_kernel<7>>(MGF_LDS_BYTES);
     hipLaunchKernelGGL(attn_fwd_stream_mfma_kernel<7>, dim3(persistent_grid(p.S * p.H)), dim3(MF_THREADS), MGF_LDS_BYTES, st, p,
                        (const bf16raw*)qkv, (bf16raw*)out, lse);
@@ -1626,7 +1671,7 @@ static int attn_bwd_stream_launch(const AttnP& p, const void* qkv, const void* o
 int attn_bwd_mfma_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                          float* delta, void* dqkv, void* dqkv_cls, hipStream_t st) {
   const int nt = (p.L + 31) >> 5;
-  if (options().attn_fused >= 2 && nt == 7 && (long)p.S * p.H < (1L << 24)) return attn_bwd_stream_launch(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+  if (options().attn_fused >= 2 && nt == 7 && mg_mode(p.mode) && (long)p.S * p.H < (1L << 24)) return attn_bwd_stream_launch(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
   if (options().attn_fused && nt <= 7) {           // one pass over HBM: all four operand tiles fit the LDS of one workgroup
     if (nt == 7) return attn_bwd_fused_launch_t<7>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
     return attn_bwd_fused_launch_t<0>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);

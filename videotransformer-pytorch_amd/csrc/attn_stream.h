@@ -236,7 +236,7 @@ __device__ __forceinline__ void stream_bwd_dq(const AttnP& p, const typename E::
   E::store_rows(stg, acc, p.scale, lane, [&](int r) -> T* {
     const int qq = w.row0 + r;
     if (qq >= p.L) return nullptr;
-    return (p.mode == VTX_ATTN_SPACE && qq == 0) ? dqkv_cls + (long)w.s * p.ld_dqkv + h * 64
+    return attn_cls_row(p, qq) ? dqkv_cls + (long)w.s * p.ld_dqkv + h * 64
                                                   : dqkv + lin_row(w.li, qq) * p.ld_dqkv + h * 64;
   });
 }
@@ -307,7 +307,7 @@ __device__ __forceinline__ void stream_bwd_dkv(const AttnP& p, const typename E:
   auto base_of = [&](int r) -> T* {
     const int kk = w.row0 + r;
     if (kk >= p.L) return nullptr;
-    return (p.mode == VTX_ATTN_SPACE && kk == 0) ? dqkv_cls + (long)w.s * p.ld_dqkv : dqkv + lin_row(w.li, kk) * p.ld_dqkv;
+    return attn_cls_row(p, kk) ? dqkv_cls + (long)w.s * p.ld_dqkv : dqkv + lin_row(w.li, kk) * p.ld_dqkv;
   };
   E::store_rows(stg, dk, p.scale, lane, [&](int r) -> T* { T* b = base_of(r); return b ? b + D + h * 64 : nullptr; });
   E::store_rows(stg, dv, 1.0f, lane, [&](int r) -> T* { T* b = base_of(r); return b ? b + 2 * D + h * 64 : nullptr; });

@@ -198,7 +198,10 @@ __global__ __launch_bounds__(256) void fact_glue_de_kernel(int B, int T_, int D,
 }
 
 // ---- da rows for the spatial projection backward ----------------------------------
-template <typename T>
+// T_ sequences per clip with P tokens each.  SEQ_MAJOR false: sequence (b, t) holds tokens n = p T_ + t (spatial attention with
+// the cls token); true: sequence (b, j) holds the consecutive tokens n = j P + i (temporal attention over the cls token, T_ =
+// patches, P = frames).  Either way the clip's cls row goes to the T_ rows behind the tokens, scaled per sequence and by 1 / T_.
+template <typename T, bool SEQ_MAJOR>
 __global__ void space_grad_prep_kernel(int B, int T_, int P, int D, const T* __restrict__ dout, long ld,
                                        const float* __restrict__ s, T* __restrict__ da, long ldda) {
   const long per = D / 8;
@@ -212,7 +215,7 @@ __global__ void space_grad_prep_kernel(int B, int T_, int P, int D, const T* __r
     if (row < (long)B * N) {
       const long b = row / N, n = row - b * N;
       load8(dout + (b * (N + 1) + 1 + n) * ld + c, v);
-      sc = s ? s[b * T_ + (n % T_)] : 1.0f;
+      sc = s ? s[b * T_ + (SEQ_MAJOR ? n / P : n % T_)] : 1.0f;
     } else {
       const long bt = row - (long)B * N;
       const long b = bt / T_;
@@ -614,14 +617,23 @@ extern "C" int vtx_fact_glue_bwd(int dtype, int B, int T, int P, int D, const vo
 
 extern "C" int vtx_space_grad_prep(int dtype, int B, int T, int P, int D, const void* dout, long ld, const float* s,
                                    void* da, long ldda, void* stream) {
+  const bool seq_major = P < 0;                     // P < 0: -P consecutive tokens per sequence (include/vtx.h)
+  if (seq_major) P = -P;
   VTX_REQUIRE(B > 0 && T > 0 && P > 0 && D % 8 == 0 && dout && da, VTX_EINVAL, "space_grad_prep: bad arguments");
   const long work = ((long)B * P * T + (long)B * T) * (D / 8);
   dim3 grid(grid_for(work, 256)), block(256);
   hipStream_t st = as_stream(stream);
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(space_grad_prep_kernel<float>, grid, block, 0, st, B, T, P, D, (const float*)dout, ld, s, (float*)da, ldda),
-             hipLaunchKernelGGL(space_grad_prep_kernel<bf16raw>, grid, block, 0, st, B, T, P, D, (const bf16raw*)dout, ld, s, (bf16raw*)da, ldda),
-             "space_grad_prep");
+  if (seq_major) {
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((space_grad_prep_kernel<float, true>), grid, block, 0, st, B, T, P, D, (const float*)dout, ld, s, (float*)da, ldda),
+               hipLaunchKernelGGL((space_grad_prep_kernel<bf16raw, true>), grid, block, 0, st, B, T, P, D, (const bf16raw*)dout, ld, s, (bf16raw*)da, ldda),
+               "space_grad_prep");
+  } else {
+    DISPATCH_T(dtype,
+               hipLaunchKernelGGL((space_grad_prep_kernel<float, false>), grid, block, 0, st, B, T, P, D, (const float*)dout, ld, s, (float*)da, ldda),
+               hipLaunchKernelGGL((space_grad_prep_kernel<bf16raw, false>), grid, block, 0, st, B, T, P, D, (const bf16raw*)dout, ld, s, (bf16raw*)da, ldda),
+               "space_grad_prep");
+  }
   return check_launch("space_grad_prep");
 }
 

@@ -9,9 +9,10 @@ tensors raise (the CPU reference lives in oracle/, used by the tests only).
 
 Not carried over (raise ``NotImplementedError`` when exercised): non-zero
 dropout probabilities (the reference models always pass 0), norm / activation
-classes other than nn.LayerNorm / nn.GELU, FFN num_layers != 2, and the
-``use_cls_token`` variants that the shipped operator_order never instantiates
-(temporal op with cls / spatial op without cls).
+classes other than nn.LayerNorm / nn.GELU and FFN num_layers != 2.  Both
+operator orders of divided attention run: time-then-space (the models' own) and
+space-then-time, where the temporal op attends over the cls token and the
+spatial op does not (``use_cls_token``, reference transformer.py:602,611).
 """
 import numpy as np
 
@@ -260,9 +261,6 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
 
     def forward(self, query, key=None, value=None, residual=None, return_attention=False, **kwargs):
         assert residual is None, 'Always adding the shortcut in the forward function'
-        if self.use_cls_token:
-            raise NotImplementedError('vtx: temporal attention over the cls token (use_cls_token=True) is a '
-                                      'dead branch of the reference models and is not implemented')
         self._guard()
         x = _to_compute(query)
         xs, exact = _stream_of(query)
@@ -271,6 +269,12 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
         if (n1 - 1) % t:
             raise ValueError(f'{n1 - 1} tokens per clip are not a multiple of num_frames={t}')
         p = (n1 - 1) // t
+        if self.use_cls_token:                       # space-then-time order: sequences (b, p) of the cls row + T tokens
+            s = None if return_attention else _drop_scale(self.layer_drop, b * p, 3, x.device)
+            res = F_.TimeClsAttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                                         self.attn.proj.weight, self.attn.proj.bias, t, self.num_heads, s,
+                                         bool(return_attention), self.norm.eps, xs, exact)
+            return res if return_attention else _with_stream(res, exact)
         if return_attention:
             _no_exact('the attention map of a temporal block')
             tok = x[:, 1:].reshape(b * p, t, d)
@@ -299,9 +303,6 @@ class DividedSpatialAttentionWithPreNorm(_DividedBase):
 
     def forward(self, query, key=None, value=None, residual=None, return_attention=False, **kwargs):
         assert residual is None, 'Always adding the shortcut in the forward function'
-        if not self.use_cls_token:
-            raise NotImplementedError('vtx: spatial attention without the cls token (use_cls_token=False) is a '
-                                      'dead branch of the reference models and is not implemented')
         self._guard()
         x = _to_compute(query)
         xs, exact = _stream_of(query)
@@ -310,9 +311,10 @@ class DividedSpatialAttentionWithPreNorm(_DividedBase):
         if (x.shape[1] - 1) % t:
             raise ValueError(f'{x.shape[1] - 1} tokens per clip are not a multiple of num_frames={t}')
         s = None if return_attention else _drop_scale(self.layer_drop, b * t, 3, x.device)
-        res = F_.SpaceAttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
-                                   self.attn.proj.weight, self.attn.proj.bias, t, self.num_heads, s,
-                                   bool(return_attention), self.norm.eps, xs, exact)
+        fn = F_.SpaceAttnFn if self.use_cls_token else F_.SpaceNoClsAttnFn
+        res = fn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                       self.attn.proj.weight, self.attn.proj.bias, t, self.num_heads, s,
+                       bool(return_attention), self.norm.eps, xs, exact)
         return res if return_attention else _with_stream(res, exact)
 
 

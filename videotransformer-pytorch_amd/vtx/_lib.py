@@ -13,7 +13,7 @@ _PKG = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('VTX_LIB', os.path.join(_PKG, 'libvtx.so'))
 
 VTX_F32, VTX_BF16, VTX_BF16_X32 = 0, 1, 3
-ATTN_CONTIG, ATTN_SPACE = 0, 1
+ATTN_CONTIG, ATTN_SPACE, ATTN_TIME_CLS, ATTN_SPACE_NOCLS = 0, 1, 2, 3
 
 
 class RowMap(C.Structure):

@@ -12,7 +12,7 @@ import weakref
 import torch
 
 from . import ops
-from ._lib import IDENT, ATTN_CONTIG, ATTN_SPACE
+from ._lib import IDENT, ATTN_CONTIG, ATTN_SPACE, ATTN_TIME_CLS, ATTN_SPACE_NOCLS
 
 _wcache = {}
 
@@ -346,19 +346,20 @@ def _prenorm_bwd(dout, dxn, x_stream, xmap, ln_w, mean, rstd, params, skip=None)
     return dx, d_ln_w, d_ln_b
 
 
-def _qkv_fwd(xn, qkv_w, qkv_b, rows, D, need_t):
-    """The qkv projection of the three attention Functions -> (qkv [rows, 3D], W_qkv^T for the backward or None)."""
+def _qkv_fwd(xn, qkv_w, qkv_b, rows, D, need_t, qmap=IDENT, qrows=None):
+    """The qkv projection of the attention Functions -> (qkv [rows, 3D], W_qkv^T for the backward or None).  ``qmap`` /
+    ``qrows``: row m of xn goes to row qmap(m) of a [qrows, 3D] buffer whose other rows stay unwritten."""
     wq, wqT = weights(qkv_w, xn.dtype, need_t)
-    qkv = _empty((rows, 3 * D), xn)
-    ops.gemm_nt(xn, wq, qkv, rows, 3 * D, D, bias=qkv_b)
+    qkv = _empty((rows if qrows is None else qrows, 3 * D), xn)
+    ops.gemm_nt(xn, wq, qkv, rows, 3 * D, D, bias=qkv_b, cmap=qmap)
     return qkv, wqT
 
 
-def _qkv_bwd(params, dqkv, xn, wqT, rows, D):
+def _qkv_bwd(params, dqkv, xn, wqT, rows, D, qmap=IDENT):
     """Backward of _qkv_fwd -> (d_qkv_w, d_qkv_b, dxn); ``params``: as in _weight_grads."""
-    d_qkv_w, d_qkv_b = _weight_grads(params, dqkv, xn, rows, 3 * D, D)
+    d_qkv_w, d_qkv_b = _weight_grads(params, dqkv, xn, rows, 3 * D, D, amap=qmap)
     dxn = _empty((rows, D), dqkv)
-    ops.gemm_nt(dqkv, wqT, dxn, rows, D, 3 * D)
+    ops.gemm_nt(dqkv, wqT, dxn, rows, D, 3 * D, amap=qmap)
     return d_qkv_w, d_qkv_b, dxn
 
 
@@ -548,6 +549,142 @@ class SpaceAttnFn(torch.autograd.Function):
         ops.cls_qkv_reduce(dqkv_cls, dqkv, B, T, 3 * D, N1)
         d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M1, D)
         dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
+        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
+
+
+class TimeClsAttnFn(torch.autograd.Function):
+    """DividedTemporalAttentionWithPreNorm.forward, use_cls_token=True: the temporal half of the space-then-time operator
+    order (reference transformer.py:238-282).  The mirror image of SpaceAttnFn: LayerNorm and the qkv / proj Linears run once
+    over the natural token order, the attention kernel gathers the clip's cls row in front of the T rows of every sequence
+    (b, p) (VTX_ATTN_TIME_CLS), the P cls rows of a clip leave the proj GEMM through its split rows and are averaged over p.
+    There is no temporal_fc in this variant.  scale_vec: one DropPath scale per sequence (b, p), which also scales that
+    sequence's cls row before the mean."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, T, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
+        x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
+        B, N1, D = x.shape
+        N = N1 - 1
+        P = N // T
+        M1 = B * N1
+        hd = D // heads
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M1, IDENT)
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M1, D, need_t)
+        Mo = B * N + B * P
+        o = _empty((Mo, D), x)
+        S, L = B * P, T + 1
+        lse = _empty((S * heads * L,), x, torch.float32)
+        probs = _empty((S, heads, L, L), x, torch.float32) if want_probs else None
+        ops.attn_fwd(qkv, o, lse, ATTN_TIME_CLS, S, L, heads, hd, hd ** -0.5, B, T, P, probs=probs)
+        if want_probs:
+            ctx.mark_non_differentiable(probs)
+            return probs
+        wp, wpT = weights(proj_w, x.dtype, need_t)
+        out = torch.empty_like(x)
+        a_cls = _empty((B * P, D), x)
+        tm = ops.tokmap(N)
+        ops.gemm_nt(o, wp, out, Mo, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(T, 1, 1, 0),
+                    R=res, rmap=tm, split_row=B * N, Csplit=a_cls)
+        ops.cls_mean_fwd(a_cls, res, out, B, P, D, N1)               # the mean over p, in the order of p
+        ctx.cfg = (T, heads, scale_vec is not None)
+        ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
+
+    @staticmethod
+    def backward(ctx, dout, _dstream=None):
+        x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
+        p_ln_w, p_ln_b, p_qkv_w, p_qkv_b, p_proj_w, p_proj_b = ctx.params
+        T, heads, has_scale = ctx.cfg
+        sv = sv if has_scale else None
+        dout = _chk(dout)
+        B, N1, D = x.shape
+        N = N1 - 1
+        P = N // T
+        M1 = B * N1
+        Mo = B * N + B * P
+        hd = D // heads
+        x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
+        da = _empty((Mo, D), x)
+        ops.time_cls_grad_prep(dout, sv, da, B, T, P, D)      # token rows scaled per sequence (b, p), cls rows by s / P
+        d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, Mo, D, D)
+        do = _empty((Mo, D), x)
+        ops.gemm_nt(da, wpT, do, Mo, D, D)
+        dqkv = _empty((M1, 3 * D), x)
+        dqkv_cls = _empty((B * P, 3 * D), x)
+        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_TIME_CLS, B * P, T + 1, heads, hd, hd ** -0.5, B, T, P, dqkv_cls=dqkv_cls)
+        ops.cls_qkv_reduce(dqkv_cls, dqkv, B, P, 3 * D, N1)
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M1, D)
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
+        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
+
+
+class SpaceNoClsAttnFn(torch.autograd.Function):
+    """DividedSpatialAttentionWithPreNorm.forward, use_cls_token=False: the spatial half of the space-then-time operator
+    order (reference transformer.py:340-382).  LayerNorm and the Linears run over the B*N token rows in their natural order;
+    the attention kernel regroups them into the sequences (b, t) of P tokens (VTX_ATTN_SPACE_NOCLS).  The cls rows pass
+    through untouched, forward and backward, as in TimeAttnFn.  scale_vec: one DropPath scale per sequence (b, t)."""
+
+    @staticmethod
+    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, T, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
+        x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
+        B, N1, D = x.shape
+        N = N1 - 1
+        P = N // T
+        M = B * N
+        hd = D // heads
+        tm = ops.tokmap(N)
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, tm)
+        if exact:
+            ops.layernorm_acc_fwd(xs, x, B, D, D, ops.clsmap(N), x32, D, ops.clsmap(N))       # the cls rows: accumulate only
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t, qmap=tm, qrows=B * N1)              # natural order; cls rows unwritten, unread
+        o = _empty((M, D), x)
+        S, L = B * T, P
+        lse = _empty((S * heads * L,), x, torch.float32)
+        probs = _empty((S, heads, L, L), x, torch.float32) if want_probs else None
+        ops.attn_fwd(qkv, o, lse, ATTN_SPACE_NOCLS, S, L, heads, hd, hd ** -0.5, B, T, P, probs=probs)
+        if want_probs:
+            ctx.mark_non_differentiable(probs)
+            return probs
+        wp, wpT = weights(proj_w, x.dtype, need_t)
+        out = torch.empty_like(x)
+        ops.gemm_nt(o, wp, out, M, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(N, T, T, 1), R=res, rmap=tm)
+        if exact:
+            _zero_rows(x, out, B, D, ops.clsmap(N))                 # the block contributes nothing to the cls rows
+        else:
+            ops.row_scale_copy(x, out, B, D, smap=ops.clsmap(N), dmap=ops.clsmap(N))
+        ctx.cfg = (T, heads, scale_vec is not None)
+        ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
+
+    @staticmethod
+    def backward(ctx, dout, _dstream=None):
+        x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
+        p_ln_w, p_ln_b, p_qkv_w, p_qkv_b, p_proj_w, p_proj_b = ctx.params
+        T, heads, has_scale = ctx.cfg
+        dout = _chk(dout)
+        B, N1, D = x.shape
+        N = N1 - 1
+        P = N // T
+        M = B * N
+        hd = D // heads
+        tm = ops.tokmap(N)
+        x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
+        do = _empty((M, D), x)
+        if has_scale:
+            da = _empty((M, D), x)
+            ops.row_scale_copy(dout, da, M, D, smap=tm, s=sv, rs=(N, T, T, 1))
+            d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, M, D, D)
+            ops.gemm_nt(da, wpT, do, M, D, D)
+        else:
+            d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), dout, o, M, D, D, amap=tm)
+            ops.gemm_nt(dout, wpT, do, M, D, D, amap=tm)
+        dqkv = _empty((B * N1, 3 * D), x)              # natural order; the kernel writes its cls rows as zeros
+        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE_NOCLS, B * T, P, heads, hd, hd ** -0.5, B, T, P)
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M, D, qmap=tm)
+        # LayerNorm + residual; the cls rows pass through
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=(B, ops.clsmap(N)))
         return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
 
 

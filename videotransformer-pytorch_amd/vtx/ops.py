@@ -323,10 +323,17 @@ def _attn_desc(qkv, out, lse, mode, S, L, H, hd, scale, B=0, T=0, P=0, probs=Non
     return d
 
 
+def _attn_kind(mode, L):
+    """Timing class of a launch: the two spatial layouts, else by length."""
+    if mode in (_lib.ATTN_SPACE, _lib.ATTN_SPACE_NOCLS):
+        return 'space'
+    return 'time' if L <= 32 else 'seq' if L <= 256 else 'long'
+
+
 def attn_fwd(qkv, out, lse, mode, S, L, H, hd, scale, B=0, T=0, P=0, probs=None):
     need_cuda(qkv, out, lse)
     d = _attn_desc(qkv, out, lse, mode, S, L, H, hd, scale, B, T, P, probs)
-    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq' if L <= 256 else 'long')
+    kind = _attn_kind(mode, L)
     rows = S * L                       # algorithmic bytes: read q,k,v, write o (+ fp32 log-sum-exp)
     with _timed(f'attn_fwd_{kind}', 4.0 * S * H * L * L * hd, rows * H * hd * 4 * qkv.element_size() + rows * H * 4,
                 f'{S}x{L}x{H}'):
@@ -342,7 +349,7 @@ def attn_bwd(qkv, out, lse, dout, dqkv, mode, S, L, H, hd, scale, B=0, T=0, P=0,
     b.dqkv_cls = ptr(dqkv_cls)
     delta = torch.empty(S * H * L, dtype=torch.float32, device=qkv.device)
     b.delta = ptr(delta)
-    kind = 'space' if mode == _lib.ATTN_SPACE else ('time' if L <= 32 else 'seq' if L <= 256 else 'long')
+    kind = _attn_kind(mode, L)
     rows = S * L                       # read q,k,v,o,do, write dq,dk,dv
     with _timed(f'attn_bwd_{kind}', 10.0 * S * H * L * L * hd, rows * H * hd * 8 * qkv.element_size() + rows * H * 4,
                 f'{S}x{L}x{H}'):
@@ -371,6 +378,13 @@ def cls_mean_fwd(a_cls, x, out, B, T, D, rows_per_clip):
 
 def space_grad_prep(dout, s, da, B, T, P, D):
     call('vtx_space_grad_prep', dt(dout), B, T, P, D, ptr(dout), D, ptr(s), ptr(da), D, stream())
+
+
+def time_cls_grad_prep(dout, s, da, B, T, P, D):
+    """Backward prep of temporal attention over the cls token: da[0:B*N] = dout[b, 1+n] * s[b*P + n/T], da[B*N + b*P + p] =
+    dout[b, 0] * s[b*P + p] / P (s may be None).  vtx_space_grad_prep in its sequence-major form: P sequences per clip in the
+    entry point's T slot, minus the T consecutive tokens of a sequence in its P slot (include/vtx.h)."""
+    call('vtx_space_grad_prep', dt(dout), B, P, -T, D, ptr(dout), D, ptr(s), ptr(da), D, stream())
 
 
 def cls_qkv_reduce(dqkv_cls, dqkv, B, T, W, rows_per_clip):
