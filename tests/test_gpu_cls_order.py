@@ -1,6 +1,6 @@
 """Divided attention in space-then-time order: operator_order = ['space_attn', 'time_attn', 'ffn'], where the spatial block
-runs without the cls token (VTX_ATTN_SPACE_NOCLS, vtx.functions.SpaceNoClsAttnFn) and the temporal block over it
-(VTX_ATTN_TIME_CLS, vtx.functions.TimeClsAttnFn).  Reference transformer.py:238-282, :340-382, :602,611.
+runs without the cls token (VTX_ATTN_SPACE_NOCLS, vtx.functions.AttnFn kind 'space_nocls') and the temporal block over it
+(VTX_ATTN_TIME_CLS, kind 'time_cls').  Reference transformer.py:238-282, :340-382, :602,611.
 
   1. model-level parity against the goldens of the running reference (tests/golden/make_golden_cls_order.py): fp32 within
      TOL_F32; bf16 within TOL_BF16 / TOL_BF16_GRAD, widened per tensor to AUTOCAST_FACTOR x the reference's own autocast

@@ -271,17 +271,15 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
         p = (n1 - 1) // t
         if self.use_cls_token:                       # space-then-time order: sequences (b, p) of the cls row + T tokens
             s = None if return_attention else _drop_scale(self.layer_drop, b * p, 3, x.device)
-            res = F_.TimeClsAttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
-                                         self.attn.proj.weight, self.attn.proj.bias, t, self.num_heads, s,
-                                         bool(return_attention), self.norm.eps, xs, exact)
+            res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                                  self.attn.proj.weight, self.attn.proj.bias, 'time_cls', t, self.num_heads, s,
+                                  bool(return_attention), self.norm.eps, xs, exact)
             return res if return_attention else _with_stream(res, exact)
         if return_attention:
             _no_exact('the attention map of a temporal block')
             tok = x[:, 1:].reshape(b * p, t, d)
-            out = F_.SelfAttnFn.apply(tok, self.norm.weight, self.norm.bias, self.attn.qkv.weight,
-                                      self.attn.qkv.bias, self.attn.proj.weight, self.attn.proj.bias,
-                                      self.num_heads, None, True, self.norm.eps)
-            return out
+            return F_.AttnFn.apply(tok, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                                   self.attn.proj.weight, self.attn.proj.bias, 'self', 0, self.num_heads, None, True, self.norm.eps)
         s = _drop_scale(self.layer_drop, b * p, 3, x.device)
         return _with_stream(F_.TimeAttnFn.apply(
             x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias, self.attn.proj.weight,
@@ -311,10 +309,9 @@ class DividedSpatialAttentionWithPreNorm(_DividedBase):
         if (x.shape[1] - 1) % t:
             raise ValueError(f'{x.shape[1] - 1} tokens per clip are not a multiple of num_frames={t}')
         s = None if return_attention else _drop_scale(self.layer_drop, b * t, 3, x.device)
-        fn = F_.SpaceAttnFn if self.use_cls_token else F_.SpaceNoClsAttnFn
-        res = fn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
-                       self.attn.proj.weight, self.attn.proj.bias, t, self.num_heads, s,
-                       bool(return_attention), self.norm.eps, xs, exact)
+        res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                              self.attn.proj.weight, self.attn.proj.bias, 'space' if self.use_cls_token else 'space_nocls', t,
+                              self.num_heads, s, bool(return_attention), self.norm.eps, xs, exact)
         return res if return_attention else _with_stream(res, exact)
 
 
@@ -339,9 +336,9 @@ class MultiheadAttentionWithPreNorm(nn.Module):
         x = _to_compute(query)
         xs, exact = _stream_of(query)
         s = None if return_attention else _drop_scale(self.layer_drop, x.shape[0], 3, x.device)
-        res = F_.SelfAttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
-                                  self.attn.proj.weight, self.attn.proj.bias, self.num_heads, s,
-                                  bool(return_attention), self.norm.eps, xs, exact)
+        res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
+                              self.attn.proj.weight, self.attn.proj.bias, 'self', 0, self.num_heads, s,
+                              bool(return_attention), self.norm.eps, xs, exact)
         return res if return_attention else _with_stream(res, exact)
 
 

@@ -7,6 +7,8 @@ video_transformer.py:228,236).  Parameters stay float32; their compute-dtype
 copies (and the transposes used by the input-gradient GEMMs) are staged by
 ``weights()`` and cached per parameter version.
 """
+import collections
+import functools
 import weakref
 
 import torch
@@ -295,7 +297,7 @@ def _chk(x):
     return x
 
 
-# ---- the pre-norm skeleton shared by TimeAttnFn, SpaceAttnFn, SelfAttnFn and FFNFn -------------------------------
+# ---- the pre-norm skeleton shared by TimeAttnFn, AttnFn (all four kinds) and FFNFn -------------------------------
 # LayerNorm -> body -> residual in the GEMM epilogue; backward: body -> weight gradients -> LayerNorm backward + residual.
 # The bodies live in the Functions; what surrounds them is here, once.
 def _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, rows, xmap):
@@ -363,6 +365,29 @@ def _qkv_bwd(params, dqkv, xn, wqT, rows, D, qmap=IDENT):
     return d_qkv_w, d_qkv_b, dxn
 
 
+# The cls rows of an attention block without the cls token (TimeAttnFn, AttnFn 'space_nocls'): they pass through untouched,
+# forward and backward.
+def _cls_rows(shape):
+    """(rows, rowmap) of the cls rows of a [B, 1 + N, D] stream -- the ``skip`` of _prenorm_bwd."""
+    return shape[0], ops.clsmap(shape[1] - 1)
+
+
+def _cls_pass_acc(x, xs, x32):
+    """Exact stream, next to _prenorm_fwd: x32 = xs + x on the cls rows too (accumulate only, nothing is normalised)."""
+    rows, cm = _cls_rows(x.shape)
+    ops.layernorm_acc_fwd(xs, x, rows, x.shape[-1], x.shape[-1], cm, x32, x.shape[-1], cm)
+
+
+def _cls_pass_out(x, out, exact):
+    """The cls rows of the block's output: zeros under the exact stream (out is a contribution, and the block contributes
+    nothing to them), else the rows of x."""
+    rows, cm = _cls_rows(x.shape)
+    if exact:
+        _zero_rows(x, out, rows, x.shape[-1], cm)
+    else:
+        ops.row_scale_copy(x, out, rows, x.shape[-1], smap=cm, dmap=cm)
+
+
 # ---------------------------------------------------------------------------------
 class TimeAttnFn(torch.autograd.Function):
     """DividedTemporalAttentionWithPreNorm.forward, use_cls_token=False (reference transformer.py:234-282).
@@ -394,7 +419,7 @@ class TimeAttnFn(torch.autograd.Function):
         merged = _merge_tfc and (scale_vec is None or keep_scale is not None) and proj_b is not None and tfc_b is not None
         xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, tm)
         if exact:
-            ops.layernorm_acc_fwd(xs, x, B, D, D, ops.clsmap(N), x32, D, ops.clsmap(N))       # the cls rows: accumulate only
+            _cls_pass_acc(x, xs, x32)
         qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t)
         o = _empty((M, D), x)
         S = M // T
@@ -417,10 +442,7 @@ class TimeAttnFn(torch.autograd.Function):
             wt, wtT = weights(tfc_w, dtp, need_t)
             ops.gemm_nt(a, wt, out, M, D, D, cmap=tm, bias=tfc_b, R=res, rmap=tm)
             wts = (wqT, wpT, wtT)
-        if exact:
-            _zero_rows(x, out, B, D, ops.clsmap(N))                 # the block contributes nothing to the cls rows
-        else:
-            ops.row_scale_copy(x, out, B, D, smap=ops.clsmap(N), dmap=ops.clsmap(N))
+        _cls_pass_out(x, out, exact)
         ctx.cfg = (T, heads, scale_vec is not None, merged, keep_scale)
         ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, tfc_w, tfc_b)
         return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse, a), scale_vec, wts)
@@ -481,263 +503,138 @@ class TimeAttnFn(torch.autograd.Function):
         ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, S, T, heads, hd, hd ** -0.5)
         d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M, D)
         # LayerNorm + residual; the cls rows pass through
-        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=(B, ops.clsmap(N)))
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=_cls_rows(dout.shape))
         return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, d_tfc_w, d_tfc_b, None, None, None, None, None, None, None)
 
 
 # ---------------------------------------------------------------------------------
-class SpaceAttnFn(torch.autograd.Function):
-    """DividedSpatialAttentionWithPreNorm.forward, use_cls_token=True
-    (reference transformer.py:336-382).  LayerNorm and the qkv / proj Linears are
-    row-wise, so they run once over the natural token order (the cls row once per
-    clip instead of once per frame); only the attention kernel regroups rows."""
+# ---- the four proj-only attention sub-blocks: one body (AttnFn), the variants as rows of _attn_layout -------------
+# x + DropPath(proj(attn(LN(x)))).  LayerNorm and the qkv / proj Linears are row-wise, so they run once over the natural token
+# order (a cls row once per clip, not once per sequence); only the attention kernel regroups rows, by the layout `mode`
+# (csrc/attn_common.h), and `cls` says what happens to the cls rows around it.
+CLS_NONE, CLS_MEAN, CLS_PASS = 0, 1, 2
+AttnLayout = collections.namedtuple('AttnLayout', (
+    'mode', 'S', 'L', 'B', 'T', 'P',     # vtx_attn_fwd / _bwd: layout, sequences, tokens per sequence, clip shape (0 0 0: CONTIG)
+    'rows', 'xmap',                      # rows the LayerNorm normalises, row m of them at xmap(m) of the stream
+    'qrows', 'qmap',                     # rows of the qkv buffer, row m of xn at qmap(m) of it
+    'Mo', 'tok', 'ncls', 'groups',       # rows of o: tok token rows, then ncls split cls rows = `groups` per clip
+    'rs', 'omap',                        # DropPath row scale of the proj GEMM; row map of its output and its residual
+    'cls', 'direct'))                    # cls policy; parameter gradients may go straight into .grad
+
+
+@functools.lru_cache(maxsize=64)
+def _attn_layout(kind, shape, T):
+    """Everything AttnFn derives from the variant ``kind`` and the stream's shape [B, 1 + P*T, D] ('self': [Bn, L, D], T
+    unused).  Pure host arithmetic over ints and row maps (tests/test_attn_layout_host.py checks every row against the
+    kernels' own shape rules); cached, so a training step pays for it once."""
+    Bc, N1, _ = shape
+    if kind == 'self':
+        # MultiheadAttentionWithPreNorm.forward (reference transformer.py:428-456): x [Bn, L, D], every row a token of one of
+        # the Bn contiguous sequences; scale_vec: one DropPath scale per sequence.  direct False: this kind hands every gradient
+        # to autograd even with direct gradients on, and its LayerNorm sums start from fresh zeros -- the status quo, not a decision
+        M = Bc * N1
+        return AttnLayout(ATTN_CONTIG, Bc, N1, 0, 0, 0, rows=M, xmap=IDENT, qrows=M, qmap=IDENT, Mo=M, tok=M, ncls=0,
+                          groups=0, rs=(N1, 1, 1, 0), omap=IDENT, cls=CLS_NONE, direct=False)
+    N = N1 - 1
+    P = N // T
+    M, M1, tm = Bc * N, Bc * N1, ops.tokmap(N)
+    if kind == 'space':
+        # DividedSpatialAttentionWithPreNorm.forward, use_cls_token=True (reference transformer.py:336-382): the kernel gathers
+        # the clip's cls row in front of the P rows of every sequence (b, t) (VTX_ATTN_SPACE), the T cls rows of a clip leave the
+        # proj GEMM through its split rows and are averaged over t.  scale_vec: one DropPath scale per sequence (b, t), which
+        # also scales that sequence's cls row before the mean.
+        return AttnLayout(ATTN_SPACE, Bc * T, P + 1, Bc, T, P, rows=M1, xmap=IDENT, qrows=M1, qmap=IDENT, Mo=M + Bc * T, tok=M,
+                          ncls=Bc * T, groups=T, rs=(N, T, T, 1), omap=tm, cls=CLS_MEAN, direct=True)
+    if kind == 'time_cls':
+        # DividedTemporalAttentionWithPreNorm.forward, use_cls_token=True: the temporal half of the space-then-time operator
+        # order (reference transformer.py:238-282).  The mirror image of 'space': sequences (b, p) of the cls row + T tokens
+        # (VTX_ATTN_TIME_CLS), the P cls rows of a clip are averaged over p, in the order of p.  There is no temporal_fc in this
+        # variant.  scale_vec: one DropPath scale per sequence (b, p).
+        return AttnLayout(ATTN_TIME_CLS, Bc * P, T + 1, Bc, T, P, rows=M1, xmap=IDENT, qrows=M1, qmap=IDENT, Mo=M + Bc * P, tok=M,
+                          ncls=Bc * P, groups=P, rs=(T, 1, 1, 0), omap=tm, cls=CLS_MEAN, direct=True)
+    if kind == 'space_nocls':
+        # DividedSpatialAttentionWithPreNorm.forward, use_cls_token=False: the spatial half of the space-then-time operator
+        # order (reference transformer.py:340-382).  LayerNorm and the Linears run over the B*N token rows; qkv keeps the natural
+        # order (its cls rows unwritten, unread; dqkv's come back as zeros) and the kernel regroups the tokens into the sequences
+        # (b, t) of P (VTX_ATTN_SPACE_NOCLS).  The cls rows pass through (_cls_pass_*).  scale_vec: one scale per sequence (b, t).
+        return AttnLayout(ATTN_SPACE_NOCLS, Bc * T, P, Bc, T, P, rows=M, xmap=tm, qrows=M1, qmap=tm, Mo=M, tok=M, ncls=0,
+                          groups=0, rs=(N, T, T, 1), omap=tm, cls=CLS_PASS, direct=True)
+    raise ValueError(f'AttnFn: unknown kind {kind!r}')
+
+
+class AttnFn(torch.autograd.Function):
+    """The pre-norm attention sub-block of ``kind`` 'self' / 'space' / 'time_cls' / 'space_nocls' (see _attn_layout for what
+    each is in the reference).  want_probs: return the attention probabilities [S, heads, L, L] instead."""
 
     @staticmethod
-    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, T, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
+    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, kind, T, heads, scale_vec, want_probs, eps=1e-5, xs=None,
+                exact=False):
         x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M1 = B * N1
+        lay = _attn_layout(kind, x.shape, T)
+        D = x.shape[-1]
         hd = D // heads
+        Mo = lay.Mo
         need_t = any(ctx.needs_input_grad)
-        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M1, IDENT)
-        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M1, D, need_t)
-        Mo = B * N + B * T
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, lay.rows, lay.xmap)
+        if exact and lay.cls == CLS_PASS:
+            _cls_pass_acc(x, xs, x32)
+        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, lay.rows, D, need_t, qmap=lay.qmap, qrows=lay.qrows)
         o = _empty((Mo, D), x)
-        S, L = B * T, P + 1
-        lse = _empty((S * heads * L,), x, torch.float32)
-        probs = _empty((S, heads, L, L), x, torch.float32) if want_probs else None
-        ops.attn_fwd(qkv, o, lse, ATTN_SPACE, S, L, heads, hd, hd ** -0.5, B, T, P, probs=probs)
+        lse = _empty((lay.S * heads * lay.L,), x, torch.float32)
+        probs = _empty((lay.S, heads, lay.L, lay.L), x, torch.float32) if want_probs else None
+        ops.attn_fwd(qkv, o, lse, lay.mode, lay.S, lay.L, heads, hd, hd ** -0.5, lay.B, lay.T, lay.P, probs=probs)
         if want_probs:
             ctx.mark_non_differentiable(probs)
             return probs
         wp, wpT = weights(proj_w, x.dtype, need_t)
         out = torch.empty_like(x)
-        a_cls = _empty((B * T, D), x)
-        tm = ops.tokmap(N)
-        ops.gemm_nt(o, wp, out, Mo, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(N, T, T, 1),
-                    R=res, rmap=tm, split_row=B * N, Csplit=a_cls)
-        ops.cls_mean_fwd(a_cls, res, out, B, T, D, N1)
-        ctx.cfg = (T, heads, scale_vec is not None)
-        ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
+        a_cls = _empty((lay.ncls, D), x) if lay.ncls else None
+        ops.gemm_nt(o, wp, out, Mo, D, D, cmap=lay.omap, bias=proj_b, row_scale=scale_vec, rs=lay.rs, R=res, rmap=lay.omap,
+                    split_row=lay.tok if lay.ncls else 0, Csplit=a_cls)
+        if lay.cls == CLS_MEAN:
+            ops.cls_mean_fwd(a_cls, res, out, lay.B, lay.groups, D, x.shape[1])
+        elif lay.cls == CLS_PASS:
+            _cls_pass_out(x, out, exact)
+        ctx.cfg = (kind, T, heads, scale_vec is not None)
+        ctx.params = ((ln_w, ln_b), (qkv_w, qkv_b), (proj_w, proj_b)) if lay.direct else (None, None, None)
         return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
 
     @staticmethod
     def backward(ctx, dout, _dstream=None):
         x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
-        p_ln_w, p_ln_b, p_qkv_w, p_qkv_b, p_proj_w, p_proj_b = ctx.params
-        T, heads, has_scale = ctx.cfg
-        sv = sv if has_scale else None
+        p_ln, p_qkv, p_proj = ctx.params
+        kind, T, heads, has_scale = ctx.cfg
+        lay = _attn_layout(kind, x.shape, T)
         dout = _chk(dout)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M1 = B * N1
-        Mo = B * N + B * T
+        D = x.shape[-1]
         hd = D // heads
+        Mo = lay.Mo
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
-        da = _empty((Mo, D), x)
-        ops.space_grad_prep(dout, sv, da, B, T, P, D)
-        d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, Mo, D, D)
+        # da [Mo, D]: dout under the DropPath scale, in the row order of o.  With cls rows to split off it is always built
+        # (token rows scaled per sequence, cls rows by s / groups); else only when there is a scale -- without one the GEMMs
+        # read dout itself through the row map
+        amap = IDENT
+        if lay.cls == CLS_MEAN:
+            da = _empty((Mo, D), x)
+            prep = ops.time_cls_grad_prep if lay.mode == ATTN_TIME_CLS else ops.space_grad_prep
+            prep(dout, sv if has_scale else None, da, lay.B, lay.T, lay.P, D)
+        elif has_scale:
+            da = _empty((Mo, D), x)
+            ops.row_scale_copy(dout, da, Mo, D, smap=lay.omap, s=sv, rs=lay.rs)
+        else:
+            da, amap = dout, lay.omap
+        d_proj_w, d_proj_b = _weight_grads(p_proj, da, o, Mo, D, D, amap=amap)
         do = _empty((Mo, D), x)
-        ops.gemm_nt(da, wpT, do, Mo, D, D)
-        dqkv = _empty((M1, 3 * D), x)
-        dqkv_cls = _empty((B * T, 3 * D), x)
-        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE, B * T, P + 1, heads, hd, hd ** -0.5, B, T, P,
-                     dqkv_cls=dqkv_cls)
-        ops.cls_qkv_reduce(dqkv_cls, dqkv, B, T, 3 * D, N1)
-        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M1, D)
-        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
-
-
-class TimeClsAttnFn(torch.autograd.Function):
-    """DividedTemporalAttentionWithPreNorm.forward, use_cls_token=True: the temporal half of the space-then-time operator
-    order (reference transformer.py:238-282).  The mirror image of SpaceAttnFn: LayerNorm and the qkv / proj Linears run once
-    over the natural token order, the attention kernel gathers the clip's cls row in front of the T rows of every sequence
-    (b, p) (VTX_ATTN_TIME_CLS), the P cls rows of a clip leave the proj GEMM through its split rows and are averaged over p.
-    There is no temporal_fc in this variant.  scale_vec: one DropPath scale per sequence (b, p), which also scales that
-    sequence's cls row before the mean."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, T, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
-        x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M1 = B * N1
-        hd = D // heads
-        need_t = any(ctx.needs_input_grad)
-        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M1, IDENT)
-        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M1, D, need_t)
-        Mo = B * N + B * P
-        o = _empty((Mo, D), x)
-        S, L = B * P, T + 1
-        lse = _empty((S * heads * L,), x, torch.float32)
-        probs = _empty((S, heads, L, L), x, torch.float32) if want_probs else None
-        ops.attn_fwd(qkv, o, lse, ATTN_TIME_CLS, S, L, heads, hd, hd ** -0.5, B, T, P, probs=probs)
-        if want_probs:
-            ctx.mark_non_differentiable(probs)
-            return probs
-        wp, wpT = weights(proj_w, x.dtype, need_t)
-        out = torch.empty_like(x)
-        a_cls = _empty((B * P, D), x)
-        tm = ops.tokmap(N)
-        ops.gemm_nt(o, wp, out, Mo, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(T, 1, 1, 0),
-                    R=res, rmap=tm, split_row=B * N, Csplit=a_cls)
-        ops.cls_mean_fwd(a_cls, res, out, B, P, D, N1)               # the mean over p, in the order of p
-        ctx.cfg = (T, heads, scale_vec is not None)
-        ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
-        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
-
-    @staticmethod
-    def backward(ctx, dout, _dstream=None):
-        x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
-        p_ln_w, p_ln_b, p_qkv_w, p_qkv_b, p_proj_w, p_proj_b = ctx.params
-        T, heads, has_scale = ctx.cfg
-        sv = sv if has_scale else None
-        dout = _chk(dout)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M1 = B * N1
-        Mo = B * N + B * P
-        hd = D // heads
-        x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
-        da = _empty((Mo, D), x)
-        ops.time_cls_grad_prep(dout, sv, da, B, T, P, D)      # token rows scaled per sequence (b, p), cls rows by s / P
-        d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, Mo, D, D)
-        do = _empty((Mo, D), x)
-        ops.gemm_nt(da, wpT, do, Mo, D, D)
-        dqkv = _empty((M1, 3 * D), x)
-        dqkv_cls = _empty((B * P, 3 * D), x)
-        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_TIME_CLS, B * P, T + 1, heads, hd, hd ** -0.5, B, T, P, dqkv_cls=dqkv_cls)
-        ops.cls_qkv_reduce(dqkv_cls, dqkv, B, P, 3 * D, N1)
-        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M1, D)
-        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
-
-
-class SpaceNoClsAttnFn(torch.autograd.Function):
-    """DividedSpatialAttentionWithPreNorm.forward, use_cls_token=False: the spatial half of the space-then-time operator
-    order (reference transformer.py:340-382).  LayerNorm and the Linears run over the B*N token rows in their natural order;
-    the attention kernel regroups them into the sequences (b, t) of P tokens (VTX_ATTN_SPACE_NOCLS).  The cls rows pass
-    through untouched, forward and backward, as in TimeAttnFn.  scale_vec: one DropPath scale per sequence (b, t)."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, T, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
-        x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M = B * N
-        hd = D // heads
-        tm = ops.tokmap(N)
-        need_t = any(ctx.needs_input_grad)
-        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, tm)
-        if exact:
-            ops.layernorm_acc_fwd(xs, x, B, D, D, ops.clsmap(N), x32, D, ops.clsmap(N))       # the cls rows: accumulate only
-        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t, qmap=tm, qrows=B * N1)              # natural order; cls rows unwritten, unread
-        o = _empty((M, D), x)
-        S, L = B * T, P
-        lse = _empty((S * heads * L,), x, torch.float32)
-        probs = _empty((S, heads, L, L), x, torch.float32) if want_probs else None
-        ops.attn_fwd(qkv, o, lse, ATTN_SPACE_NOCLS, S, L, heads, hd, hd ** -0.5, B, T, P, probs=probs)
-        if want_probs:
-            ctx.mark_non_differentiable(probs)
-            return probs
-        wp, wpT = weights(proj_w, x.dtype, need_t)
-        out = torch.empty_like(x)
-        ops.gemm_nt(o, wp, out, M, D, D, cmap=tm, bias=proj_b, row_scale=scale_vec, rs=(N, T, T, 1), R=res, rmap=tm)
-        if exact:
-            _zero_rows(x, out, B, D, ops.clsmap(N))                 # the block contributes nothing to the cls rows
-        else:
-            ops.row_scale_copy(x, out, B, D, smap=ops.clsmap(N), dmap=ops.clsmap(N))
-        ctx.cfg = (T, heads, scale_vec is not None)
-        ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b)
-        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
-
-    @staticmethod
-    def backward(ctx, dout, _dstream=None):
-        x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
-        p_ln_w, p_ln_b, p_qkv_w, p_qkv_b, p_proj_w, p_proj_b = ctx.params
-        T, heads, has_scale = ctx.cfg
-        dout = _chk(dout)
-        B, N1, D = x.shape
-        N = N1 - 1
-        P = N // T
-        M = B * N
-        hd = D // heads
-        tm = ops.tokmap(N)
-        x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
-        do = _empty((M, D), x)
-        if has_scale:
-            da = _empty((M, D), x)
-            ops.row_scale_copy(dout, da, M, D, smap=tm, s=sv, rs=(N, T, T, 1))
-            d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, M, D, D)
-            ops.gemm_nt(da, wpT, do, M, D, D)
-        else:
-            d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), dout, o, M, D, D, amap=tm)
-            ops.gemm_nt(dout, wpT, do, M, D, D, amap=tm)
-        dqkv = _empty((B * N1, 3 * D), x)              # natural order; the kernel writes its cls rows as zeros
-        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_SPACE_NOCLS, B * T, P, heads, hd, hd ** -0.5, B, T, P)
-        d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M, D, qmap=tm)
-        # LayerNorm + residual; the cls rows pass through
-        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=(B, ops.clsmap(N)))
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None)
-
-
-class SelfAttnFn(torch.autograd.Function):
-    """MultiheadAttentionWithPreNorm.forward (reference transformer.py:428-456):
-    x [Bn, L, D] -> x + DropPath(proj(attn(LN(x))))."""
-
-    @staticmethod
-    def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, heads, scale_vec, want_probs, eps=1e-5, xs=None, exact=False):
-        x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
-        Bn, L, D = x.shape
-        M = Bn * L
-        hd = D // heads
-        need_t = any(ctx.needs_input_grad)
-        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, IDENT)
-        qkv, wqT = _qkv_fwd(xn, qkv_w, qkv_b, M, D, need_t)
-        o = _empty((M, D), x)
-        lse = _empty((Bn * heads * L,), x, torch.float32)
-        probs = _empty((Bn, heads, L, L), x, torch.float32) if want_probs else None
-        ops.attn_fwd(qkv, o, lse, ATTN_CONTIG, Bn, L, heads, hd, hd ** -0.5, probs=probs)
-        if want_probs:
-            ctx.mark_non_differentiable(probs)
-            return probs
-        wp, wpT = weights(proj_w, x.dtype, need_t)
-        out = torch.empty_like(x)
-        ops.gemm_nt(o, wp, out, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(L, 1, 1, 0), R=res)
-        ctx.cfg = (heads, scale_vec is not None)
-        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
-
-    @staticmethod
-    def backward(ctx, dout, _dstream=None):
-        x, ln_w, mean, rstd, xn, qkv, o, lse, sv, wqT, wpT = ctx.saved_tensors
-        heads, has_scale = ctx.cfg
-        dout = _chk(dout)
-        Bn, L, D = x.shape
-        M = Bn * L
-        hd = D // heads
-        x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
-        if has_scale:
-            da = _empty((M, D), x)
-            ops.row_scale_copy(dout, da, M, D, s=sv, rs=(L, 1, 1, 0))
-        else:
-            da = dout
-        # params None (three times): this Function hands every gradient to autograd even with direct gradients on, and its
-        # LayerNorm sums start from fresh zeros -- the status quo, not a decision
-        d_proj_w, d_proj_b = _weight_grads(None, da, o, M, D, D)
-        do = _empty((M, D), x)
-        ops.gemm_nt(da, wpT, do, M, D, D)
-        dqkv = _empty((M, 3 * D), x)
-        ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, Bn, L, heads, hd, hd ** -0.5)
-        d_qkv_w, d_qkv_b, dxn = _qkv_bwd(None, dqkv, xn, wqT, M, D)
-        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, None)
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None)
+        ops.gemm_nt(da, wpT, do, Mo, D, D, amap=amap)
+        dqkv = _empty((lay.qrows, 3 * D), x)
+        dqkv_cls = _empty((lay.ncls, 3 * D), x) if lay.ncls else None
+        ops.attn_bwd(qkv, o, lse, do, dqkv, lay.mode, lay.S, lay.L, heads, hd, hd ** -0.5, lay.B, lay.T, lay.P, dqkv_cls=dqkv_cls)
+        if lay.cls == CLS_MEAN:
+            ops.cls_qkv_reduce(dqkv_cls, dqkv, lay.B, lay.groups, 3 * D, x.shape[1])
+        d_qkv_w, d_qkv_b, dxn = _qkv_bwd(p_qkv, dqkv, xn, wqT, lay.rows, D, qmap=lay.qmap)
+        dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, lay.xmap, ln_w, mean, rstd, p_ln,
+                                          skip=_cls_rows(x.shape) if lay.cls == CLS_PASS else None)
+        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None, None)
 
 
 _compact = True
