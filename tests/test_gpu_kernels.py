@@ -5,6 +5,9 @@ fp32 path bar: 1e-3 of max|ref| (BASELINE north_star); in practice ~1e-6.
 bf16 path: inputs are rounded to bf16 first, the reference is computed in fp64 from the
 rounded inputs, bar 1e-2 (one bf16 output rounding is 2^-9 = 2e-3 of the element).
 Bit-exact: patch gather (fp32), HOG features and bins.
+The exact-arithmetic counterparts (equality instead of a bar) live in test_gpu_exact_arith.py (GEMMs, wprod, reductions,
+copies, casts), test_gpu_exact_attention.py and test_gpu_exact_layernorm.py (csrc/ln.hip: row-count edges of the grid-stride
+loops, both partial reduces, every NCH up to D = 2048).
 """
 import ctypes
 import json
