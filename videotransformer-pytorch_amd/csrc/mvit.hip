@@ -296,6 +296,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int B, int Tn, int H, 
     const unsigned t = r / HoWo, rr = r - t * HoWo, ho = rr / (unsigned)Wo, wo = rr - ho * Wo;
 #pragma unroll
     for (int j = 0; j < 8; ++j) { best[j] = -INFINITY; bi[j] = 0; }
+    bool first = true;                          // the first in-range tap is taken whatever it holds (a window of -inf: ATen's start index)
     for (int kh = 0; kh < 3; ++kh) {
       const int hh = (int)ho * 2 + kh - 1;
       if (hh < 0 || hh >= H) continue;
@@ -306,7 +307,8 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(int B, int Tn, int H, 
         load8(xb + (1 + ((long)t * H + hh) * W + ww) * C, v);
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          if (v[j] > best[j] || v[j] != v[j]) { best[j] = v[j]; bi[j] = kh * 3 + kw; }   // strictly greater (or NaN): the first maximum wins, as ATen
+          if (v[j] > best[j] || v[j] != v[j] || first) { best[j] = v[j]; bi[j] = kh * 3 + kw; }   // strictly greater (or NaN): the first maximum wins, as ATen
+        first = false;
       }
     }
     store8(y + oi, best);
