@@ -142,7 +142,8 @@ def test_timesformer_l_t96_full_depth_eval_vs_golden(prec):
     1.05e-2 at depth 12 -- the rounding of the stream grows with sqrt(depth) and at 24 layers it is 3x the reference's AMP noise.
     Bars for bf16 (stated plainly: the fixed 1.5e-2 of the 12-layer configurations is NOT met at this depth): (a) the depth-scaled
     bar TOL_BF16 * sqrt(24 / 12) = 2.12e-2, and (b) no worse than 1.25x what the bf16 stream costs the REFERENCE's own arithmetic.
-    An fp32 residual stream is the fix for deep models; it is not built."""
+    An fp32 residual stream is the fix for deep models: vtx.set_stream('fp32'), held to the fixed bar at this depth by
+    test_timesformer_l_t96_full_depth_exact_stream (tests/test_gpu_exact_stream.py)."""
     import vtx
     import video_transformer as V
     vtx.set_precision(prec)

@@ -158,8 +158,8 @@ def test_vivit_b_t16_exact_stream_vs_golden():
 
 @pytest.mark.parametrize('mode', ['fp32', 'fp32+grad'])
 def test_block_recompute_under_the_exact_stream(mode):
-    """vtx.set_recompute(True) with the exact stream: the block's input carries the float32 stream as an attribute and the re-run in
-    backward reads it from the same object -- outputs and gradients bit-identical to the stored-activation run ('fp32+grad': the
+    """vtx.set_recompute(True) with the exact stream: the checkpointed block takes the Stream (contribution, float32 stream) as its
+    argument and the re-run in backward gets the same pair -- outputs and gradients bit-identical to the stored-activation run ('fp32+grad': the
     float32 gradient rides on the gradient tensors between the same backward nodes, recompute or not)."""
     import vtx
     import video_transformer as V
@@ -197,6 +197,7 @@ def test_float32_gradient_stream_survives_only_on_the_unmodified_tensor():
     vtx.set_stream('fp32')
     assert F_._grad_stream(d, xs) is None                        # mode off
     # end to end: a tap on the stream between two blocks (a second consumer) still gives the right gradients
+    import transformer as T_
     import video_transformer as V
     grads = {}
     for mode in ('fp32', 'fp32+grad'):
@@ -208,7 +209,7 @@ def test_float32_gradient_stream_survives_only_on_the_unmodified_tensor():
         torch.manual_seed(11)
         y = m(synth.synth_clip(2, 4, 3, 64, 64, seed=2).to(DEV))
         h.remove()
-        (y.float().sum() + 0.5 * taps[0].float().sum()).backward()
+        (y.float().sum() + 0.5 * T_.stream_value(taps[0]).float().sum()).backward()
         grads[mode] = {k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None}
     for k in grads['fp32']:
         e = relerr(grads['fp32+grad'][k].cpu(), grads['fp32'][k].cpu())
@@ -295,6 +296,86 @@ def test_bench_stack_exact_stream_with_partial_ffn_drop(mode):
         worst = max(worst, e)
         assert e <= TOL_BF16_GRAD, f'{k}: {e:.3e}'
     report(f'bench stack bf16 exact stream {mode}: worst parameter gradient l2-rel {worst:.3e}')
+
+
+# ---- the hand-off between sub-blocks: transformer.Stream(d, xs) ----------------------------------------------------------------
+# The smallest model that has every hand-off (tokens -> block, attention -> attention -> FFN, block -> block, block -> readout).
+
+def _handoff_model(at='divided_space_time'):
+    import video_transformer as V
+    m, _ = _build(V.TimeSformer, 3, num_frames=4, attention_type=at, **dict(SMALL, num_transformer_layers=3))
+    return m.eval(), synth.synth_clip(2, 4, 3, 64, 64, seed=2).to(DEV)
+
+
+@pytest.mark.parametrize('at', ['divided_space_time', 'space_only', 'joint_space_time'])
+@pytest.mark.parametrize('mode', ['fp32', 'fp32+grad', 'bf16', 'fp32 under float32 compute'])
+def test_what_the_sub_blocks_hand_on(at, mode):
+    """Every sub-block, every block and the container hand on a Stream (bf16 contribution, float32 stream of the same shape) in the
+    two exact modes under bf16 compute, and a plain tensor otherwise (mode off; float32 compute is its own exact stream)."""
+    import vtx
+    import transformer as T_
+    exact = mode in ('fp32', 'fp32+grad')
+    if mode == 'fp32 under float32 compute':
+        vtx.set_precision('fp32')
+    vtx.set_stream(mode if exact or mode == 'bf16' else 'fp32')
+    m, clip = _handoff_model(at)
+    outs, hooks = [], []
+    mods = [m.transformer_layers] + list(m.transformer_layers.layers)
+    mods += [sub for blk in m.transformer_layers.layers for sub in list(blk.attentions) + list(blk.ffns)]
+    for mod in mods:
+        hooks.append(mod.register_forward_hook(lambda mod, inp, out: outs.append(out)))
+    with torch.no_grad():
+        y = m(clip)
+    for h in hooks:
+        h.remove()
+    n_sub = 3 if at == 'divided_space_time' else 2
+    assert len(outs) == 1 + 3 + 3 * n_sub and y.dtype == torch.float32
+    for out in outs:
+        if exact:
+            assert type(out) is T_.Stream
+            assert out.d.dtype == torch.bfloat16 and out.xs.dtype == torch.float32 and out.xs.shape == out.d.shape
+            assert not out.xs.requires_grad
+        else:
+            assert type(out) is torch.Tensor
+
+
+def test_stream_value_is_the_rounded_sum():
+    """stream_value(Stream(d, xs)) = bf16(xs + d): one round-to-nearest-even of the float32 sum (that the kernel's sum IS the
+    float32 sum: test_layernorm_acc_fwd_vs_float64)."""
+    import transformer as T_
+    m, clip = _handoff_model()
+    with torch.no_grad():
+        s = m.transformer_layers(m.prepare_tokens(clip)[0])
+        assert type(s) is T_.Stream
+        assert torch.equal(T_.stream_value(s), (s.xs + s.d.float()).to(torch.bfloat16))
+
+
+def test_the_readout_takes_the_pair():
+    import transformer as T_
+    m, clip = _handoff_model()
+    with torch.no_grad():
+        s = m.transformer_layers(m.prepare_tokens(clip)[0])
+        assert type(s) is T_.Stream
+        assert torch.equal(m._readout(s), m(clip))
+
+
+def test_a_collapsed_stream_restarts_instead_of_vanishing():
+    """A forward hook that turns a block's output into one tensor (stream_value): the next block starts a new stream AT that
+    tensor -- the whole sum up to there, not the last contribution alone.  Bit-equal to block 2 and the readout run by hand on it."""
+    import transformer as T_
+    m, clip = _handoff_model()
+    seen = []
+
+    def collapse(mod, inp, out):
+        seen.append(T_.stream_value(out))
+        return seen[-1]
+    h = m.transformer_layers.layers[1].register_forward_hook(collapse)
+    with torch.no_grad():
+        y = m(clip)
+        h.remove()
+        assert len(seen) == 1 and type(seen[0]) is torch.Tensor and seen[0].dtype == torch.bfloat16
+        by_hand = m._readout(m.transformer_layers.layers[2](seen[0]))
+    assert torch.equal(y, by_hand)
 
 
 # ---- 'fp32+grad': the stream's gradient in float32 too ---------------------------------------------------------------------

@@ -14,6 +14,8 @@ operator orders of divided attention run: time-then-space (the models' own) and
 space-then-time, where the temporal op attends over the cls token and the
 spatial op does not (``use_cls_token``, reference transformer.py:602,611).
 """
+import collections
+
 import numpy as np
 
 import torch
@@ -95,30 +97,33 @@ class DropPath(nn.Module):
         return F_.RowScaleFn.apply(x, s, rows_per)
 
 
+# What flows between sub-blocks under the exact stream (vtx.set_stream('fp32'), bf16 kernels): d, the bf16 contribution (an autograd
+# tensor), and xs, the float32 stream d was computed from (a non-differentiable side buffer; None: the stream starts at d).  A plain
+# tuple, deliberately not usable as a tensor: stream_value() gives the stream as one.
+Stream = collections.namedtuple('Stream', 'd xs')
+
+
 def _stream_of(t):
-    """(float32 stream, exact?) for a block input under vtx.set_stream('fp32'): the stream rides on the contribution tensor as an
-    attribute (it is a side buffer, not an autograd tensor -- vtx/functions.py, "the exact residual stream").  Exact mode is the
-    bf16 path only; float32 activations are their own exact stream."""
-    exact = F_.exact_stream() and t.dtype == torch.bfloat16
-    return (getattr(t, '_vtx_xs', None) if exact else None), exact
+    """(d, xs, exact?) of a sub-block input.  A Stream: its members.  A plain bf16 tensor under vtx.set_stream('fp32'): the stream
+    starts (or restarts) at it.  Exact mode is the bf16 path only; float32 activations are their own exact stream."""
+    if isinstance(t, Stream):
+        if not F_.exact_stream():
+            raise TypeError("vtx: a Stream was handed on, but vtx.set_stream('fp32') is off")
+        return t.d, t.xs, True
+    return t, None, F_.exact_stream() and t.dtype == torch.bfloat16
 
 
 def _with_stream(res, exact):
-    """What a block hands on: the contribution with the new float32 stream attached (exact), or the bf16 stream itself."""
-    if not exact:
-        return res
-    out, x32 = res
-    out._vtx_xs = x32
-    return out
+    """What a sub-block hands on: Stream(contribution, the float32 stream it read) (exact), or the bf16 stream itself."""
+    return Stream(*res) if exact else res
 
 
 def stream_value(t):
-    """The stream as one tensor for consumers outside the blocks: t itself, or bf16(float32 stream + contribution) under the
-    exact stream (vtx.functions.StreamValueFn)."""
-    xs, exact = _stream_of(t)
-    if not exact or xs is None:
+    """The stream as one tensor for consumers outside the blocks: t itself, or bf16(float32 stream + contribution) for a Stream
+    (vtx.functions.StreamValueFn)."""
+    if not isinstance(t, Stream):
         return t
-    return F_.StreamValueFn.apply(t, xs)
+    return t.d if t.xs is None else F_.StreamValueFn.apply(t.d, t.xs)
 
 
 def _no_exact(what):
@@ -262,8 +267,8 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
     def forward(self, query, key=None, value=None, residual=None, return_attention=False, **kwargs):
         assert residual is None, 'Always adding the shortcut in the forward function'
         self._guard()
-        x = _to_compute(query)
-        xs, exact = _stream_of(query)
+        x, xs, exact = _stream_of(query)
+        x = _to_compute(x)
         b, n1, d = x.shape
         t = self.num_frames
         if (n1 - 1) % t:
@@ -302,8 +307,8 @@ class DividedSpatialAttentionWithPreNorm(_DividedBase):
     def forward(self, query, key=None, value=None, residual=None, return_attention=False, **kwargs):
         assert residual is None, 'Always adding the shortcut in the forward function'
         self._guard()
-        x = _to_compute(query)
-        xs, exact = _stream_of(query)
+        x, xs, exact = _stream_of(query)
+        x = _to_compute(x)
         b = x.shape[0]
         t = self.num_frames
         if (x.shape[1] - 1) % t:
@@ -333,8 +338,8 @@ class MultiheadAttentionWithPreNorm(nn.Module):
         if self.training:
             _no_dropout(self.proj_drop.p, 'proj_drop')
             _no_dropout(self.attn.attn_drop.p, 'attn_drop')
-        x = _to_compute(query)
-        xs, exact = _stream_of(query)
+        x, xs, exact = _stream_of(query)
+        x = _to_compute(x)
         s = None if return_attention else _drop_scale(self.layer_drop, x.shape[0], 3, x.device)
         res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                               self.attn.proj.weight, self.attn.proj.bias, 'self', 0, self.num_heads, s,
@@ -369,7 +374,7 @@ class FFNWithPreNorm(nn.Module):
     def forward(self, x):
         if self.training:
             _no_dropout(self.dropout_p, 'dropout_p')
-        xs, exact = _stream_of(x)
+        x, xs, exact = _stream_of(x)
         x = _to_compute(x)
         s = _drop_scale(self.layer_drop, x.shape[0], x.ndim, x.device)
         fc1, fc2 = self.layers[0][0], self.layers[1]
@@ -442,7 +447,7 @@ class TransformerContainer(nn.Module):
                 x = layer(x, return_attention=True)
             elif recompute:
                 # the CPU generator state is saved and restored around the re-run: DropPath draws the same masks.  (Under the exact
-                # stream the block's input carries its float32 stream as an attribute; the re-run reads it from the same object.)
+                # stream x is a Stream: the re-run gets the contribution and its float32 stream as the arguments they are.)
                 x = torch.utils.checkpoint.checkpoint(layer, x, use_reentrant=False)
             else:
                 x = layer(x)

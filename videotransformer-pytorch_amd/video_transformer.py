@@ -15,7 +15,7 @@ import torch.nn as nn
 import vtx
 from vtx import functions as F_
 from vtx import ops
-from transformer import PatchEmbed, TransformerContainer, get_sine_cosine_pos_emb, stream_value
+from transformer import PatchEmbed, TransformerContainer, get_sine_cosine_pos_emb, stream_value, _stream_of, _with_stream
 from weight_init import (trunc_normal_, init_from_vit_pretrain_, init_from_mae_pretrain_,
                          init_from_kinetics_pretrain_)
 from mvit import (PatchEmbeding, create_conv_patch_embed, create_multiscale_vision_transformers)  # noqa: F401
@@ -58,15 +58,13 @@ class _VideoTransformerBase(nn.Module):
         exact = F_.exact_stream() and dtype == torch.bfloat16
         out = F_.TokensFn.apply(x, proj.weight, proj.bias, self.cls_token, pos,
                                 None if time_embed is None else _embed(time_embed, dev), dtype, layout, exact)
-        if exact:                                    # the stream starts in float32 (transformer._stream_of reads the attribute)
-            out, xs0 = out
-            out._vtx_xs = xs0
-        return out
+        return _with_stream(out, exact)              # (exact: the stream starts in float32 -- TokensFn gives the first pair)
 
     def _readout(self, x):
-        # under vtx.set_stream('fp32') x is the last sub-block's contribution and carries the float32 stream (transformer._stream_of)
-        exact = F_.exact_stream() and x.dtype == torch.bfloat16 and getattr(x, '_vtx_xs', None) is not None
-        xs = x._vtx_xs if exact else None
+        # under vtx.set_stream('fp32') x is a Stream: the last sub-block's contribution and the float32 stream it read; the add is
+        # fused into the LayerNorm kernel
+        x, xs, exact = _stream_of(x)
+        exact = exact and xs is not None             # a stream that starts at x (the space_only frame mean): nothing to add
         if self.return_cls_token:
             y = F_.LayerNormFn.apply(x, self.norm.weight, self.norm.bias, self.norm.eps, True, xs, exact)
             return F_.CastFn.apply(y, torch.float32)
@@ -277,7 +275,7 @@ class ViViT(_VideoTransformerBase):
         else:
             tok = self._tokens(x, 'pt', self.time_embed)
         # the reference also returns its (pre-embedding) cls tokens; nothing downstream reads them
-        cls_tokens = self.cls_token.expand(tok.shape[0], -1, -1)
+        cls_tokens = self.cls_token.expand(_stream_of(tok)[0].shape[0], -1, -1)
         return tok, cls_tokens, b
 
     def _fact_temporal_tokens(self, x, b):

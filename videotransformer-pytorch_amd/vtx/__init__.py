@@ -52,13 +52,12 @@ def recompute_enabled():
 
 def set_stream(kind):
     """How the bf16 path keeps the residual stream: 'bf16' (default: every sub-block's x + f(x) is rounded to bf16 -- the fastest
-    form, whose rounding of the running sum grows with sqrt(depth): 2x the reference's own autocast deviation on outputs at 12
-    layers, 3x at 24) or 'fp32' (the exact stream: sub-blocks hand on their contribution, the running sum lives in float32 and is
-    advanced inside the next LayerNorm kernel -- what torch.autocast does in the reference; +0.7 GB of HBM traffic per sub-block at
-    96 clips, +4 % step time) or 'fp32+grad' (the exact stream AND its gradient in float32 through the backward: the LayerNorm
-    backward of every sub-block adds its term to the float32 gradient of the stream and hands on the sum and its one bf16 rounding;
-    +7 % step time in all; parameter gradients at 12 layers: worst 1.4e-2 -> 1.2e-2, median 8.5e-3 -> 7.2e-3 off the fp32 reference).  Every attention type of
-    TimeSformer / ViViT; the float32 precision mode is its own exact stream."""
+    form, whose rounding of the running sum grows with sqrt(depth)) or 'fp32' (the exact stream: sub-blocks hand on their
+    contribution, the running sum lives in float32 and is advanced inside the next LayerNorm kernel -- what torch.autocast does in
+    the reference) or 'fp32+grad' (the exact stream AND its gradient in float32 through the backward: the LayerNorm backward of
+    every sub-block adds its term to the float32 gradient of the stream and hands on the sum and its one bf16 rounding).  Every
+    attention type of TimeSformer / ViViT; the float32 precision mode is its own exact stream.  What each mode costs in step time
+    and gains in accuracy: DESIGN.md section 3."""
     if kind not in ('bf16', 'fp32', 'fp32+grad'):
         raise ValueError(kind)
     functions.set_exact_stream(kind != 'bf16')
@@ -73,5 +72,6 @@ def get_stream():
 
 import os as _os  # noqa: E402
 
-if _os.environ.get('VTX_STREAM', 'bf16') in ('fp32', 'fp32+grad'):      # initial value for entry points that keep the reference's flag list (model_pretrain.py)
-    set_stream(_os.environ['VTX_STREAM'])
+_v = _os.environ.get('VTX_STREAM')      # initial value for entry points that keep the reference's flag list (model_pretrain.py)
+if _v is not None:
+    set_stream(_v)

@@ -213,6 +213,12 @@ def _ln_grad_buffers(params, D, device):
 # flow through the bf16 stream (d(xs + d)/dd = 1), so every backward below is shared between the two modes.  Every attention
 # type of TimeSformer / ViViT (readers that need the stream as ONE tensor -- the space_only frame mean, the ViViT fact-encoder
 # glue -- take it through StreamValueFn); MViT keeps its bf16 stream.
+# The hand-off between sub-blocks is explicit: the modules pass the pair on as transformer.Stream(d, xs), which is no tensor (a
+# hook or wrapper that wants one calls transformer.stream_value), and a plain bf16 tensor handed to a sub-block starts the stream
+# anew at that tensor -- nothing can drop xs without saying so.  Two attributes on tensors stay, because losing either is
+# harmless: `_vtx_g32`, the float32 gradient of the stream on its bf16 rounding, is stamped with the tensor's version counter
+# and falls back to a correct restart from the bf16 gradient (_grad_stream); `_vtx_host`, the host copy of a DropPath scale
+# vector (transformer.DropPath), only selects the compacted FFN, and without it the uncompacted one runs.
 _exact = False
 
 
