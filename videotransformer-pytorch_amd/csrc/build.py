@@ -1,9 +1,10 @@
-"""Build libvtx.so (gfx950) with hipcc -- no torch headers, no cmake.
+"""Build libvtx.so and libvtx_aug.so (gfx950) with hipcc -- no torch headers, no cmake.
 
     python videotransformer-pytorch_amd/csrc/build.py [--force]
 
 Each .hip file is compiled to an object (skipped when up to date) and linked into
-videotransformer-pytorch_amd/libvtx.so.  hipcc cross-compiles without a GPU.
+videotransformer-pytorch_amd/libvtx.so; csrc/aug.hip (clip augmentation, include/vtx_aug.h) becomes
+videotransformer-pytorch_amd/libvtx_aug.so.  hipcc cross-compiles without a GPU.
 """
 import os
 import subprocess
@@ -13,6 +14,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, 'libvtx.so')
+AUG_OUT = os.path.join(PKG, 'libvtx_aug.so')
 OBJ = os.path.join(HERE, '_obj')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_mfma.hip', 'attn_long.hip', 'attn_f32.hip', 'elementwise.hip', 'hog.hip', 'optim.hip', 'head.hip', 'mvit.hip', 'wprod.hip', 'xattn_mfma.hip']
@@ -21,14 +23,17 @@ SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_
 # two it replaces (MI355X_MICROARCH.md): step 128.24 -> 127.84 ms over three interleaved A/B rounds.  NOT adopted: without the packing
 # the compiler fuses other multiply-add pairs, every bf16 result moves inside its rounding noise, and the noisiest statistic of the
 # suite -- the 24-layer default-stream maximum -- landed on the wrong side of its bar.  `build.py --variant noslp -fno-slp-vectorize`.)
+AUG_SOURCES = ['aug.hip']          # the second library: nothing of it is linked into libvtx.so
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result', '-Wno-unused-value', '-Wno-inline-asm',
          '-Wno-cuda-compat']
-EXTRA = {'hog.hip': ['-ffp-contract=off']}       # bit-exact HOG: no fma contraction
+EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contraction
+         'aug.hip': ['-ffp-contract=off']}         # torchvision's float32 blends and weighted sums, product by product
 
 
 def _deps():
     hdrs = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith('.h')]
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx.h'))
+    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_aug.h'))
     hdrs.append(os.path.abspath(__file__))                       # the flags live here
     return max(os.path.getmtime(h) for h in hdrs)
 
@@ -85,19 +90,25 @@ def build(force=False, verbose=True):
             fcntl.flock(lock, fcntl.LOCK_UN)
 
 
-def _build_locked(force, verbose):
-    with ThreadPoolExecutor(max_workers=min(8, len(SOURCES))) as ex:
-        res = list(ex.map(lambda s: _compile(s, force), SOURCES))
-    objs = [o for o, _ in res]
-    if any(c for _, c in res) or not os.path.exists(OUT):
-        cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC', '-o', OUT] + objs
+def _link(out, res, extra, verbose):
+    if any(c for _, c in res) or not os.path.exists(out):
+        cmd = [HIPCC, '--offload-arch=gfx950', '-shared', '-fPIC'] + extra + ['-o', out] + [o for o, _ in res]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f'link failed:\n{r.stdout}\n{r.stderr}')
         if verbose:
-            print(f'built {OUT}')
+            print(f'built {out}')
     elif verbose:
-        print(f'{OUT} up to date')
+        print(f'{out} up to date')
+
+
+def _build_locked(force, verbose):
+    both = SOURCES + AUG_SOURCES
+    with ThreadPoolExecutor(max_workers=min(8, len(both))) as ex:
+        res = list(ex.map(lambda s: _compile(s, force), both))
+    _link(OUT, res[:len(SOURCES)], [], verbose)
+    # -Bsymbolic: the library's own definitions of the helpers common.h declares, whatever else the process has loaded
+    _link(AUG_OUT, res[len(SOURCES):], ['-Wl,-Bsymbolic'], verbose)
     return OUT
 
 

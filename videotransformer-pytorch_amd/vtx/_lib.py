@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get('VTX_LIB', os.path.join(_PKG, 'libvtx.so'))
 
 VTX_F32, VTX_BF16, VTX_BF16_X32 = 0, 1, 3
 ATTN_CONTIG, ATTN_SPACE, ATTN_TIME_CLS, ATTN_SPACE_NOCLS = 0, 1, 2, 3
+RESAMPLE_BILINEAR, RESAMPLE_BICUBIC = 0, 1
+JIT_BRIGHTNESS, JIT_CONTRAST, JIT_SATURATION = 0, 1, 2
 
 
 class RowMap(C.Structure):
@@ -172,11 +174,55 @@ SIGNATURES = {
     'vtx_selftest': (ci, [C.c_char_p, sz]),
 }
 
+# libvtx_aug.so (include/vtx_aug.h, csrc/aug.hip): clip augmentation, a library of its own.  Must list every symbol the header declares.
+AUG_LIB_PATH = os.environ.get('VTX_AUG_LIB', os.path.join(_PKG, 'libvtx_aug.so'))
+AUG_SIGNATURES = {
+    'vtx_aug_version': (ci, []),
+    'vtx_aug_last_error_string': (C.c_char_p, []),
+    'vtx_resample_max_taps': (ci, [ci, ci, ci, ci]),
+    'vtx_resample_build_table': (ci, [ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
+    'vtx_clip_resample_u8': (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+    'vtx_clip_jitter_workspace': (sz, [ci, ci]),
+    'vtx_clip_jitter_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+}
+
 _lib = None
+_aug = None
 
 
 class VtxError(RuntimeError):
     pass
+
+
+def load_aug():
+    """Load libvtx_aug.so and bind every symbol of include/vtx_aug.h.  Raises if anything is missing: there is no fallback."""
+    global _aug
+    if _aug is not None:
+        return _aug
+    if not os.path.isfile(AUG_LIB_PATH):
+        raise VtxError(f'libvtx_aug.so not found at {AUG_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(AUG_LIB_PATH)
+    for name, (res, args) in AUG_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_aug.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _aug = lib
+    return lib
+
+
+def aug_check(rc, what=''):
+    msg = load_aug().vtx_aug_last_error_string()
+    raise VtxError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def aug_call(name, *args):
+    rc = getattr(load_aug(), name)(*args)
+    if rc != 0:
+        aug_check(rc, name)
 
 
 def load():

@@ -1,0 +1,206 @@
+"""Clip augmentation on the device: the transforms of the reference's ``transforms_train`` / ``transforms_eval``
+(data_transform.py:495-574) that run before ToTensor + Normalize, on decoded uint8 clips [B,T,H,W,3].
+
+    aug = vtx.aug.ClipAugment(img_size=224)             # RandomResizedCrop (bicubic) + flip + ColorJitter(0.4, 0.4, 0.4)
+    vtx.set_input_normalization(mean, std)              # ToTensor + Normalize: fused into the patch gather
+    out = model(aug(clip_u8.cuda()))
+
+What is random is drawn on the host (``sample_params``: torchvision's draws restated, under a ``torch.Generator``), once per
+clip -- every frame of a clip gets the same crop, flip and colour factors, as the reference's single call on a [T,C,H,W]
+tensor does.  The pixels are touched by libvtx_aug.so only (csrc/aug.hip, include/vtx_aug.h): ``vtx_clip_resample_u8`` and ``vtx_clip_jitter_u8``.
+
+Not built: ThreeCrop, RandAugment (``auto_augment``), RandomGrayscale, hue jitter and the temporal sampling of the dataset.
+"""
+import math
+from collections import namedtuple
+
+import numpy as np
+import torch
+
+from . import ops
+
+#: one clip's draws: crop box (rows top .. top+height, columns left .. left+width of the source frame), the flip coin and the
+#: colour ops in the order they are applied (0 brightness, 1 contrast, 2 saturation) with their factors
+ClipDraw = namedtuple('ClipDraw', 'top left height width flip ops factors')
+
+
+def _uniform(lo, hi, generator):
+    return float(torch.empty(1).uniform_(float(lo), float(hi), generator=generator))
+
+
+def _crop_box(height, width, scale, ratio, generator):
+    """torchvision RandomResizedCrop.get_params: ten tries of (uniform area, log-uniform ratio), then the centre crop with the
+    ratio clamped into range."""
+    area = height * width
+    log_ratio = torch.log(torch.tensor([float(ratio[0]), float(ratio[1])]))
+    for _ in range(10):
+        target_area = area * _uniform(scale[0], scale[1], generator)
+        aspect = float(torch.exp(torch.empty(1).uniform_(float(log_ratio[0]), float(log_ratio[1]), generator=generator)))
+        w = int(round(math.sqrt(target_area * aspect)))
+        h = int(round(math.sqrt(target_area / aspect)))
+        if 0 < w <= width and 0 < h <= height:
+            top = int(torch.randint(0, height - h + 1, size=(1,), generator=generator))
+            left = int(torch.randint(0, width - w + 1, size=(1,), generator=generator))
+            return top, left, h, w
+    in_ratio = float(width) / float(height)
+    if in_ratio < min(ratio):
+        w = width
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = height
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = width, height
+    h, w = max(1, min(h, height)), max(1, min(w, width))
+    return (height - h) // 2, (width - w) // 2, h, w
+
+
+def _jitter_ranges(color_jitter):
+    """ColorJitter's (brightness, contrast, saturation) ranges [max(0, 1 - v), 1 + v]; None where the op is off."""
+    if color_jitter is None:
+        return None
+    if isinstance(color_jitter, (list, tuple)):
+        if len(color_jitter) not in (3, 4):
+            raise ValueError('color_jitter: a number or 3 values (brightness, contrast, saturation)')
+        if len(color_jitter) == 4 and color_jitter[3]:
+            raise NotImplementedError('color_jitter: hue is not built')
+        vals = [float(v) for v in color_jitter[:3]]
+    else:
+        vals = [float(color_jitter)] * 3
+    out = []
+    for v in vals:
+        if v < 0:
+            raise ValueError('color_jitter: values must be non-negative')
+        out.append(None if v == 0 else (max(0.0, 1.0 - v), 1.0 + v))
+    return out
+
+
+def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, generator=None):
+    """The draws of RandomResizedCrop + RandomHorizontalFlip + ColorJitter for B clips of ``src_hw`` = (height, width) frames:
+    a list of B ``ClipDraw``.  Host code; all randomness comes from ``generator`` (None = torch's default CPU generator)."""
+    height, width = int(src_hw[0]), int(src_hw[1])
+    scale = tuple(scale or (0.08, 1.0))
+    ratio = tuple(ratio or (3. / 4., 4. / 3.))
+    ranges = _jitter_ranges(color_jitter)
+    draws = []
+    for _ in range(int(B)):
+        top, left, h, w = _crop_box(height, width, scale, ratio, generator)
+        flip = bool(hflip > 0. and float(torch.rand(1, generator=generator)) < hflip)
+        jops, jfac = [], []
+        if ranges is not None:
+            order = torch.randperm(4, generator=generator).tolist()          # ColorJitter.get_params: the order, then b, c, s
+            fac = [None if r is None else _uniform(r[0], r[1], generator) for r in ranges]
+            for fn in order:
+                if fn < 3 and fac[fn] is not None:
+                    jops.append(fn)
+                    jfac.append(fac[fn])
+        draws.append(ClipDraw(top, left, h, w, flip, tuple(jops), tuple(jfac)))
+    return draws
+
+
+def _check_draws(draws, B, Hs, Ws):
+    if len(draws) != B:
+        raise ValueError(f'params: {len(draws)} records for {B} clips')
+    for d in draws:
+        if not (0 <= d.top and 0 < d.height and d.top + d.height <= Hs and 0 <= d.left and 0 < d.width and d.left + d.width <= Ws):
+            raise ValueError(f'params: crop box (top {d.top}, left {d.left}, {d.height}x{d.width}) outside the {Hs}x{Ws} frame')
+        if len(d.ops) != len(d.factors) or len(d.ops) > 3 or len(set(d.ops)) != len(d.ops) or any(o not in (0, 1, 2) for o in d.ops):
+            raise ValueError(f'params: colour ops {d.ops} / factors {d.factors}: each of 0, 1, 2 at most once, one factor per op')
+
+
+def _tables(specs, mode, antialias):
+    """specs: per clip (src_len, crop_start, crop_len, out_len, flip, lo, n) -> first [B,n], count [B,n], weights [B,n,taps]
+    (rows lo .. lo+n of each clip's table)."""
+    taps = max(ops.resample_max_taps(s[2], s[3], mode, antialias) for s in specs)
+    built = {}                                              # clips that share a spec (ClipEval: all of them) share the table
+    for s in specs:
+        if s[:5] not in built:
+            built[s[:5]] = ops.resample_table(s[0], s[1], s[2], s[3], mode, antialias, s[4], taps)
+    tabs = [built[s[:5]] for s in specs]
+    cut = [tuple(a[s[5]:s[5] + s[6]] for a in t) for t, s in zip(tabs, specs)]
+    return tuple(np.stack([c[i] for c in cut]) for i in range(3))
+
+
+def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
+    """Tables (and colour records) to the device in one copy, then the kernels."""
+    xf, xc, xw = _tables(xspecs, mode, antialias)
+    yf, yc, yw = _tables(yspecs, mode, antialias)
+    parts = [xf, xc, xw.view(np.int32), yf, yc, yw.view(np.int32)]
+    jitter = draws is not None and any(d.ops for d in draws)
+    if jitter:
+        B = len(draws)
+        jo = np.zeros((B, 4), dtype=np.int32)
+        jf = np.zeros((B, 6), dtype=np.float32)
+        for b, d in enumerate(draws):
+            jo[b, 0] = len(d.ops)
+            jo[b, 1:1 + len(d.ops)] = d.ops
+            jf[b, :len(d.ops)] = d.factors
+            jf[b, 3:3 + len(d.ops)] = [1.0 - float(f) for f in d.factors]      # in float64, then rounded: torchvision's _blend
+        parts += [jo, jf.view(np.int32)]
+    dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.device)
+    views, at = [], 0
+    for p in parts:
+        views.append(dev[at:at + p.size].view(p.shape))
+        at += p.size
+    f32 = lambda t: t.view(torch.float32)
+    out = ops.clip_resample_u8(clips, out_hw, (views[0], views[1], f32(views[2])), (views[3], views[4], f32(views[5])))
+    if jitter:
+        ops.clip_jitter_u8_(out, views[6], f32(views[7]))
+    return out
+
+
+def _check_clips(clips):
+    ops._check_u8_clip(clips, 'vtx.aug')
+    return clips.shape[0], clips.shape[2], clips.shape[3]
+
+
+class ClipAugment:
+    """``transforms_train`` (data_transform.py:495-531) without its ToTensor + Normalize tail, per clip on the device.  Takes
+    that function's arguments and defaults; ``scale=(0.5, 1.0), color_jitter=None`` is the ``mim`` branch of
+    data_trainer.py:61-63.  uint8 CUDA [B,T,Hs,Ws,3] -> uint8 CUDA [B,T,img_size,img_size,3]."""
+
+    def __init__(self, img_size=224, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, interpolation='bicubic', antialias=False):
+        self.out_hw = (int(img_size), int(img_size)) if not isinstance(img_size, (tuple, list)) else (int(img_size[0]), int(img_size[1]))
+        self.scale, self.ratio, self.hflip, self.color_jitter = scale, ratio, float(hflip), color_jitter
+        ops._resample_mode(interpolation)
+        _jitter_ranges(color_jitter)
+        self.interpolation, self.antialias = interpolation, bool(antialias)
+
+    def __call__(self, clips_u8, generator=None, params=None):
+        B, Hs, Ws = _check_clips(clips_u8)
+        if params is None:
+            params = sample_params(B, (Hs, Ws), self.scale, self.ratio, self.hflip, self.color_jitter, generator)
+        _check_draws(params, B, Hs, Ws)
+        H, W = self.out_hw
+        xs = [(Ws, d.left, d.width, W, d.flip, 0, W) for d in params]
+        ys = [(Hs, d.top, d.height, H, False, 0, H) for d in params]
+        return _run(clips_u8, xs, ys, self.out_hw, self.interpolation, self.antialias, params)
+
+
+class ClipEval:
+    """``transforms_eval`` (data_transform.py:546-566) without ToTensor + Normalize: resize the short side to
+    floor(img_size / crop_pct), centre crop img_size -- one resampling pass whose tables are those of the whole resized frame,
+    cut to the crop window."""
+
+    def __init__(self, img_size=224, crop_pct=None, interpolation='bicubic', antialias=False):
+        self.img_size = int(img_size)
+        self.scale_size = int(math.floor(self.img_size / (crop_pct or 0.875)))
+        ops._resample_mode(interpolation)
+        self.interpolation, self.antialias = interpolation, bool(antialias)
+
+    def resized_hw(self, Hs, Ws):
+        """torchvision Resize(int): the short side becomes scale_size, the long side int(scale_size * long / short)."""
+        short, long = (Ws, Hs) if Ws <= Hs else (Hs, Ws)
+        new_short, new_long = self.scale_size, int(self.scale_size * long / short)
+        return (new_long, new_short) if Ws <= Hs else (new_short, new_long)
+
+    def __call__(self, clips_u8):
+        B, Hs, Ws = _check_clips(clips_u8)
+        Hr, Wr = self.resized_hw(Hs, Ws)
+        S = self.img_size
+        if Hr < S or Wr < S:
+            raise ValueError(f'ClipEval: the resized frame {Hr}x{Wr} is smaller than the {S}x{S} crop (padding is not built)')
+        top, left = int(round((Hr - S) / 2.0)), int(round((Wr - S) / 2.0))
+        xs = [(Ws, 0, Ws, Wr, False, left, S)] * B
+        ys = [(Hs, 0, Hs, Hr, False, top, S)] * B
+        return _run(clips_u8, xs, ys, (S, S), self.interpolation, self.antialias)

@@ -602,6 +602,83 @@ def hog_fwd(frames, want_bins=False):
     return (out, bins) if want_bins else out
 
 
+# ------------------------------------------------- clip augmentation (csrc/aug.hip -> libvtx_aug.so)
+RESAMPLE_MODES = {'bilinear': _lib.RESAMPLE_BILINEAR, 'bicubic': _lib.RESAMPLE_BICUBIC}
+
+
+def _resample_mode(mode):
+    try:
+        return RESAMPLE_MODES[mode]
+    except KeyError:
+        raise ValueError(f"resample: interpolation {mode!r} is not built ('bilinear' or 'bicubic')")
+
+
+def resample_max_taps(crop_len, out_len, mode, antialias=False):
+    """Taps per output index a table of vtx_resample_build_table needs (host only)."""
+    n = _lib.load_aug().vtx_resample_max_taps(int(crop_len), int(out_len), _resample_mode(mode), int(bool(antialias)))
+    if n <= 0:
+        _lib.aug_check(n, 'vtx_resample_max_taps')
+    return n
+
+
+def resample_table(src_len, crop_start, crop_len, out_len, mode, antialias=False, flip=False, max_taps=None):
+    """F.interpolate(align_corners=False) weights of one axis (host only, NumPy): first int32 [out_len], count int32 [out_len],
+    weights float32 [out_len, max_taps] (zero behind ``count``)."""
+    import numpy as np
+    if max_taps is None:
+        max_taps = resample_max_taps(crop_len, out_len, mode, antialias)
+    first = np.zeros(out_len, dtype=np.int32)
+    count = np.zeros(out_len, dtype=np.int32)
+    weights = np.zeros((out_len, max_taps), dtype=np.float32)
+    _lib.aug_call('vtx_resample_build_table', int(src_len), int(crop_start), int(crop_len), int(out_len), _resample_mode(mode),
+         int(bool(antialias)), int(bool(flip)), int(max_taps), first.ctypes.data, count.ctypes.data, weights.ctypes.data)
+    return first, count, weights
+
+
+def _check_u8_clip(clip, what):
+    need_cuda(clip)
+    if clip.dtype != torch.uint8 or clip.ndim != 5 or clip.shape[-1] != 3:
+        raise TypeError(f'{what}: clip must be uint8 [B,T,H,W,3], got {clip.dtype} {tuple(clip.shape)}')
+
+
+def clip_resample_u8(src, out_hw, xtab, ytab):
+    """src uint8 [B,T,Hs,Ws,3] -> uint8 [B,T,H,W,3].  xtab = (first [B,W] int32, count [B,W] int32, weights [B,W,K] float32)
+    device tensors, one resample_table per clip; ytab likewise with H."""
+    _check_u8_clip(src, 'clip_resample_u8')
+    src = src.contiguous()
+    B, T, Hs, Ws, _ = src.shape
+    H, W = int(out_hw[0]), int(out_hw[1])
+    for (f, c, w), n in ((xtab, W), (ytab, H)):
+        need_cuda(f, c, w)
+        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
+                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n)
+                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
+            raise TypeError(f'clip_resample_u8: a table is (int32 [{B},{n}], int32 [{B},{n}], float32 [{B},{n},taps]), contiguous')
+    dst = torch.empty(B, T, H, W, 3, dtype=torch.uint8, device=src.device)
+    with _timed('clip_resample', nbytes=src.numel() + dst.numel(), key=f'{B}x{T} {Hs}x{Ws}->{H}x{W}'):
+        _lib.aug_call('vtx_clip_resample_u8', B, T, Hs, Ws, H, W, ptr(src), ptr(dst), ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]),
+             xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]), ptr(ytab[2]), ytab[2].shape[2], stream())
+    return dst
+
+
+def clip_jitter_u8_(clip, jit_ops, factors):
+    """In place on a contiguous uint8 [B,T,H,W,3] clip: per clip, jit_ops [B,4] int32 = {n, op, op, op} (0 brightness, 1 contrast,
+    2 saturation) applied in that order with factors [B,6] float32 = {r, r, r, 1 - r, 1 - r, 1 - r} (torchvision's ColorJitter
+    without hue; 1 - r is formed in float64 and rounded on its own, as torchvision's _blend does)."""
+    _check_u8_clip(clip, 'clip_jitter_u8_')
+    need_cuda(jit_ops, factors)
+    B, T, H, W, _ = clip.shape
+    if not clip.is_contiguous():
+        raise TypeError('clip_jitter_u8_: contiguous clip required (in place)')
+    if (jit_ops.dtype != torch.int32 or tuple(jit_ops.shape) != (B, 4) or factors.dtype != torch.float32
+            or tuple(factors.shape) != (B, 6) or not (jit_ops.is_contiguous() and factors.is_contiguous())):
+        raise TypeError(f'clip_jitter_u8_: jit_ops int32 [{B},4] and factors float32 [{B},6], contiguous')
+    ws = torch.empty(_lib.load_aug().vtx_clip_jitter_workspace(B, T) // 4, dtype=torch.int32, device=clip.device)
+    with _timed('clip_jitter', nbytes=3 * clip.numel(), key=f'{B}x{T} {H}x{W}'):
+        _lib.aug_call('vtx_clip_jitter_u8', B, T, H, W, ptr(clip), ptr(jit_ops), ptr(factors), ptr(ws), ws.numel() * 4, stream())
+    return clip
+
+
 # ------------------------------------------------- clip-batch mixing, accuracy (csrc/head.hip)
 def mixup_batch_(x, lam):
     """In place: x[b] = x[b]*lam + x[B-1-b]*(1-lam) on a contiguous fp32 [B, ...] batch (reference mixup.py:112-113)."""
