@@ -126,8 +126,9 @@ def nt_reference(name, A, W, bias=None, h=None, scale=None, R=None):
 TOK_B, TOK_P, TOK_T = 3, 197, 4
 TOK_N = TOK_P * TOK_T
 
-# vtx_gemm_nt epilogues with exact arithmetic (the GELU epilogues, act 1 / 2 and dgelu_kind 0, are not; 'act_residual'
-# is checked exactly on its pre-activation copy only)
+# vtx_gemm_nt epilogues with exact arithmetic (the GELU epilogues, act 1 / 2 and dgelu_kind 0, are not: exact_gelu.py and
+# test_gpu_exact_gelu.py hold them to the fp32 kernel's values by equality and to float64 by a per-element bound;
+# 'act_residual' is checked exactly on its pre-activation copy only)
 NT_EPILOGUES = ('plain', 'bias', 'mul', 'scale', 'scale_split', 'residual', 'periodic', 'act_residual')
 
 
@@ -232,9 +233,13 @@ def guarded(shape, dtype, device, pad_cols=8):
     return sentinel_fill(full)
 
 
-def _sentinel_touched(t):
+def sentinel_touched(t):
+    """Number of elements of the sentinel-filled tensor t that no longer hold the sentinel."""
     want = SENT_BF16 if t.element_size() == 2 else SENT_F32
     return int((t.contiguous().view(_INT[t.dtype]) != want).sum().item())
+
+
+_sentinel_touched = sentinel_touched
 
 
 def _tile_of(idx, shape):
@@ -266,7 +271,7 @@ def check_exact(name, got, expected, sentinel_regions=()):
                           f'{_tile_of(i, got.shape)}' for i in where)
         msgs.append(f'{nbad} of {got.numel()} elements differ; first: {shown}')
     for label, region in (sentinel_regions.items() if isinstance(sentinel_regions, dict) else enumerate(sentinel_regions)):
-        touched = _sentinel_touched(region.detach())
+        touched = sentinel_touched(region.detach())
         if touched:
             msgs.append(f'{touched} guard elements of region {label} overwritten')
     report(f'{"FAIL" if msgs else "ok  "} exact {name}: {got.numel()} elements'

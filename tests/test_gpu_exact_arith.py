@@ -4,7 +4,9 @@ The inputs are small integers and dyadic scales, so every fp32 operation inside 
 unique whatever the summation order: the exact value for fp32 outputs, RNE(exact value) for bf16 outputs.  Every case is
 compared with equality, and the guard regions around the output (ldc padding columns, the cls rows a row map skips, the
 tail of Csplit / C2) must be bit-unchanged.  Each dispatch branch is forced with the vtx_opts fixture; the comment on a
-case names the branch of vtx_gemm_nt (csrc/gemm_nt.hip) / vtx_gemm_tn (csrc/gemm_tn.hip) it reaches.
+case names the branch of vtx_gemm_nt (csrc/gemm_nt.hip) / vtx_gemm_tn (csrc/gemm_tn.hip) it reaches.  The 'act_residual' case
+checks its pre-activation copy exactly and the GELU output against float64 with a tolerance; the GELU value itself is pinned,
+element by element, in test_gpu_exact_gelu.py.
 """
 import functools
 

@@ -128,7 +128,12 @@ __device__ inline void gelu_parts(float x, float& cdf, float& gauss) {
   p = fmaf(p, t, -0.284496736f);
   p = fmaf(p, t, 0.254829592f);
   const float uu = u * u;
-  gauss = __builtin_amdgcn_exp2f(uu * -1.4426950408889634f);        // exp(-x^2/2)
+  // exp(-x^2/2).  v_exp_f32 flushes a subnormal result to zero, and the derivative multiplies the Gaussian by
+  // |x| / sqrt(2 pi) = 5.3 where that happens (|x| > 13.19): beyond an argument of -126 the exponential is taken 2^64
+  // higher and scaled back by a multiply, which keeps subnormals.  Every other argument sees + 0 and * 1: the same bits.
+  const float e2 = uu * -1.4426950408889634f;
+  const bool deep = e2 < -126.0f;
+  gauss = __builtin_amdgcn_exp2f(e2 + (deep ? 64.0f : 0.0f)) * (deep ? 0x1p-64f : 1.0f);
   const float q = (0.5f * p) * t;
   const float half_tail = q * gauss;                                 // 0.5 * erfc(|x|/sqrt2)
   const float upper = 1.0f - half_tail;
