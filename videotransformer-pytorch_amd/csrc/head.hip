@@ -61,6 +61,9 @@ __global__ __launch_bounds__(256) void mixup_target_kernel(const long* __restric
 
 // ---- softmax cross-entropy: one wave per row ------------------------------------------------
 // loss_row[b] = sum_c -t[b][c] * log_softmax(x[b])[c]   (soft targets)   or   -log_softmax(x[b])[label[b]]
+// -log_softmax is formed as (mx - x[c]) + log(se), the row maximum subtracted first as ATen's log_softmax does: both terms
+// round at the scale of the row's spread, so a common offset of the logits changes nothing (lse - x[c] with lse = mx + log(se)
+// rounds at the magnitude of the logits: 2.4e-4 absolute at an offset of 4096).
 __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__ x, const float* __restrict__ soft,
                                                        const long* __restrict__ labels, int B, int C, float* __restrict__ loss_row,
                                                        float* __restrict__ lse_out) {
@@ -72,17 +75,17 @@ __global__ __launch_bounds__(256) void xent_fwd_kernel(const float* __restrict__
   mx = wave_max(mx);
   float se = 0.f;
   for (int c = lane; c < C; c += 64) se += expf(xr[c] - mx);
-  const float lse = mx + logf(wave_sum(se));
+  const float lg = logf(wave_sum(se));
   float acc = 0.f;
   if (soft) {
     const float* tr = soft + (long)row * C;
-    for (int c = lane; c < C; c += 64) acc += tr[c] * (lse - xr[c]);
+    for (int c = lane; c < C; c += 64) acc += tr[c] * ((mx - xr[c]) + lg);
     acc = wave_sum(acc);
   } else {
     const long lab = labels[row];                // outside [0, C) (nn.CrossEntropyLoss's ignore_index = -100 included): not counted
-    acc = (lab >= 0 && lab < C) ? lse - xr[lab] : 0.f;
+    acc = (lab >= 0 && lab < C) ? (mx - xr[lab]) + lg : 0.f;
   }
-  if (lane == 0) { loss_row[row] = acc; lse_out[row] = lse; }
+  if (lane == 0) { loss_row[row] = acc; lse_out[row] = mx + lg; }
 }
 
 // out[0] = mean of the counted rows of rows[0..B) in a fixed order (one workgroup), out[1] = their number: with labels,
@@ -108,6 +111,8 @@ __global__ __launch_bounds__(256) void mean_rows_kernel(const float* __restrict_
 }
 
 // dx[b][c] = g * (softmax(x[b])[c] * sum_c t[b][c] - t[b][c]),  g = dloss / B  (mean reduction)
+// softmax = exp((x - mx) - log(se)) with the row's mx and se recomputed here (one more pass over a row the wave reads anyway):
+// the saved lse is rounded at the magnitude of the logits, and exp(x - lse) would carry that error times |lse| into every entry.
 __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__ x, const float* __restrict__ soft,
                                                        const long* __restrict__ labels, const float* __restrict__ lse, int B, int C,
                                                        float g, const float* __restrict__ gdev, const float* __restrict__ count,
@@ -123,15 +128,20 @@ __global__ __launch_bounds__(256) void xent_bwd_kernel(const float* __restrict__
     for (int c = lane; c < C; c += 64) a += soft[(long)row * C + c];
     ts = wave_sum(a);
   }
-  const float l = lse[row];
   const long lab = soft ? -1 : labels[row];
   if (!soft && (lab < 0 || lab >= C)) {         // not counted: no gradient
     for (int c = lane; c < C; c += 64) dx[(long)row * C + c] = 0.f;
     return;
   }
+  float mx = -INFINITY;
+  for (int c = lane; c < C; c += 64) mx = fmaxf(mx, xr[c]);
+  mx = wave_max(mx);
+  float se = 0.f;
+  for (int c = lane; c < C; c += 64) se += expf(xr[c] - mx);
+  const float lg = logf(wave_sum(se));
   for (int c = lane; c < C; c += 64) {
     const float t = soft ? soft[(long)row * C + c] : (c == lab ? 1.f : 0.f);
-    dx[(long)row * C + c] = g * (expf(xr[c] - l) * ts - t);
+    dx[(long)row * C + c] = g * (expf((xr[c] - mx) - lg) * ts - t);
   }
 }
 
