@@ -76,7 +76,8 @@ const char* vtx_last_error_string(void);
  * continuous-flow kernels, 5 = lean passes (the default, same as 0), 6 = lean passes with the first four of every tile rolled
  * into its last K tile -- 4 / 5 / 6 give identical results), "pp_cont" = 0|1 (continuous flow of the persistent GEMM: the
  * next tile's first K tiles are requested inside the current main loop; 1 by default, 0 = per-tile prologue; identical
- * results), "ln_rows" = 1 .. 4 (rows per trip of the LayerNorm forward kernel, default 3; identical results),
+ * results), "ln_rows" = 1 .. 4 (rows a wave fetches per trip of the LayerNorm forward kernel, default 3; D > 1024: always 1;
+ * identical results),
  * "attn_fused" = 0|1|2 (backward of the 33..224-token attention: kernel pair / one pass with two phases / one phase with streamed
  * operands (193..224 tokens; default); dk and dv identical, dq of 2 equal to fp32 rounding), "attn_fwd_stream" = 0|1 (forward of
  * the 193..224-token attention: workgroup per (sequence, head) / persistent with streamed K and V (default); identical results),

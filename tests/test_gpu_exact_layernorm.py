@@ -10,8 +10,8 @@ or up to 2048 (acc_fwd) workgroups of 4 waves, so 20 487 and 24 581 rows give se
 rows, one row and none; 2032 / 2033 rows are 127 / 128 partial slabs: the 4-lane and the wide partial reduce.  The forward
 kernels take ln_rows rows per trip over up to 2048 workgroups: 8193 and 32 773 rows.
 Instantiations (2100 rows, the wide reduce): NCH 1 .. 4 FULL and ragged for every entry point, NCH 6 and 8 for
-vtx_layernorm_fwd / vtx_layernorm_bwd; RES and no-RES for F32, BF16 and X32 (X32 up to D = 1024), G32; ln_fwd_kernel
-(ln_rows 1) and ln_fwd2_kernel (NR 2 .. 4).  Not run: BF16_X32 at D > 1024 (ln_bwd_kernel<bf16, 6 / 8, .., float>).
+vtx_layernorm_fwd / vtx_layernorm_bwd; RES and no-RES for F32, BF16 and X32 (X32 up to D = 1024), G32; ln_fwd2_kernel
+at NR 1 (ln_rows 1, and D > 1024) and NR 2 .. 4.  Not run: BF16_X32 at D > 1024 (ln_bwd_kernel<bf16, 6 / 8, .., float>).
 """
 import functools
 
@@ -176,7 +176,7 @@ def test_layernorm_acc_fwd_row_counts(D, rows):
 @pytest.mark.parametrize('D', L.EDGE_D)
 @pytest.mark.parametrize('kind', ['f32', 'bf16'])
 def test_layernorm_fwd_row_counts(kind, D, rows, vtx_opts):
-    """ln_rows 1 (ln_fwd_kernel: a second trip from 8193 rows) and 2 .. 4 (ln_fwd2_kernel: 32 773 rows give a second, ragged
+    """ln_fwd2_kernel under ln_rows 1 (NR 1: a second trip from 8193 rows) and 2 .. 4 (32 773 rows give a second, ragged
     trip at every NR)."""
     run_fwd(rows, D, kind, (1, 2, 3, 4), vtx_opts)
 
@@ -201,7 +201,7 @@ def test_layernorm_bwd_deterministic():
 # ------------------------------------------------------------------------------------------------ instantiations
 @pytest.mark.parametrize('D', L.INST_D + L.INST_D_WIDE)
 def test_layernorm_fwd_instantiations(D, vtx_opts):
-    """NCH 1 .. 4 FULL / ragged under ln_rows 1 .. 4; D > 1024: ln_fwd_kernel<NCH 6 / 8> whatever ln_rows says."""
+    """NCH 1 .. 4 FULL / ragged under ln_rows 1 .. 4; D > 1024: ln_fwd2_kernel<NCH 6 / 8, NR 1> whatever ln_rows says."""
     for kind in ('f32', 'bf16'):
         run_fwd(L.INST_ROWS, D, kind, (1, 2, 3, 4) if D <= 1024 else (3,), vtx_opts)
 

@@ -242,16 +242,17 @@ def parent_cases(spec):
 
 # the same in a child process that loads the library VTX_LIB names (a process loads one library)
 _PARENT_JOB = r'''
-import json, sys, torch
+import importlib, json, sys, torch
 sys.path[:0] = sys.argv[1:4]
-import test_gpu_long_attention as T
-torch.save(T.parent_cases(json.loads(sys.argv[5])), sys.argv[4])
+cases = getattr(importlib.import_module(sys.argv[5]), sys.argv[6])
+torch.save(cases(json.loads(sys.argv[7])), sys.argv[4])
 '''
 
 
-def assert_parent_bit_for_bit(spec, tmp_path, what):
-    """Every tensor of parent_cases(spec) from this build equals, bit for bit, what the library named by VTX_PARENT_LIB (built
-    from the parent commit) computes; skipped when VTX_PARENT_LIB names no file."""
+def parent_build_cases(cases, spec, tmp_path):
+    """cases(spec) -- a module-level function of a test module, {case: [CPU tensors]} -- as the library named by VTX_PARENT_LIB
+    (built from the parent commit) computes it in a child process; skipped when VTX_PARENT_LIB names no file.  Returns that
+    dict and the library's file name; this process is asserted to run another library."""
     import vtx
     parent = os.environ.get('VTX_PARENT_LIB', '')
     if not parent or not os.path.isfile(parent):
@@ -259,12 +260,19 @@ def assert_parent_bit_for_bit(spec, tmp_path, what):
         pytest.skip('VTX_PARENT_LIB does not name a library built from the parent commit')
     out = str(tmp_path / 'parent.pt')
     env = dict(os.environ, VTX_LIB=os.path.abspath(parent))
-    for k in ('VTX_ATTN_F32', 'VTX_ATTN_LONG', 'VTX_ATTN_VALU'):
+    for k in ('VTX_ATTN_F32', 'VTX_ATTN_LONG', 'VTX_ATTN_VALU', 'VTX_LN_ROWS', 'VTX_GEMM_TN'):
         env.pop(k, None)
     subprocess.run([sys.executable, '-c', _PARENT_JOB, ROOT, os.path.join(ROOT, 'videotransformer-pytorch_amd'),
-                    os.path.join(ROOT, 'tests'), out, json.dumps(spec)], check=True, env=env, timeout=600)
+                    os.path.join(ROOT, 'tests'), out, cases.__module__, cases.__name__, json.dumps(spec)], check=True, env=env, timeout=600)
     want = torch.load(out)
     assert os.path.realpath(vtx.load()._name) != os.path.realpath(parent), 'this process runs the parent library itself'
+    return want, os.path.basename(parent)
+
+
+def assert_parent_bit_for_bit(spec, tmp_path, what):
+    """Every tensor of parent_cases(spec) from this build equals, bit for bit, what the library named by VTX_PARENT_LIB (built
+    from the parent commit) computes; skipped when VTX_PARENT_LIB names no file."""
+    want, parent = parent_build_cases(parent_cases, spec, tmp_path)
     got = parent_cases(spec)
     assert sorted(got) == sorted(want) and len(got) == len(spec['contig']) + len(spec['space'])
     names = ('out', 'lse', 'dqkv', 'dqkv_cls')
@@ -274,7 +282,7 @@ def assert_parent_bit_for_bit(spec, tmp_path, what):
             assert a.dtype == b.dtype and a.shape == b.shape
             assert torch.isfinite(a.float()).any(), f'{case}: {name} was never written'
             assert torch.equal(_bits(a), _bits(b)), f'{case}: {name} of {what} differs from the parent'
-    report(f'ok   {what} bit-identical to {os.path.basename(parent)} on {len(got)} shapes: ' + ', '.join(got))
+    report(f'ok   {what} bit-identical to {parent} on {len(got)} shapes: ' + ', '.join(got))
 
 
 def test_long_is_the_parent_bit_for_bit(attn_long, tmp_path):

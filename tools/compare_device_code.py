@@ -5,7 +5,8 @@
 For every csrc/_obj/<file>.o of both trees: extract the device code object (as tools/check_isa.py does), hash its .text section
 and list its kernel symbols.  Prints one line per file (sha256 of .text, other / this) and exits 1 when a .text section or a
 symbol list differs.  The whole code object is NOT compared: it carries the build directory, .text does not.  When the
-sections differ but every kernel's own bytes agree (instantiations emitted in another order) the line says so.
+sections differ but every kernel's own bytes agree (instantiations emitted in another order) the line says so; when the symbol
+lists differ (a kernel was added or retired) it names, of the kernels both builds have, the ones whose bytes differ.
 """
 import hashlib
 import os
@@ -56,7 +57,9 @@ def main():
         tb, kb = device_code(os.path.join(this, OBJ, n))
         ha, hb = hashlib.sha256(ta).hexdigest()[:16], hashlib.sha256(tb).hexdigest()[:16]
         if sorted(ka) != sorted(kb):
-            verdict = 'SYMBOLS DIFFER: ' + ' '.join(sorted(set(ka) ^ set(kb)))
+            common = sorted(set(ka) & set(kb))
+            verdict = ('SYMBOLS DIFFER: ' + ' '.join(sorted(set(ka) ^ set(kb))) + f'; OF THE {len(common)} IN BOTH, DIFFERENT: ' +
+                       (' '.join(k for k in common if ka[k] != kb[k]) or 'none'))
         elif ta == tb:
             verdict = 'identical'
         elif all(ka[k] == kb[k] for k in ka):

@@ -136,8 +136,9 @@ def timesformer_joint(batch=8, precision='bf16'):
 
 
 if __name__ == '__main__':
-    for a in [a for a in sys.argv[1:] if '=' in a]:      # option=value, e.g. attn_long=0
-        vtx.set_option(*a.split('='))
+    for a in [a for a in sys.argv[1:] if '=' in a]:      # option=value, e.g. attn_long=0; stream=fp32: vtx.set_stream (bf16 configs)
+        k, v = a.split('=')
+        vtx.set_stream(v) if k == 'stream' else vtx.set_option(k, v)
     which = [a for a in sys.argv[1:] if '=' not in a] or ['hog', 'vivit', 'tsf16', 'tsfl96']
     if 'tsfjoint' in which:
         timesformer_joint(precision='fp32' if 'fp32' in which else 'bf16')
