@@ -50,18 +50,26 @@ def is_pow2(n):
 # ------------------------------------------------------------------------------------------------ layout
 class Layout:
     """Logical row m -> physical row base + m + (m // n) * skip of a flat [phys, ld] buffer (ops.rowmap(n, skip, base); the
-    default is ops.tokmap(TOK_N) on a [B, 1 + N, ld] tensor whose last clip may be partly filled) plus two trailing rows."""
+    default is ops.tokmap(TOK_N) on a [B, 1 + N, ld] tensor whose last clip may be partly filled) plus two trailing rows.
+    With `table` (an exact_tab.TabLayout of `rows` logical rows) the rows are placed and gathered through the table's index
+    vector base + m + tab[m // grp] instead, the buffer has the table layout's row count, and rowmap() is ops.tabmap(...)."""
 
-    def __init__(self, rows, n=TOK_N, skip=1, base=1):
+    def __init__(self, rows, n=TOK_N, skip=1, base=1, table=None):
+        self.table = table
+        if table is not None:
+            assert rows == table.M
+            n, skip, base = table.grp, table.max_step, table.base
         self.rows, self.n, self.skip, self.base = rows, n, skip, base
         m = torch.arange(rows)
-        self.idx = base + m + (m // n) * skip
-        self.phys = int(self.idx[-1]) + 3
+        self.idx = base + m + (m // n) * skip if table is None else table.rows
+        self.phys = int(self.idx[-1]) + 3 if table is None else table.phys
         self.clips = (rows + n - 1) // n
         self.unmapped = torch.ones(self.phys, dtype=torch.bool)
         self.unmapped[self.idx] = False
 
     def rowmap(self, ops):
+        if self.table is not None:
+            return self.table.rowmap(ops)
         return ops.rowmap(self.n, self.skip, self.base)
 
     def place(self, vals, dtype=torch.float32, seed=0, pad=PAD):

@@ -246,13 +246,15 @@ def test_bench_stack_vs_oracle_with_partial_ffn_drop(prec, tol, gtol):
 
 
 @pytest.mark.parametrize('dtype', [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize('B,rows_per,D,Hd', [(5, 37, 128, 256), (6, 1569, 768, 3072)])
+@pytest.mark.parametrize('B,rows_per,D,Hd', [(5, 37, 128, 256), (5, 257, 128, 256), (4, 256, 128, 256), (6, 1569, 768, 3072)])
 def test_ffn_skips_dropped_clips(dtype, B, rows_per, D, Hd):
     """DropPath at the FFN drops whole clips (reference transformer.py:34-42,543).  FFNFn runs the block on the kept clips
     only -- table row maps in LayerNorm, the fc2 epilogue's residual / result rows and the gradient gather (the large case
-    goes through the persistent GEMM's residual-block flow) -- and must give what computing every clip and multiplying by
+    goes through the persistent GEMM's residual-block flow, the two small ones with 257 / 256 rows per clip through the
+    non-persistent GEMM families: M < 2048) -- and must give what computing every clip and multiplying by
     zero gives: the same stream values bit for bit, the same input gradient, parameter gradients up to the fp32 summation
-    order of the weight-gradient reduction."""
+    order of the weight-gradient reduction.  (5, 37, ..) is the "too short to compact" case: clips of fewer than 256 rows keep
+    the compute-and-multiply-by-zero path, so it compares that path with itself."""
     from vtx import functions as F_
     g = torch.Generator().manual_seed(11)
     r = lambda *sh, sc=1.0: (torch.randn(*sh, generator=g) * sc)              # noqa: E731
@@ -263,6 +265,13 @@ def test_ffn_skips_dropped_clips(dtype, B, rows_per, D, Hd):
     patterns = [[1, 3], [0], [B - 1], list(range(B)), list(range(1, B)), []]
     for dropped in patterns:
         host = torch.tensor([0.0 if i in dropped else c for i in range(B)], dtype=torch.float32)
+        probe = host.to(DEV)
+        probe._vtx_host = host
+        plan = F_._compaction_plan(probe, B, rows_per, probe.device)
+        if rows_per < 256:
+            assert plan is None, f'clips of {rows_per} rows must not compact'
+        elif 0 < len(dropped) < B:
+            assert plan is not None and plan[:2] == (B - len(dropped), len(dropped)), f'B={B} rows={rows_per} dropped={dropped}: no compaction plan'
         res = []
         for compact in (False, True, True):               # the compact path twice: it must be deterministic
             F_.set_compact_droppath(compact)
