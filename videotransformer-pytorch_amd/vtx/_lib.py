@@ -186,8 +186,24 @@ AUG_SIGNATURES = {
     'vtx_clip_jitter_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
 }
 
+# libvtx_randaug.so (include/vtx_randaug.h, csrc/randaug.hip): RandAugment, the third library.  Must list every symbol the header declares.
+RANDAUG_LIB_PATH = os.environ.get('VTX_RANDAUG_LIB', os.path.join(_PKG, 'libvtx_randaug.so'))
+PW_NONE, PW_POSTERIZE, PW_SOLARIZE = 0, 1, 2
+RANDAUG_SIGNATURES = {
+    'vtx_randaug_version': (ci, []),
+    'vtx_randaug_last_error_string': (C.c_char_p, []),
+    'vtx_clip_warp_nearest_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    'vtx_clip_sharpness_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, vp, vp]),
+    'vtx_clip_pointwise_u8': (ci, [ci, ci, ci, ci, vp, vp, vp]),
+    'vtx_clip_autocontrast_workspace': (sz, [ci, ci]),
+    'vtx_clip_autocontrast_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, sz, vp]),
+    'vtx_clip_equalize_workspace': (sz, [ci, ci]),
+    'vtx_clip_equalize_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, sz, vp]),
+}
+
 _lib = None
 _aug = None
+_randaug = None
 
 
 class VtxError(RuntimeError):
@@ -223,6 +239,34 @@ def aug_call(name, *args):
     rc = getattr(load_aug(), name)(*args)
     if rc != 0:
         aug_check(rc, name)
+
+
+def load_randaug():
+    """Load libvtx_randaug.so and bind every symbol of include/vtx_randaug.h.  Raises if anything is missing: there is no fallback."""
+    global _randaug
+    if _randaug is not None:
+        return _randaug
+    if not os.path.isfile(RANDAUG_LIB_PATH):
+        raise VtxError(f'libvtx_randaug.so not found at {RANDAUG_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(RANDAUG_LIB_PATH)
+    for name, (res, args) in RANDAUG_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_randaug.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _randaug = lib
+    return lib
+
+
+def randaug_call(name, *args):
+    lib = load_randaug()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_randaug_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 
 def load():

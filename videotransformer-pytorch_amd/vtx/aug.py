@@ -2,14 +2,21 @@
 (data_transform.py:495-574) that run before ToTensor + Normalize, on decoded uint8 clips [B,T,H,W,3].
 
     aug = vtx.aug.ClipAugment(img_size=224)             # RandomResizedCrop (bicubic) + flip + ColorJitter(0.4, 0.4, 0.4)
+    aug = vtx.aug.ClipAugment(img_size=224, auto_augment='rand-m9-mstd0.5-inc1')      # ... + RandAugment() instead of the jitter
     vtx.set_input_normalization(mean, std)              # ToTensor + Normalize: fused into the patch gather
     out = model(aug(clip_u8.cuda()))
 
 What is random is drawn on the host (``sample_params``: torchvision's draws restated, under a ``torch.Generator``), once per
 clip -- every frame of a clip gets the same crop, flip and colour factors, as the reference's single call on a [T,C,H,W]
-tensor does.  The pixels are touched by libvtx_aug.so only (csrc/aug.hip, include/vtx_aug.h): ``vtx_clip_resample_u8`` and ``vtx_clip_jitter_u8``.
+tensor does.  The pixels are touched by libvtx_aug.so (csrc/aug.hip, include/vtx_aug.h): ``vtx_clip_resample_u8`` and
+``vtx_clip_jitter_u8``, and, under ``auto_augment``, by libvtx_randaug.so (csrc/randaug.hip, include/vtx_randaug.h).
 
-Not built: ThreeCrop, RandAugment (``auto_augment``), RandomGrayscale, hue jitter and the temporal sampling of the dataset.
+``auto_augment``: as in the reference (data_transform.py:520-521) any truthy value selects ``RandAugment()`` with its defaults
+(two ops of fourteen at magnitude bin 9 of 31, nearest interpolation, no fill) and the content of the string is ignored.  What
+is restated is torchvision's tensor path as of 0.13 .. 0.20; torchvision is not a dependency and no version is pinned.
+
+Not built: ThreeCrop, RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations, and the temporal sampling of
+the dataset.
 """
 import math
 from collections import namedtuple
@@ -20,8 +27,15 @@ import torch
 from . import ops
 
 #: one clip's draws: crop box (rows top .. top+height, columns left .. left+width of the source frame), the flip coin and the
-#: colour ops in the order they are applied (0 brightness, 1 contrast, 2 saturation) with their factors
-ClipDraw = namedtuple('ClipDraw', 'top left height width flip ops factors')
+#: colour ops in the order they are applied (0 brightness, 1 contrast, 2 saturation) with their factors; ``randaug``: the
+#: (op index, signed magnitude) pairs of RandAugment in the order they are applied (``sample_randaug``), () without auto_augment
+ClipDraw = namedtuple('ClipDraw', 'top left height width flip ops factors randaug', defaults=[()])
+
+#: torchvision's RandAugment._augmentation_space, in its order (the op index is the position)
+RANDAUG_OPS = ('Identity', 'ShearX', 'ShearY', 'TranslateX', 'TranslateY', 'Rotate', 'Brightness', 'Color', 'Contrast', 'Sharpness',
+               'Posterize', 'Solarize', 'AutoContrast', 'Equalize')
+_RA_SIGNED = frozenset(range(1, 10))
+_RA_JITTER = {6: 0, 7: 2, 8: 1}          # Brightness, Color, Contrast -> op of vtx_clip_jitter_u8 (0 brightness, 2 saturation, 1 contrast)
 
 
 def _uniform(lo, hi, generator):
@@ -75,13 +89,85 @@ def _jitter_ranges(color_jitter):
     return out
 
 
-def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, generator=None):
+def _randaug_magnitudes(out_hw, magnitude, bins):
+    """RandAugment._augmentation_space at one bin: the magnitude of each of the 14 ops for (height, width) frames (float32
+    linspaces read with float(), as torchvision does)."""
+    H, W = int(out_hw[0]), int(out_hw[1])
+    at = lambda lo, hi: float(torch.linspace(lo, hi, bins)[magnitude])
+    shear, colour = at(0.0, 0.3), at(0.0, 0.9)
+    posterize = float((8 - (torch.arange(bins) / ((bins - 1) / 4)).round().int())[magnitude])
+    return (0.0, shear, shear, at(0.0, 150.0 / 331.0 * W), at(0.0, 150.0 / 331.0 * H), at(0.0, 30.0), colour, colour, colour, colour,
+            posterize, at(255.0, 0.0), 0.0, 0.0)
+
+
+def _draw_randaug(mags, num_ops, generator):
+    """RandAugment.forward's draws for one clip: per op randint(14), and randint(2) for the sign if the op is signed."""
+    rec = []
+    for _ in range(num_ops):
+        op = int(torch.randint(len(RANDAUG_OPS), (1,), generator=generator))
+        mag = mags[op]
+        if op in _RA_SIGNED and int(torch.randint(2, (1,), generator=generator)):
+            mag *= -1.0
+        rec.append((op, mag))
+    return tuple(rec)
+
+
+def sample_randaug(B, out_hw, num_ops=2, magnitude=9, num_magnitude_bins=31, generator=None):
+    """The draws of torchvision's RandAugment(num_ops, magnitude, num_magnitude_bins) for B clips of ``out_hw`` = (height, width)
+    frames (the size RandAugment sees: it runs behind the crop): per clip a tuple of (op index into RANDAUG_OPS, signed magnitude)
+    in the order of application.  One draw per clip: every frame shares it."""
+    num_ops, magnitude, bins = int(num_ops), int(magnitude), int(num_magnitude_bins)
+    if num_ops < 0 or bins < 2 or not 0 <= magnitude < bins:
+        raise ValueError(f'sample_randaug: num_ops={num_ops} >= 0, 0 <= magnitude={magnitude} < num_magnitude_bins={bins} expected')
+    mags = _randaug_magnitudes(out_hw, magnitude, bins)
+    return [_draw_randaug(mags, num_ops, generator) for _ in range(int(B))]
+
+
+def _inverse_affine(center, angle, translate, shear):
+    """torchvision's _get_inverse_affine_matrix at scale 1 (degrees in, float64)."""
+    rot, sx, sy = math.radians(angle), math.radians(shear[0]), math.radians(shear[1])
+    cx, cy = center
+    tx, ty = translate
+    a = math.cos(rot - sy) / math.cos(sy)
+    b = -math.cos(rot - sy) * math.tan(sx) / math.cos(sy) - math.sin(rot)
+    c = math.sin(rot - sy) / math.cos(sy)
+    d = -math.sin(rot - sy) * math.tan(sx) / math.cos(sy) + math.cos(rot)
+    m = [d, -b, 0.0, -c, a, 0.0]
+    m[2] += m[0] * (-cx - tx) + m[1] * (-cy - ty)
+    m[5] += m[3] * (-cx - tx) + m[4] * (-cy - ty)
+    m[2] += cx
+    m[5] += cy
+    return m
+
+
+def randaug_theta(op, mag, H, W):
+    """The six entries of the inverse matrix RandAugment._apply_op hands to the warp for a geometric op (1 .. 5) of signed magnitude
+    ``mag`` on H x W frames: shear about center=[0, 0] (the frame's corner, (-W/2, -H/2) from its middle), translation by int(mag)
+    pixels, rotation by ``mag`` degrees through F.rotate (angle -mag)."""
+    if op in (1, 2):
+        sh = math.degrees(math.atan(mag))
+        return _inverse_affine((-W * 0.5, -H * 0.5), 0.0, (0.0, 0.0), (sh, 0.0) if op == 1 else (0.0, sh))
+    if op in (3, 4):
+        return _inverse_affine((0.0, 0.0), 0.0, (float(int(mag)), 0.0) if op == 3 else (0.0, float(int(mag))), (0.0, 0.0))
+    if op == 5:
+        return _inverse_affine((0.0, 0.0), -mag, (0.0, 0.0), (0.0, 0.0))
+    raise ValueError(f'randaug_theta: op {op} is not geometric')
+
+
+def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, generator=None, auto_augment=None, out_hw=None):
     """The draws of RandomResizedCrop + RandomHorizontalFlip + ColorJitter for B clips of ``src_hw`` = (height, width) frames:
-    a list of B ``ClipDraw``.  Host code; all randomness comes from ``generator`` (None = torch's default CPU generator)."""
+    a list of B ``ClipDraw``.  Host code; all randomness comes from ``generator`` (None = torch's default CPU generator).
+    A truthy ``auto_augment`` draws RandAugment() for ``out_hw`` frames in place of the ColorJitter (``ops`` and ``factors`` stay
+    empty), clip by clip: crop, flip, RandAugment."""
     height, width = int(src_hw[0]), int(src_hw[1])
     scale = tuple(scale or (0.08, 1.0))
     ratio = tuple(ratio or (3. / 4., 4. / 3.))
     ranges = _jitter_ranges(color_jitter)
+    mags = None
+    if auto_augment:
+        if out_hw is None:
+            raise ValueError('sample_params: auto_augment needs out_hw, the frame size behind the crop')
+        ranges, mags = None, _randaug_magnitudes(out_hw, 9, 31)
     draws = []
     for _ in range(int(B)):
         top, left, h, w = _crop_box(height, width, scale, ratio, generator)
@@ -94,11 +180,11 @@ def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4
                 if fn < 3 and fac[fn] is not None:
                     jops.append(fn)
                     jfac.append(fac[fn])
-        draws.append(ClipDraw(top, left, h, w, flip, tuple(jops), tuple(jfac)))
+        draws.append(ClipDraw(top, left, h, w, flip, tuple(jops), tuple(jfac), _draw_randaug(mags, 2, generator) if mags else ()))
     return draws
 
 
-def _check_draws(draws, B, Hs, Ws):
+def _check_draws(draws, B, Hs, Ws, num_ops=2):
     if len(draws) != B:
         raise ValueError(f'params: {len(draws)} records for {B} clips')
     for d in draws:
@@ -106,6 +192,13 @@ def _check_draws(draws, B, Hs, Ws):
             raise ValueError(f'params: crop box (top {d.top}, left {d.left}, {d.height}x{d.width}) outside the {Hs}x{Ws} frame')
         if len(d.ops) != len(d.factors) or len(d.ops) > 3 or len(set(d.ops)) != len(d.ops) or any(o not in (0, 1, 2) for o in d.ops):
             raise ValueError(f'params: colour ops {d.ops} / factors {d.factors}: each of 0, 1, 2 at most once, one factor per op')
+        ra = d.randaug
+        if len(ra) > num_ops or (ra and d.ops):
+            raise ValueError(f'params: RandAugment record {ra}: at most {num_ops} ops, and none beside colour-jitter ops')
+        for rec in ra:
+            if (len(rec) != 2 or isinstance(rec[0], bool) or not isinstance(rec[0], (int, np.integer)) or not 0 <= rec[0] < len(RANDAUG_OPS)
+                    or not math.isfinite(rec[1])):
+                raise ValueError(f'params: RandAugment record {rec}: (op index 0 .. {len(RANDAUG_OPS) - 1}, finite magnitude)')
 
 
 def _tables(specs, mode, antialias):
@@ -121,8 +214,52 @@ def _tables(specs, mode, antialias):
     return tuple(np.stack([c[i] for c in cut]) for i in range(3))
 
 
+def _randaug_plan(draws, H, W):
+    """The launches of the RandAugment records, slot by slot: [(kernel family, [host records])].  Within a slot every clip drew one
+    op, so the batch splits by family and each family needed is launched once, with ``sel`` (or per-clip records) naming the
+    clips that drew it; Identity launches nothing."""
+    B = len(draws)
+    plan = []
+    for s in range(max(len(d.randaug) for d in draws)):
+        theta = np.tile(np.array([1, 0, 0, 0, 1, 0], dtype=np.float32), (B, 1))
+        sharp, jf = np.zeros((B, 2), dtype=np.float32), np.zeros((B, 6), dtype=np.float32)
+        jo, pw = np.zeros((B, 4), dtype=np.int32), np.zeros((B, 2), dtype=np.int32)
+        sel = {k: np.zeros(B, dtype=np.int32) for k in ('warp', 'sharpness', 'autocontrast', 'equalize')}
+        for b, d in enumerate(draws):
+            if s >= len(d.randaug):
+                continue
+            op, mag = int(d.randaug[s][0]), float(d.randaug[s][1])
+            if 1 <= op <= 5:
+                theta[b], sel['warp'][b] = randaug_theta(op, mag, H, W), 1
+            elif op in _RA_JITTER:
+                jo[b, :2] = (1, _RA_JITTER[op])
+                jf[b, 0], jf[b, 3] = 1.0 + mag, 1.0 - (1.0 + mag)                # 1 - r in float64, then rounded: torchvision's _blend
+            elif op == 9:
+                sharp[b], sel['sharpness'][b] = (1.0 + mag, 1.0 - (1.0 + mag)), 1
+            elif op == 10:
+                pw[b] = (1, int(mag))
+            elif op == 11:
+                pw[b] = (2, math.ceil(mag))                                     # v >= 178.5 for integers: v >= 179
+            elif op == 12:
+                sel['autocontrast'][b] = 1
+            elif op == 13:
+                sel['equalize'][b] = 1
+        if sel['warp'].any():
+            plan.append(('warp', [theta, sel['warp']]))
+        if sel['sharpness'].any():
+            plan.append(('sharpness', [sharp, sel['sharpness']]))
+        if jo.any():
+            plan.append(('jitter', [jo, jf]))
+        if pw.any():
+            plan.append(('pointwise', [pw]))
+        for k in ('autocontrast', 'equalize'):
+            if sel[k].any():
+                plan.append((k, [sel[k]]))
+    return plan
+
+
 def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
-    """Tables (and colour records) to the device in one copy, then the kernels."""
+    """Tables (and colour / RandAugment records) to the device in one copy, then the kernels."""
     xf, xc, xw = _tables(xspecs, mode, antialias)
     yf, yc, yw = _tables(yspecs, mode, antialias)
     parts = [xf, xc, xw.view(np.int32), yf, yc, yw.view(np.int32)]
@@ -137,6 +274,9 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
             jf[b, :len(d.ops)] = d.factors
             jf[b, 3:3 + len(d.ops)] = [1.0 - float(f) for f in d.factors]      # in float64, then rounded: torchvision's _blend
         parts += [jo, jf.view(np.int32)]
+    plan = _randaug_plan(draws, out_hw[0], out_hw[1]) if draws is not None and any(d.randaug for d in draws) else []
+    for _, recs in plan:
+        parts += [r.view(np.int32) for r in recs]
     dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.device)
     views, at = [], 0
     for p in parts:
@@ -146,6 +286,22 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
     out = ops.clip_resample_u8(clips, out_hw, (views[0], views[1], f32(views[2])), (views[3], views[4], f32(views[5])))
     if jitter:
         ops.clip_jitter_u8_(out, views[6], f32(views[7]))
+    at = 8 if jitter else 6
+    for kind, recs in plan:
+        v = views[at:at + len(recs)]
+        at += len(recs)
+        if kind == 'warp':
+            out = ops.clip_warp_nearest_u8(out, f32(v[0]), v[1])
+        elif kind == 'sharpness':
+            out = ops.clip_sharpness_u8(out, f32(v[0]), v[1])
+        elif kind == 'jitter':
+            ops.clip_jitter_u8_(out, v[0], f32(v[1]))
+        elif kind == 'pointwise':
+            ops.clip_pointwise_u8_(out, v[0])
+        elif kind == 'autocontrast':
+            ops.clip_autocontrast_u8_(out, v[0])
+        else:
+            ops.clip_equalize_u8_(out, v[0])
     return out
 
 
@@ -157,9 +313,12 @@ def _check_clips(clips):
 class ClipAugment:
     """``transforms_train`` (data_transform.py:495-531) without its ToTensor + Normalize tail, per clip on the device.  Takes
     that function's arguments and defaults; ``scale=(0.5, 1.0), color_jitter=None`` is the ``mim`` branch of
-    data_trainer.py:61-63.  uint8 CUDA [B,T,Hs,Ws,3] -> uint8 CUDA [B,T,img_size,img_size,3]."""
+    data_trainer.py:61-63; a truthy ``auto_augment`` (the -auto_augment flag, data_trainer.py:82) puts RandAugment() in the place
+    of the ColorJitter, whatever the string says.  uint8 CUDA [B,T,Hs,Ws,3] -> uint8 CUDA [B,T,img_size,img_size,3]."""
 
-    def __init__(self, img_size=224, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, interpolation='bicubic', antialias=False):
+    def __init__(self, img_size=224, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, interpolation='bicubic', antialias=False,
+                 auto_augment=None):
+        self.auto_augment = auto_augment
         self.out_hw = (int(img_size), int(img_size)) if not isinstance(img_size, (tuple, list)) else (int(img_size[0]), int(img_size[1]))
         self.scale, self.ratio, self.hflip, self.color_jitter = scale, ratio, float(hflip), color_jitter
         ops._resample_mode(interpolation)
@@ -169,7 +328,8 @@ class ClipAugment:
     def __call__(self, clips_u8, generator=None, params=None):
         B, Hs, Ws = _check_clips(clips_u8)
         if params is None:
-            params = sample_params(B, (Hs, Ws), self.scale, self.ratio, self.hflip, self.color_jitter, generator)
+            params = sample_params(B, (Hs, Ws), self.scale, self.ratio, self.hflip, self.color_jitter, generator,
+                                   auto_augment=self.auto_augment, out_hw=self.out_hw)
         _check_draws(params, B, Hs, Ws)
         H, W = self.out_hw
         xs = [(Ws, d.left, d.width, W, d.flip, 0, W) for d in params]

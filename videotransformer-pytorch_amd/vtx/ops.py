@@ -679,6 +679,83 @@ def clip_jitter_u8_(clip, jit_ops, factors):
     return clip
 
 
+# ------------------------------------------------- RandAugment (csrc/randaug.hip -> libvtx_randaug.so)
+def _check_record(t, B, n, dtype, what):
+    need_cuda(t)
+    if t.dtype != dtype or tuple(t.shape) != ((B, n) if n else (B,)) or not t.is_contiguous():
+        raise TypeError(f'{what}: {str(dtype).replace("torch.", "")} [{B}{f",{n}" if n else ""}] contiguous device tensor expected, '
+                        f'got {t.dtype} {tuple(t.shape)}')
+
+
+def _randaug_out_of_place(name, cls, src, rec, rec_n, sel, out, nbytes_per):
+    _check_u8_clip(src, name)
+    B, T, H, W, _ = src.shape
+    _check_record(rec, B, rec_n, torch.float32, name)
+    _check_record(sel, B, 0, torch.int32, name)
+    if not src.is_contiguous():
+        raise TypeError(f'{name}: contiguous clip required')
+    if out is None:
+        out = torch.empty_like(src)
+    else:
+        _check_u8_clip(out, name)
+        if out is src or out.data_ptr() == src.data_ptr():
+            raise ValueError(f'{name}: out of place only (out is the source clip)')
+        if out.shape != src.shape or not out.is_contiguous():
+            raise TypeError(f'{name}: out must be a contiguous uint8 {tuple(src.shape)} clip')
+    with _timed(cls, nbytes=nbytes_per * src.numel(), key=f'{B}x{T} {H}x{W}'):
+        _lib.randaug_call('vtx_' + name, B, T, H, W, ptr(src), ptr(out), ptr(rec), ptr(sel), stream())
+    return out
+
+
+def clip_warp_nearest_u8(src, theta, sel, out=None):
+    """uint8 [B,T,H,W,3] -> a new clip (or ``out``): the nearest-neighbour affine warp of RandAugment's ShearX/Y, TranslateX/Y and
+    Rotate.  theta float32 [B,6]: the inverse matrix of torchvision's _get_inverse_affine_matrix; sel int32 [B]: 0 = copy the clip."""
+    return _randaug_out_of_place('clip_warp_nearest_u8', 'clip_warp', src, theta, 6, sel, out, 2)
+
+
+def clip_sharpness_u8(src, factors, sel, out=None):
+    """uint8 [B,T,H,W,3] -> a new clip (or ``out``): torchvision's adjust_sharpness.  factors float32 [B,2] = {r, 1 - r} (1.0 - r
+    formed in float64 and rounded on its own); sel int32 [B]: 0 = copy the clip."""
+    return _randaug_out_of_place('clip_sharpness_u8', 'clip_sharpness', src, factors, 2, sel, out, 2)
+
+
+def _in_place_clip(clip, what):
+    _check_u8_clip(clip, what)
+    if not clip.is_contiguous():
+        raise TypeError(f'{what}: contiguous clip required (in place)')
+    return clip.shape[:4]
+
+
+def clip_pointwise_u8_(clip, pw_ops):
+    """In place: pw_ops int32 [B,2] = {0 none | 1 posterize | 2 solarize, argument} (bits to keep | integer threshold)."""
+    B, T, H, W = _in_place_clip(clip, 'clip_pointwise_u8_')
+    _check_record(pw_ops, B, 2, torch.int32, 'clip_pointwise_u8_')
+    with _timed('clip_pointwise', nbytes=2 * clip.numel(), key=f'{B}x{T} {H}x{W}'):
+        _lib.randaug_call('vtx_clip_pointwise_u8', B, T, H, W, ptr(clip), ptr(pw_ops), stream())
+    return clip
+
+
+def _randaug_two_pass(name, cls, clip, sel):
+    B, T, H, W = _in_place_clip(clip, name + '_')
+    _check_record(sel, B, 0, torch.int32, name + '_')
+    lib = _lib.load_randaug()
+    nbytes = getattr(lib, f'vtx_{name[:-3]}_workspace')(B, T)
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=clip.device)
+    with _timed(cls, nbytes=3 * clip.numel(), key=f'{B}x{T} {H}x{W}'):
+        _lib.randaug_call(f'vtx_{name}', B, T, H, W, ptr(clip), ptr(sel), ptr(ws), nbytes, stream())
+    return clip
+
+
+def clip_autocontrast_u8_(clip, sel):
+    """In place: torchvision's autocontrast per frame and channel on the clips with sel[b] != 0 (sel int32 [B])."""
+    return _randaug_two_pass('clip_autocontrast_u8', 'clip_autocontrast', clip, sel)
+
+
+def clip_equalize_u8_(clip, sel):
+    """In place: torchvision's equalize per frame and channel on the clips with sel[b] != 0 (sel int32 [B])."""
+    return _randaug_two_pass('clip_equalize_u8', 'clip_equalize', clip, sel)
+
+
 # ------------------------------------------------- clip-batch mixing, accuracy (csrc/head.hip)
 def mixup_batch_(x, lam):
     """In place: x[b] = x[b]*lam + x[B-1-b]*(1-lam) on a contiguous fp32 [B, ...] batch (reference mixup.py:112-113)."""
