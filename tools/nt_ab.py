@@ -3,7 +3,9 @@
     python tools/nt_ab.py M N K kind option=v1,v2[,v3] [rounds] [launches]
 
 kind: plain | scale | residual | mul | gelu2.  Every round times `launches` back-to-back launches of each option value
-(HIP events on the launch stream), values interleaved; prints median / min per value and the ratio to the first one.
+(HIP events on the launch stream), values interleaved; prints mean +- standard deviation over the rounds, median, min and
+max per value and the ratio of the means to the first one.  A difference of two means counts when it exceeds the spread
+(min .. max) of the rounds of either value.
 """
 import os
 import sys
@@ -52,9 +54,11 @@ def main():
     base = None
     for v in vals:
         t = sorted(times[v])
-        med, mn = t[len(t) // 2], t[0]
-        base = base or med
-        print(f'{M}x{N}x{K} {kind:8s} {opt}={v}: median {med:8.1f} us  min {mn:8.1f} us  ({2.0 * M * N * K / med / 1e6:7.1f} TF/s)  x{med / base:.4f}')
+        med, mn, mx, mean = t[len(t) // 2], t[0], t[-1], sum(t) / len(t)
+        sd = (sum((x - mean) ** 2 for x in t) / max(len(t) - 1, 1)) ** 0.5
+        base = base or mean
+        print(f'{M}x{N}x{K} {kind:8s} {opt}={v}: mean {mean:8.1f} +- {sd:4.1f} us  median {med:8.1f}  min {mn:8.1f}  max {mx:8.1f}  '
+              f'({2.0 * M * N * K / mean / 1e6:7.1f} TF/s)  x{mean / base:.4f}')
 
 
 if __name__ == '__main__':

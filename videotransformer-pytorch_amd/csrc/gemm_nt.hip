@@ -412,6 +412,10 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     long long* __restrict__ trace, int dbg, EpiParams ep) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   bf16raw* lds = reinterpret_cast<bf16raw*>(smem);
+  // register block flow (continuous kernels whose epilogue reads a 128 x 64 block per wave, residual or multiplier): the block goes
+  // from HBM straight into registers behind the main loop -- see blk_load below
+  constexpr bool PREG = CONT && PRE != PRE_NONE;
+  static_assert(!CONT || PRE != PRE_DGELU, "the GELU' input kernel is never continuous");
   amap.tab = nullptr;                            // the A map is in closed form (vtx_gemm_nt checks it): no table code below
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -478,8 +482,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     return publish(v);
   };
   static_assert(!CONT || EPI2, "the continuous flows belong to the read-ahead epilogue");
-  constexpr bool CF = CONT && PRE == PRE_NONE;   // continuous operand flow: the epilogue leaves the ring alone
-  constexpr bool PF = CONT && PRE != PRE_NONE;   // residual-block flow: the ring receives the epilogue's block (see below)
   // Request addresses = a wave-uniform 64-bit base per operand (first byte of the tile's A rows / B rows, in scalar
   // registers, advanced by scalar adds) + a 32-bit byte offset per lane and piece: the DMA instruction takes both
   // (saddr + voffset), so a request costs no vector ALU work inside the MFMA sections and the eight per-lane
@@ -635,7 +637,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     }
 #define PP_ISS_COND(kind_, ktv_, ex_) if (ex_) issue(kind_, ktv_)          /* only K tiles of this tile */
 #define PP_ISS_ALWAYS(kind_, ktv_, ex_) issue(kind_, ktv_)                 /* continuous flow: the next tile's follow */
-#define PP_ISS_PRE(kind_, ktv_, ex_) if (ex_) issue(kind_, ktv_); else pre_slot(kind_, ktv_)   /* ... or the residual block */
 
   // Continuous flow (CONT: epilogues that leave the operand ring alone).  The K tiles of successive tiles form ONE
   // stream through the ring: the requests that the last two K tiles of a tile have no use for -- exactly the seven
@@ -661,9 +662,9 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
   const int tend = xcount;
   if (t >= tend) { check_out(); return; }
   int t_next = tend, t_nn = tend;
-  if constexpr (CF) t_next = next_tile();
+  if constexpr (CONT) t_next = next_tile();
   int pending = 0;                               // index drawn ahead by lane 0 of the workgroup
-  if (EPI2 && !CF && tid == 0) pending = atomicAdd(my_ctr, 1);
+  if (EPI2 && !CONT && tid == 0) pending = atomicAdd(my_ctr, 1);
   set_tile(t, 0);
   m0 = m0s; n0 = n0s;
   prologue();
@@ -676,7 +677,13 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     bf16x8 fa[2][4], fb0[4], fb1[4];
-    const bool more_c = CF && t_next < tend;     // continuous flow: another tile follows this one
+    if constexpr (PREG) {                          // fragment addresses per tile from an opaque lane id: four registers that are not live
+      int lf = lane;                               // through the epilogue, where the block's 64 registers sit beside the accumulators
+      asm volatile("" : "+v"(lf));
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) fr[ks] = (lf & 31) * PP_BK + (((2 * ks + (lf >> 5)) ^ (((lf & 31) >> 1) & 7)) << 3);
+    }
+    const bool more_c = CONT && t_next < tend;     // continuous flow: another tile follows this one
     // ---- epilogue state of this tile.  epi_head() fills the store addressing (after the main loop -- or in front of its last K
     // tile when the epilogue ROLLS: the first four passes of a lean tile, rows 0 .. 63 of the wave's block, which are final
     // after P2 of the last K tile, then run inside P3 / P4 of that K tile, in the shadow of its last sixteen MFMAs)
@@ -772,7 +779,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     // successor in this workgroup run inside its last K tile.  (One code path on purpose: with a rolling AND a non-rolling copy of
     // the last K tile behind the same loop hipcc splits the accumulator tuples at the join and spills 160 - 220 registers.)
     constexpr bool ROLLK = ROLL;
-    static_assert(!ROLL || (CF && VTX_PP_BF16_STAGE && PRE == PRE_NONE && !HAS_SC && !HAS_ACT), "rolling: the plain continuous flow only");
+    static_assert(!ROLL || (CONT && VTX_PP_BF16_STAGE && PRE == PRE_NONE && !HAS_SC && !HAS_ACT), "rolling: the plain continuous flow only");
     // Waits are per region and counted: each names the region the NEXT phase reads and leaves every
     // younger request in flight (2 DMA instructions per region; issue order A0 B0 B1 A1 per K tile).
     stamp(0);
@@ -782,7 +789,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     PP_BAR();
     stamp(1);
     if (wr == 1) PP_BAR();                        // group 1 runs one barrier behind
-    if constexpr (CF) {
+    if constexpr (CONT) {
       // bias of this wave's 64 columns -> staging slice (+256 B): lane l fetches column en0 + l;
       // DropPath scales of its 128 rows -> staging slice (+512 B): lane l fetches the scales of rows l and 64 + l
       auto bias_dma = [&]() {
@@ -881,58 +888,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           PP_KTILE(kt + 1 < nk, kt + 2 < nk, kt + 1 < nk, kt + 2 < nk, true, PP_ISS_COND, if (kt == 0) bias_dma();, , , )
         }
       }
-    } else if constexpr (PF) {
-      // Residual-block flow.  The epilogue's 128 x 64 block per wave (residual, GELU' input or multiplier: 128 KB per
-      // workgroup) used to be requested after the main loop into the idle ring -- every CU of the chip asking for its
-      // 128 KB at the same moment and waiting ~5.6 us for it -- and the next tile's operands could only be requested
-      // after the passes had read it.  Now the block takes the request slots the last two K tiles have no use for:
-      // slot (kind, K tile nk or nk + 1) = ring region s = 4 (ktv - nk) + kind, freed by the main loop in exactly that
-      // order, receives rows [16 s, 16 s + 16) of every wave's block (each wave its own 2 KB of the region, through its
-      // own two DMA instructions); regions 6 and 7 share the last slot.  Pass p of the epilogue reads region p, and the
-      // wave then requests ITS part of the next tile's operand region into the 2 KB it has just read: the standard
-      // seven-region prologue, spread over the passes, with no barrier (no wave touches another wave's part).
-      // Addresses as in set_tile(): a wave-uniform 64-bit base (the block row that holds the tile's first row) + 32-bit
-      // lane offsets; row maps with at most one group boundary per tile (the launcher routes others, and periodic
-      // residuals, to the per-tile flow).  Split rows (no residual) and rows beyond M read the tile's first row.
-      constexpr bool pres = PRE == PRE_RES;
-      const int pen = n0 + wc * 64 + (lane & 7) * 8;
-      const unsigned penc2 = pen < ep.N ? (unsigned)pen * 2u : 0u;
-      const unsigned pld2 = (unsigned)(pres ? ep.ldr : ep.ld_dgelu) * 2u;
-      // rows without a block row (beyond M; split rows, which take no residual) read the last row that has one
-      const int lastv = min(ep.M - 1, (pres && ep.split_row > 0) ? ep.split_row - 1 : 0x7fffffff);
-      const int m0c = min(m0, lastv);              // a tile of split rows only: everything reads row `lastv`
-      const TileMap prm = make_tile_map(ep.rmap, m0c);
-      const long pfirst = pres ? tile_map_row_u(prm, ep.rmap, m0c) : (long)m0c;
-      const char* pbase = reinterpret_cast<const char*>(pres ? ep.R : ep.dgelu_in) + pfirst * (long)pld2;
-      const int pbl = (pres && ep.rmap.grp > 0) ? prm.bound - m0c : 0x7fffffff;         // local row at which the skip starts
-      const int pskip = pres ? prm.skip : 0;       // (the tile's own step in the table form)
-      const int plast = lastv - m0c;               // >= 0
-      const int pl0 = (m0 - m0c) + wr * 128 + (lane >> 3);
-      auto pre_piece = [&](int j, bf16raw* dst) {  // rows 8j .. 8j+7 of the block: lane -> row 8j + lane/8, chunk lane%8
-        const int l = min(pl0 + 8 * j, plast);
-        const int lr = l + (l >= pbl ? pskip : 0);
-        const char* b = pbase;
-        asm volatile("" : "+s"(b));
-        dma16_nt(reinterpret_cast<const bf16raw*>(b + ((unsigned)lr * pld2 + penc2)), dst);
-      };
-      auto pre_slot = [&](int kind, int ktv) {
-        const int s = (ktv - nk) * 4 + kind;
-        bf16raw* dst = lds + ((ktv & 1) ^ par) * PP_BUF + kind * PP_REGION + wave * 1024;
-        pre_piece(2 * s, dst);
-        pre_piece(2 * s + 1, dst + 512);
-        if (s == 6) {                              // region 7 = (A1, K tile nk + 1): read in P3, free from P4 on
-          bf16raw* dst7 = lds + ((ktv & 1) ^ par) * PP_BUF + 3 * PP_REGION + wave * 1024;
-          pre_piece(14, dst7);
-          pre_piece(15, dst7 + 512);
-        }
-      };
-      // Every slot carries two requests as in the steady state: steady-state wait counts -- except P4 of the last K
-      // tile, whose steady-state wait names the regions of "K tile nk": block pieces the main loop does not need, which
-      // come from HBM with every CU asking for its 128 KB in the same few microseconds (requests return in order, so the
-      // wait would stall on them: measured +2.8 us per tile).  All operand requests precede all block requests.
-      for (int kt = 0; kt < nk; ++kt) {
-        PP_KTILE(kt + 1 < nk, kt + 2 < nk, true, true, kt + 1 < nk, PP_ISS_PRE, , , , )
-      }
     } else {
       for (int kt = 0; kt < nk; ++kt) {
         PP_KTILE(kt + 1 < nk, kt + 2 < nk, kt + 1 < nk, kt + 2 < nk, true, PP_ISS_COND, , , , )
@@ -965,7 +920,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // not an atomic round trip; the draw for the tile after it goes out below and returns under the
       // epilogue's own load latency.
       bool more = more_c;
-      if constexpr (!CF) {
+      if constexpr (!CONT) {
         t = publish(pending);
         more = t < tend;
       }
@@ -977,10 +932,11 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // leaves at store LATENCY: measured 14 us per tile, 24..28 us with a residual, against a 17 us main loop at
       // K = 768.)
       //   bias: 8 registers; DropPath scales of the lane's 16 rows: 16 registers;
-      //   residual / GELU' input of the wave's 128 x 64 block: 16 KB -- too many registers beside the 128
-      //   accumulators, so it goes through LDS: 16 LDS-DMA pieces into the wave's slice of the (idle) operand
-      //   ring.  The next tile's prologue then has to wait for the passes to finish reading it (one extra
-      //   barrier; ~1.5 us of prologue latency exposed instead of ~10 us of store latency).
+      //   residual / GELU' input of the wave's 128 x 64 block: 16 KB.  Per-tile flow: it goes through LDS, 16 LDS-DMA
+      //   pieces into the wave's slice of the (idle) operand ring; the next tile's prologue then has to wait for the
+      //   passes to finish reading it (one extra barrier; ~1.5 us of prologue latency exposed instead of ~10 us of store
+      //   latency).  Continuous flow: the ring belongs to the next tile's operands, the block goes into 64 registers
+      //   (blk_load below).
       // an opaque copy of the lane id for everything below: the epilogue's lane constants (staging / block read addresses, row and
       // column of the lane, ...) are then recomputed per tile -- some twenty vector instructions -- instead of being hoisted out
       // of the tile loop and kept in registers through the main loop (which spilled once the lean passes were added)
@@ -993,7 +949,46 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       constexpr bool HAS_PRE = PRE != PRE_NONE, pre_res = PRE == PRE_RES;
       bf16raw* const pre_lds = lds + wave * (128 * 64);          // [128][64] bf16, row r at r * 64: le-linear per piece
       if (!rolled) epi_head();                       // (a rolling epilogue did it in front of the last K tile)
-      if constexpr (HAS_PRE && !PF) {
+      // Register block flow.  The operand flow above has left the ring to the next tile's K tiles 0 and 1, so the wave's 128 x 64
+      // block goes straight into 64 registers (the A / B fragment registers are dead here): 16 pieces, piece j = rows 8j .. 8j+7
+      // (lane -> row 8j + lane/8, chunk lane%8 -- what the F stage of pass j/2 consumes), each ONE global_load_dwordx4 at a scalar
+      // base + 32-bit lane offset, all sixteen older than the tile's first store.  The loads are inline asm: hipcc does not track
+      // their results (a tracked one is waited for with vmcnt(0) while an LDS-DMA is in flight, and the next tile's operands
+      // always are); pass p waits for its two pieces itself with vmcnt(14 - 2p) -- the YOUNGER pieces only: loads retire in order
+      // among themselves, stores counted on top can only make the wait longer -- and ties the registers to that wait ("+v"), so
+      // no use moves above it and no copy of them crosses the loop's back-edge.  Addresses as in set_tile(): a wave-uniform 64-bit base
+      // (the block row that holds the tile's first row) + 32-bit lane offsets; row maps with at most one group boundary per tile, the
+      // tile's own step in the table form (the launcher routes others, and periodic residuals, to the per-tile flow); a column chunk
+      // beyond N reads chunk 0.
+      // (PP_BLOAD stands at the head of BOTH pass forms, lean and general, instead of once in front of them: with one load and a
+      // wait per form hipcc tied each form's wait to a COPY of the registers, made before the wait -- seen in the ISA)
+      [[maybe_unused]] u32x4 blk[16];
+      auto blk_load = [&]() {
+        const unsigned penc2 = col_ok ? (unsigned)en * 2u : 0u;
+        const unsigned pld2 = (unsigned)(pre_res ? ep.ldr : ep.ld_dgelu) * 2u;
+        // rows without a block row (beyond M; split rows, which take no residual) read the last row that has one
+        const int lastv = min(ep.M - 1, (pre_res && ep.split_row > 0) ? ep.split_row - 1 : 0x7fffffff);
+        const int m0c = min(tile_m0, lastv);         // a tile of split rows only: everything reads row `lastv`
+        const TileMap prm = make_tile_map(ep.rmap, m0c);
+        const long pfirst = pre_res ? tile_map_row_u(prm, ep.rmap, m0c) : (long)m0c;
+        const char* pbase = reinterpret_cast<const char*>(pre_res ? ep.R : ep.dgelu_in) + pfirst * (long)pld2;
+        asm volatile("" : "+s"(pbase));
+        const int pbl = (pre_res && ep.rmap.grp > 0) ? prm.bound - m0c : 0x7fffffff;      // local row at which the skip starts
+        const int pskip = pre_res ? prm.skip : 0;    // (the tile's own step in the table form)
+        const int plast = lastv - m0c;               // >= 0
+        const int pl0 = (tile_m0 - m0c) + wr * 128 + (le >> 3);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+          const int l = min(pl0 + 8 * j, plast);
+          const int lr = l + (l >= pbl ? pskip : 0);
+          const unsigned vo = (unsigned)lr * pld2 + penc2;
+          asm volatile("global_load_dwordx4 %0, %1, %2 nt" : "=v"(blk[j]) : "v"(vo), "s"(pbase) : "memory");
+        }
+      };
+#define PP_BLOAD() if constexpr (PREG) blk_load()
+#define PP_BLK(p_, u_) (PREG ? blk[2 * (p_) + (u_)] : pre[u_])
+#define PP_BWAIT(p_) if constexpr (PREG) { asm volatile("s_waitcnt vmcnt(%2)" : "+v"(blk[2 * (p_)]), "+v"(blk[2 * (p_) + 1]) : "n"(14 - 2 * (p_)) : "memory"); }
+      if constexpr (HAS_PRE && !CONT) {
         const bf16raw* const pre_base = reinterpret_cast<const bf16raw*>(pre_res ? ep.R : ep.dgelu_in);
         const long pre_ld = pre_res ? ep.ldr : ep.ld_dgelu;
         const TileMap rm = make_tile_map(ep.rmap, tile_m0);
@@ -1014,7 +1009,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // bias in the ACCUMULATOR layout (a le owns one column of each 32-column half: 2 registers instead of the 8 a
       // row-vector le needs, and 64 adds per tile instead of 128); same fp32 add, same result
       if (ep.bias && !rolled) {
-        if constexpr (CF) {                        // landed in the staging slice during K tile 0 (see above)
+        if constexpr (CONT) {                        // landed in the staging slice during K tile 0 (see above)
           asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:128\n\ts_waitcnt lgkmcnt(0)"
                        : "=&v"(bcol[0]), "=&v"(bcol[1]) : "v"(bias_rd) : "memory");
         } else {
@@ -1029,8 +1024,8 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // lean passes: the 128 row scales of the wave's block stay in TWO registers (le l: rows l and 64 + l); a pass fetches its
       // two values per le with ds_bpermute_b32 (no LDS storage: the staging slice is full) inside its read batch
       float scl[2] = {0.f, 0.f};
-      if constexpr (HAS_SC && CF) {                // landed in the staging slice during K tile 0: row r of the block at word 128 + r
-        if (lean) {
+      if constexpr (HAS_SC && CONT) {                // landed in the staging slice during K tile 0: row r of the block at word 128 + r
+        if (lean || PREG) {                        // (register block flow: the general passes fetch from these two as well)
           const unsigned scl_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) + 512 + le * 4);
           asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:256\n\ts_waitcnt lgkmcnt(0)"
                        : "=&v"(scl[0]), "=&v"(scl[1]) : "v"(scl_rd) : "memory");
@@ -1048,7 +1043,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
                      : "v"(sc_rd) : "memory");
         }
       }
-      if constexpr (HAS_SC && !CF) {
+      if constexpr (HAS_SC && !CONT) {
         auto scale_of = [&](int ml) -> float {
           if (ml >= ep.M) ml = ep.M - 1;
           const bool split = ep.split_row > 0 && ml >= ep.split_row;
@@ -1066,7 +1061,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
             for (int u = 0; u < 2; ++u) sc[p][u] = scale_of(er + 16 * p + 8 * u);
         }
       }
-      if constexpr (!CF) {
+      if constexpr (!CONT) {
         if (more && tid == 0) pending = atomicAdd(my_ctr, 1);
         // one wait for all of it; the empty asm statements make the loaded registers "used" here, so that hipcc's own
         // wait for them lands before the prologue's DMA requests and not (as vmcnt(0)) behind them
@@ -1082,9 +1077,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         if constexpr (!HAS_PRE) {
           if (more) { set_tile(t, 0); m0 = m0s; n0 = n0s; prologue(); }   // ring is free: the next tile's first 7 regions land under the passes
         }
-        if constexpr (PF) {
-          if (more) set_tile(t, (long)nk * (PP_BK * 2));   // the passes below request its K tiles 0 and 1 as stream positions nk, nk + 1
-        }
       }
       stamp(5);
       // The staged rows (and the residual rows) are read back with inline-asm ds_read + lgkmcnt(0) in ONE statement:
@@ -1093,23 +1085,32 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       const unsigned stg_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) +
                                                                     ((le >> 3) * PP_STG_LD + (le & 7) * 8) * 4);
       const unsigned pre_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(pre_lds) + le * 16);
-      // residual-block flow: pass p reads this wave's 2 KB of ring region p (buffer pa for p < 4, the other one after)
-      const unsigned pf_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(lds + wave * 1024) + le * 16);
-      const int pa = (nk & 1) ^ par;
+      const int kpar = nk & 1;                       // CONT: the ring buffer of a tile's K tile 0 alternates when the K tiles are odd in number
 #define PP_EPI2(p_, mi_, half_)                                                                         \
       {                                                                                                 \
-        const int col = le & 31, rhalf = (le >> 5) * 4;                                             \
+        /* register block flow: the lane's row / column terms from an opaque lane id PER PASS, or hipcc forms the 64-bit store */ \
+        /* addresses of all eight passes ahead of the first one and spills them beside the 64 block registers */ \
+        int lp = le;                                                                                    \
+        if constexpr (PREG) asm volatile("" : "+v"(lp));                                                \
+        const int enp = PREG ? en0 + (lp & 7) * 8 : en, erp = PREG ? em0 + (lp >> 3) : er;              \
+        const bool cokp = PREG ? enp < ep.N : col_ok;                                                   \
+        const int col = lp & 31, rhalf = (lp >> 5) * 4;                                                 \
         if (dbg != 3) {                                                                                 \
         _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int r = 0; r < 8; ++r)  \
             stg[((r & 3) + 8 * (r >> 2) + rhalf) * PP_STG_LD + ni * 32 + col] = acc[mi_][ni][8 * (half_) + r] + bcol[ni]; \
-        } else { stg[le] = acc[mi_][0][8 * (half_)] + acc[mi_][1][8 * (half_) + 7]; }                 \
+        } else { stg[lp] = acc[mi_][0][8 * (half_)] + acc[mi_][1][8 * (half_) + 7]; }                 \
         lgkm0();                                                                                        \
         __builtin_amdgcn_wave_barrier();                                                                \
         f32x4 s00, s01, s10, s11;                                                                       \
         u32x4 pre[2];                                                                                   \
-        if constexpr (HAS_PRE) {                                                                        \
-          const unsigned prd__ = PF ? pf_rd + (unsigned)((((p_) < 4 ? pa : pa ^ 1) * PP_BUF + ((p_) & 3) * PP_REGION) * 2) \
-                                    : pre_rd + 2 * (p_) * 1024;                                         \
+        PP_BWAIT(p_)                                                                                    \
+        [[maybe_unused]] float scp[2];               /* register block flow: the pass's two row scales from the two registers of the lean passes */ \
+        if constexpr (HAS_SC && PREG)                                                                   \
+          asm volatile("ds_bpermute_b32 %0, %2, %3 offset:%4\n\tds_bpermute_b32 %1, %2, %3 offset:%5\n\ts_waitcnt lgkmcnt(0)" \
+                       : "=&v"(scp[0]), "=&v"(scp[1]) : "v"((unsigned)(lp >> 3) * 4u), "v"((p_) < 4 ? scl[0] : scl[1]), \
+                         "n"(((16 * (p_)) & 63) * 4), "n"(((16 * (p_) + 8) & 63) * 4) : "memory");     \
+        if constexpr (HAS_PRE && !PREG) {                                                               \
+          const unsigned prd__ = pre_rd + 2 * (p_) * 1024;                                              \
           asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:16\n\t"                       \
                        "ds_read_b128 %2, %6 offset:2048\n\tds_read_b128 %3, %6 offset:2064\n\t"         \
                        "ds_read_b128 %4, %7\n\tds_read_b128 %5, %7 offset:1024\n\t"                     \
@@ -1127,48 +1128,46 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           v[0][j] = s00[j]; v[0][4 + j] = s01[j]; v[1][j] = s10[j]; v[1][4 + j] = s11[j];               \
         }                                                                                               \
         _Pragma("unroll") for (int u = 0; u < 2; ++u) {                                                 \
-          const int m = er + 16 * (p_) + 8 * u;                                                         \
-          const bool ok = col_ok && m < ep.M && dbg != 2;                                               \
+          const int m = erp + 16 * (p_) + 8 * u;                                                        \
+          const bool ok = cokp && m < ep.M && dbg != 2;                                                 \
           const bool split = ep.split_row > 0 && m >= ep.split_row;                                     \
           if constexpr (HAS_ACT) {                                                                      \
             if (ep.act == 2) {                     /* GELU, second output = its derivative */          \
               float gp[8];                                                                              \
               _Pragma("unroll") for (int j = 0; j < 8; ++j) gelu_erf_both(v[u][j], v[u][j], gp[j]);     \
-              if (ok) PP_ST8(reinterpret_cast<bf16raw*>(ep.C2) + (long)m * ep.ldc2 + en, gp);        \
+              if (ok) PP_ST8(reinterpret_cast<bf16raw*>(ep.C2) + (long)m * ep.ldc2 + enp, gp);          \
             } else {                                                                                    \
-              if (ep.C2 && ok) store8(reinterpret_cast<bf16raw*>(ep.C2) + (long)m * ep.ldc2 + en, v[u]); \
+              if (ep.C2 && ok) store8(reinterpret_cast<bf16raw*>(ep.C2) + (long)m * ep.ldc2 + enp, v[u]); \
               _Pragma("unroll") for (int j = 0; j < 8; ++j) v[u][j] = gelu_erf(v[u][j]);                \
             }                                                                                           \
           }                                                                                             \
           if constexpr (PRE == PRE_MUL) {          /* the block holds gelu'(x) itself */                \
-            const uint32_t w[4] = {pre[u][0], pre[u][1], pre[u][2], pre[u][3]};                         \
+            const u32x4 w = PP_BLK(p_, u);                                                              \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                             \
               v[u][2 * j] *= __uint_as_float(w[j] << 16);                                               \
               v[u][2 * j + 1] *= __uint_as_float(w[j] & 0xffff0000u);                                   \
             }                                                                                           \
           }                                                                                             \
           if constexpr (PRE == PRE_DGELU) {                                                             \
-            const uint32_t w[4] = {pre[u][0], pre[u][1], pre[u][2], pre[u][3]};                         \
+            const u32x4 w = PP_BLK(p_, u);                                                              \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                             \
               v[u][2 * j] *= gelu_erf_grad(__uint_as_float(w[j] << 16));                                \
               v[u][2 * j + 1] *= gelu_erf_grad(__uint_as_float(w[j] & 0xffff0000u));                    \
             }                                                                                           \
           }                                                                                             \
-          if constexpr (HAS_SC) { _Pragma("unroll") for (int j = 0; j < 8; ++j) v[u][j] *= sc[p_][u]; } \
+          if constexpr (HAS_SC && !PREG) { _Pragma("unroll") for (int j = 0; j < 8; ++j) v[u][j] *= sc[p_][u]; } \
+          if constexpr (HAS_SC && PREG) { _Pragma("unroll") for (int j = 0; j < 8; ++j) v[u][j] *= scp[u]; } \
           if (pre_res && !split) {                                                                      \
-            const uint32_t w[4] = {pre[u][0], pre[u][1], pre[u][2], pre[u][3]};                         \
+            const u32x4 w = PP_BLK(p_, u);                                                              \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                             \
               v[u][2 * j] += __uint_as_float(w[j] << 16);                                               \
               v[u][2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);                                   \
             }                                                                                           \
           }                                                                                             \
           if (ok) {                                                                                     \
-            if (split) store8(reinterpret_cast<bf16raw*>(ep.Csplit) + (long)(m - ep.split_row) * ep.ldsplit + en, v[u]); \
-            else PP_ST8(reinterpret_cast<bf16raw*>(ep.C) + tile_map_row(cm, ep.cmap, m) * ep.ldc + en, v[u]); \
+            if (split) store8(reinterpret_cast<bf16raw*>(ep.Csplit) + (long)(m - ep.split_row) * ep.ldsplit + enp, v[u]); \
+            else PP_ST8(reinterpret_cast<bf16raw*>(ep.C) + tile_map_row(cm, ep.cmap, m) * ep.ldc + enp, v[u]); \
           }                                                                                             \
-        }                                                                                               \
-        if constexpr (PF) {                        /* region p_ is read: it takes the next tile's operands */ \
-          if ((p_) < 7 && more) issue((p_) & 3, nk + ((p_) >> 2));                                      \
         }                                                                                               \
       }
       // Plain epilogue (nothing to read, no activation, no row scale: result = bf16(acc + bias)): the pass stages PAIRS OF
@@ -1224,6 +1223,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           u32x4 pre[2];
           float scu[2] = {1.f, 1.f};                   // the pass's two row scales (rows le / 8 and + 8 of its 16)
           const unsigned bp_addr = (unsigned)(ln >> 3) * 4u;
+          PP_BLOAD();
 #define PP_LW(mi_, half_) if (ep.bias) { PP_LW_(mi_, half_, true) } else { PP_LW_(mi_, half_, false) }
 #define PP_LW_(mi_, half_, B_)                                                                          \
           {                                                                                             \
@@ -1241,9 +1241,8 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
             }                                                                                           \
           }
 #define PP_LR(p_)                                                                                       \
-          if constexpr (HAS_PRE) {                                                                      \
-            const unsigned prd__ = PF ? pf_rd + (unsigned)((((p_) < 4 ? pa : pa ^ 1) * PP_BUF + ((p_) & 3) * PP_REGION) * 2) \
-                                      : pre_rd + 2 * (p_) * 1024;                                       \
+          if constexpr (HAS_PRE && !PREG) {                                                             \
+            const unsigned prd__ = pre_rd + 2 * (p_) * 1024;                                            \
             asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:16\n\t"                     \
                          "ds_read_b128 %2, %6 offset:2048\n\tds_read_b128 %3, %6 offset:2064\n\t"       \
                          "ds_read_b128 %4, %7\n\tds_read_b128 %5, %7 offset:1024"                       \
@@ -1258,11 +1257,12 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
                          : "=&v"(scu[0]), "=&v"(scu[1]) : "v"(bp_addr), "v"((p_) < 4 ? scl[0] : scl[1]),   \
                            "n"(((16 * (p_)) & 63) * 4), "n"(((16 * (p_) + 8) & 63) * 4) : "memory")
 #define PP_LWAITF(n_)                                                                                   \
-          if constexpr (HAS_PRE) { PP_LWAIT(n_, "+v"(s00), "+v"(s01), "+v"(s10), "+v"(s11), "+v"(pre[0]), "+v"(pre[1]), "+v"(scu[0]), "+v"(scu[1])); } \
+          if constexpr (HAS_PRE && !PREG) { PP_LWAIT(n_, "+v"(s00), "+v"(s01), "+v"(s10), "+v"(s11), "+v"(pre[0]), "+v"(pre[1]), "+v"(scu[0]), "+v"(scu[1])); } \
           else { PP_LWAIT(n_, "+v"(s00), "+v"(s01), "+v"(s10), "+v"(s11), "+v"(scu[0]), "+v"(scu[1])); }
 #define PP_LF(p_)                                                                                       \
           {                                                                                             \
             _Pragma("clang fp contract(off)")        /* scale, then residual: two roundings as in the general passes (bit-identical) */ \
+            PP_BWAIT(p_)                             /* register block flow: this pass's two pieces have landed */ \
             float v[2][8];                                                                              \
             _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                             \
               v[0][j] = s00[j]; v[0][4 + j] = s01[j]; v[1][j] = s10[j]; v[1][4 + j] = s11[j];           \
@@ -1275,7 +1275,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
                 st16_nt_s(lean_c2b + (long)(16 * (p_)) * ldc2b, vg0 + (u ? 8u * ldc2b : 0u), pack8(gp)); \
               }                                                                                         \
               if constexpr (PRE == PRE_MUL) {        /* the block holds gelu'(x) itself */              \
-                const uint32_t w[4] = {pre[u][0], pre[u][1], pre[u][2], pre[u][3]};                     \
+                const u32x4 w = PP_BLK(p_, u);                                                          \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                         \
                   v[u][2 * j] *= __uint_as_float(w[j] << 16);                                           \
                   v[u][2 * j + 1] *= __uint_as_float(w[j] & 0xffff0000u);                               \
@@ -1283,7 +1283,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
               }                                                                                         \
               if constexpr (HAS_SC) { _Pragma("unroll") for (int j = 0; j < 8; ++j) v[u][j] *= scu[u]; } \
               if constexpr (pre_res) {               /* no split rows in a lean block */                \
-                const uint32_t w[4] = {pre[u][0], pre[u][1], pre[u][2], pre[u][3]};                     \
+                const u32x4 w = PP_BLK(p_, u);                                                          \
                 _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                         \
                   v[u][2 * j] += __uint_as_float(w[j] << 16);                                           \
                   v[u][2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);                               \
@@ -1292,9 +1292,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
               const unsigned voff = vf0 + (u ? 8u * ldcb : 0u) +                                        \
                                     (((ln >> 3) + 8 * u >= lean_lb - 16 * (p_)) ? lean_skipb : 0u);   \
               st16_nt_s(base, voff, pack8(v[u]));                                                       \
-            }                                                                                           \
-            if constexpr (PF) {                      /* region p_ is read (the wait above): it takes the next tile's operands */ \
-              if ((p_) < 7 && more) issue((p_) & 3, nk + ((p_) >> 2));                                  \
             }                                                                                           \
           }
           PP_LW(0, 0) PP_LR(0);
@@ -1356,12 +1353,16 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         PP_EPI2B(4, 2, 0) PP_EPI2B(5, 2, 1) PP_EPI2B(6, 3, 0) PP_EPI2B(7, 3, 1)
 #undef PP_EPI2B
       } else {
+        PP_BLOAD();
         PP_EPI2(0, 0, 0) PP_EPI2(1, 0, 1) PP_EPI2(2, 1, 0) PP_EPI2(3, 1, 1)
         PP_EPI2(4, 2, 0) PP_EPI2(5, 2, 1) PP_EPI2(6, 3, 0) PP_EPI2(7, 3, 1)
       }
 #undef PP_EPI2
+#undef PP_BWAIT
+#undef PP_BLOAD
+#undef PP_BLK
       stamp(6);
-      if constexpr (HAS_PRE && !PF) {
+      if constexpr (HAS_PRE && !CONT) {
         __builtin_amdgcn_s_barrier();               // every wave has read its residual block: the ring may be refilled
         if (more) { set_tile(t, 0); m0 = m0s; n0 = n0s; prologue(); }
       }
@@ -1370,17 +1371,15 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       if (!more) break;
       if constexpr (CONT) {                         // the next tile's K tiles 0 and 1 are in the ring / on their way
         abase += (long)nk * (PP_BK * 2); bbase += (long)nk * (PP_BK * 2);
-        if constexpr (CF) {
-          // every (pass, half-row) group of this wave had a row inside M and the wave a column inside N: NST stores went
-          // out (rows em0 + 8 g + [0, 8), g = 0 .. 15; a store with an empty execution mask is not issued); the timeline and
-          // the store-free diagnostic mode add or drop vector memory operations
-          const bool second = !HAS_ACT || ep.act == 2 || ep.C2 != nullptr;
-          relax = em0 + 120 < ep.M && en0 < ep.N && second && trace == nullptr && (dbg == 0 || dbg == 4 || dbg == 5 || dbg == 6) && nk >= 3;
-          prev_rolled = rolled;
-        }
+        // every (pass, half-row) group of this wave had a row inside M and the wave a column inside N: NST stores went
+        // out (rows em0 + 8 g + [0, 8), g = 0 .. 15; a store with an empty execution mask is not issued); the timeline and
+        // the store-free diagnostic mode add or drop vector memory operations
+        const bool second = !HAS_ACT || ep.act == 2 || ep.C2 != nullptr;
+        relax = em0 + 120 < ep.M && en0 < ep.N && second && trace == nullptr && (dbg == 0 || dbg == 4 || dbg == 5 || dbg == 6) && nk >= 3;
+        prev_rolled = rolled;
         m0 = m0s; n0 = n0s;
-        par ^= nk & 1;
-        if constexpr (CF) { t = t_next; t_next = t_nn; }
+        par ^= kpar;
+        t = t_next; t_next = t_nn;
       }
     }
   }
@@ -1394,7 +1393,6 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
 #undef PP_PF
 #undef PP_ISS_COND
 #undef PP_ISS_ALWAYS
-#undef PP_ISS_PRE
 #undef PP_READ_A
 #undef PP_READ_B
 #undef PP_MMA
@@ -1436,12 +1434,11 @@ static int launch_pp(const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t st
     return launch_pp_t<true, PRE_DGELU, false, false, false>(d, ep, st, cfg);
   }
   if (d->R) {
-    // residual-block flow: no periodic residual, a row map with at most one group boundary per tile, 32-bit offsets
+    // register block flow (continuous): no periodic residual, a row map with at most one group boundary per tile, 32-bit offsets
     const bool pf = cont && d->r_period <= 0 && (d->rmap.grp <= 0 || d->rmap.grp >= 256) && d->rmap.skip >= 0 &&
                     (256L + (d->rmap.skip > 0 ? d->rmap.skip : 0)) * d->ldr * 2 < (1L << 31);
     if (!pf) return sc ? launch_pp_t<true, PRE_RES, true, false, false>(d, ep, st, cfg) : launch_pp_t<true, PRE_RES, false, false, false>(d, ep, st, cfg);
-    if (sc) return cont ? launch_pp_t<true, PRE_RES, true, false, true>(d, ep, st, cfg) : launch_pp_t<true, PRE_RES, true, false, false>(d, ep, st, cfg);
-    return cont ? launch_pp_t<true, PRE_RES, false, false, true>(d, ep, st, cfg) : launch_pp_t<true, PRE_RES, false, false, false>(d, ep, st, cfg);
+    return sc ? launch_pp_t<true, PRE_RES, true, false, true>(d, ep, st, cfg) : launch_pp_t<true, PRE_RES, false, false, true>(d, ep, st, cfg);
   }
   if (sc) return cont ? launch_pp_t<true, PRE_NONE, true, false, true>(d, ep, st, cfg) : launch_pp_t<true, PRE_NONE, true, false, false>(d, ep, st, cfg);
   // rolling epilogue (pp_epi = 6; NOT the default: measured on the three plain shapes of a layer, interleaved same-process A/B,
