@@ -26,12 +26,241 @@
 // run by ONE persistent kernel for up to 224 tokens (all four operand tiles stay in LDS: one pass over HBM,
 // attn_bwd_fused_mfma_kernel) and by two kernels (each with two tiles in LDS) for 225..256 tokens or option attn_fused=0;
 // the two forms are bit-identical.  FLOPs per (sequence, head): fwd 4*Lp^2*64, bwd 14*Lp^2*64 (incl. recompute).
+//
+// Layout of this file: the tile arithmetic first, each body ONCE (fwd_query_tile, score_pair, dq_ds / dq_mask_keys /
+// dq_accumulate, dkv_probs / dkv_accumulate, row_delta, the destination rows, the LDS-DMA request); then the kernels, which
+// own the schedules -- workgroup per item (forward, dq, dk / dv), one pass (attn_bwd_fused_mfma_kernel), streamed
+// (attn_bwd_stream_mfma_kernel, attn_fwd_stream_mfma_kernel) -- and call those bodies; then the short-sequence kernels.
 #include "attn_common.h"
 
 namespace vtx {
 
-__device__ inline long m_in_row(const AttnP& p, int s, int i) { return in_row(p, s, i); }
-__device__ inline long m_out_row(const AttnP& p, int s, int i) { return out_row(p, s, i); }
+// ------------------------------------------------------------------- the tile bodies, each written once
+// Every kernel of the 33..256-token family below is a schedule (who owns which tile, what is prefetched, where the barriers
+// are) around these steps.  The workgroup-per-item, one-pass and streamed forms of a pass are bit-identical because they call
+// the same step: same products, same order per accumulator.  All of them are inlined; a trip count that has to be a
+// compile-time constant is a template parameter.
+
+// st = X[row0 .. row0 + 31] . a, dp = Y[row0 .. row0 + 31] . b over the four 16-column steps of head_dim 64 (X, Y: swizzled
+// LDS tiles, a / b: the lane's row fragments): S^T and dP^T of the dq side (K, V against Q, dO), S and dP of the dk / dv side
+// (Q, dO against K, V).
+__device__ inline void score_pair(const bf16raw* X, const bf16raw* Y, int row0, const bf16x8 (&a)[4], const bf16x8 (&b)[4],
+                                  const FragOff& fo, f32x16& st, f32x16& dp) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(X, row0, 0, fo), a[0], zero, 0, 0, 0);
+  dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Y, row0, 0, fo), b[0], zero, 0, 0, 0);
+#pragma unroll
+  for (int ks = 1; ks < 4; ++ks) {
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(X, row0, ks, fo), a[ks], st, 0, 0, 0);
+    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Y, row0, ks, fo), b[ks], dp, 0, 0, 0);
+  }
+}
+
+// Forward, one 32-row query tile (fragments qf) against key tiles 0 .. nt - 1 of the K / V tiles in LDS: blocks of MA_KB key
+// tiles of raw scores S^T = K Q^T, padding mask in the `ragged` tile only (-1: none), online softmax with the scale folded
+// into the exponent's fma, O^T += V^T P^T.  acc = unnormalised O^T, m = running max of the RAW scores (scale > 0), l = sum.
+// NT_ > 0: nt == NT_ and the block loop is fully unrolled; NT_ == 0: run-time nt, the loop stays a loop.
+template <int NT_>
+__device__ inline void fwd_query_tile(const bf16raw* Ks, const bf16raw* Vs, const bf16x8 (&qf)[4], const FragOff& fo, int nt_, int ragged,
+                                      int L, float c2, int lane, f32x16 (&acc)[2], float& m, float& l) {
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const int nt = NT_ > 0 ? NT_ : nt_;
+  zero16(acc[0]);
+  zero16(acc[1]);
+  m = -1e30f;
+  l = 0.f;
+#pragma unroll(NT_ > 0 ? (NT_ + MA_KB - 1) / MA_KB : 1)
+  for (int kb = 0; kb < nt; kb += MA_KB) {
+    f32x16 st[MA_KB];                              // (tiles beyond nt stay undefined: every use below is guarded)
+#pragma unroll
+    for (int t = 0; t < MA_KB; ++t) {
+      if (kb + t < nt) {
+        st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, 0, fo), qf[0], zero, 0, 0, 0);
+#pragma unroll
+        for (int ks = 1; ks < 4; ++ks)
+          st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, ks, fo), qf[ks], st[t], 0, 0, 0);
+      }
+    }
+    float bm = -1e30f;
+#pragma unroll
+    for (int t = 0; t < MA_KB; ++t)
+      if (kb + t < nt) {
+        if (kb + t == ragged) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((kb + t) * 32 + crow(r, lane) >= L) st[t][r] = -1e30f;
+        }
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bm = fmaxf(bm, st[t][r]);
+      }
+    bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+    const float mn = fmaxf(m, bm);
+    const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
+    m = mn;
+    const float mc = mn * c2;
+    float bl = 0.f;
+#pragma unroll
+    for (int t = 0; t < MA_KB; ++t)
+      if (kb + t < nt) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { const float e = __builtin_amdgcn_exp2f(fmaf(st[t][r], c2, -mc)); st[t][r] = e; bl += e; }
+      }
+    bl += __shfl_xor(bl, 32, 64);
+    l = l * alpha + bl;
+    if (kb > 0) {
+#pragma unroll
+      for (int n2 = 0; n2 < 2; ++n2)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[n2][r] *= alpha;
+    }
+#pragma unroll
+    for (int t = 0; t < MA_KB; ++t)
+      if (kb + t < nt) {
+#pragma unroll
+        for (int s2 = 0; s2 < 2; ++s2) {
+          float pf[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) pf[j] = st[t][8 * s2 + j];
+          const bf16x8 pb = pack8(pf);
+#pragma unroll
+          for (int n2 = 0; n2 < 2; ++n2)
+            acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Vs, (kb + t) * 32 + 16 * s2, n2, fo), pb, acc[n2], 0, 0, 0);
+        }
+      }
+  }
+}
+
+// delta = rowsum(dO * O) of the lane's row: the lane's 32 of the row's 64 columns, then the other half-wave's.  df(ks) / of(ks)
+// fetch the fragments (registers in the dq and one-pass kernels, LDS in the streamed one: with the eight LDS reads in front of the
+// four dot products, as an array argument asks for, attn_bwd_stream_mfma_kernel went from 239 to 256 registers + 2 spilled).
+template <typename DF, typename OF>
+__device__ inline float row_delta(DF df, OF of) {
+  float dl = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) dl = frag_dot2(df(ks), of(ks), dl);
+  return dl + __shfl_xor(dl, 32, 64);
+}
+
+// dq side (lanes = queries): dS^T = P^T (dP^T - delta) of one key tile; the softmax scale is applied once to dq at the store.
+__device__ inline void dq_ds(const f32x16& st, const f32x16& dp, float c2, float l2, float dl, float (&ds)[16]) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -l2)) * (dp[r] - dl);
+}
+// Padded keys (tile rows row0 + r >= L) have zero K rows, so only their probability needs masking (they would otherwise
+// poison nothing but cost accuracy in the bf16 pack), and only in the ragged tile: `if (kt == ragged) dq_mask_keys(..)`.
+// (attn_bwd_fused_mfma_kernel keeps these two steps open-coded, with the measured reason there: with the mask as a flag of
+// dq_ds its <0> form went from 86 to 89 spilled scalar registers with 104 more v_readlane, as two calls its <7> form ran 1 % slower.)
+__device__ inline void dq_mask_keys(float (&ds)[16], int row0, int L, int lane) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (row0 + crow(r, lane) >= L) ds[r] = 0.f;
+}
+// dQ^T += K^T dS^T for the 32 keys at row0 of the K tile
+__device__ inline void dq_accumulate(const bf16raw* Ks, int row0, const float (&ds)[16], const FragOff& fo, f32x16 (&acc)[2]) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    const bf16x8 db = pack8(ds + 8 * s2);
+#pragma unroll
+    for (int n2 = 0; n2 < 2; ++n2)
+      acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Ks, row0 + 16 * s2, n2, fo), db, acc[n2], 0, 0, 0);
+  }
+}
+
+// dk / dv side (lanes = keys): P and dS = P (dP - delta) of the 32 queries at row0; Ls = lse * log2(e) (+huge on padded query
+// rows: P = 0), Ds = delta, both in LDS.  Padded keys only feed dk / dv rows that are never stored.  The softmax scale is
+// applied once to dk at the store.
+__device__ inline void dkv_probs(const f32x16& st, const f32x16& dp, const float* Ls, const float* Ds, int row0, float c2, int lane,
+                                 float (&pr)[16], float (&ds)[16]) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int qrow = row0 + 8 * g + 4 * (lane >> 5);
+    const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
+    const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
+    const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * g + j;
+      const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
+      pr[r] = e;
+      ds[r] = e * (dp[r] - dvv[j]);
+    }
+  }
+}
+// dV^T += dO^T P, dK^T += Q^T dS for the 16 queries at row0 (a multiple of 16) of the dO / Q tiles: one of the two steps of a
+// query tile; pb / db = pack8 of that half of dkv_probs' pr / ds.  (A step, not the tile: the streamed backward packs both
+// halves first and drops db into its exchange area, the other two kernels pack a half right in front of its products -- with
+// all four packs in front, attn_bwd_dkv_mfma_kernel<7, 0 | 1> went from 14 to 18 spilled registers.)
+__device__ inline void dkv_accumulate(const bf16raw* Os, const bf16raw* Qs, int row0, const bf16x8& pb, const bf16x8& db, const FragOff& fo,
+                                      f32x16 (&dv)[2], f32x16 (&dk)[2]) {
+#pragma unroll
+  for (int n2 = 0; n2 < 2; ++n2) {
+    dv[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os, row0, n2, fo), pb, dv[n2], 0, 0, 0);
+    dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs, row0, n2, fo), db, dk[n2], 0, 0, 0);
+  }
+}
+
+// Where the gradient of token i of sequence s goes: the sequence's cls row to dqkv_cls[s] (summed by vtx_cls_qkv_reduce),
+// every other to its row of dqkv; nullptr for a padded row.  dq_dst_row: the 64 dq columns of head h; dkv_dst_base: column 0
+// of the row (dk at + D + h * 64, dv at + 2 D + h * 64).
+__device__ inline bf16raw* dkv_dst_base(const AttnP& p, int s, const RowLin& li, int i, bf16raw* dqkv, bf16raw* dqkv_cls) {
+  if (i >= p.L) return nullptr;
+  return attn_cls_row(p, i) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, i) * p.ld_dqkv;
+}
+__device__ inline bf16raw* dq_dst_row(const AttnP& p, int s, int h, const RowLin& li, int i, bf16raw* dqkv, bf16raw* dqkv_cls) {
+  if (i >= p.L) return nullptr;
+  return attn_cls_row(p, i) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64 : dqkv + lin_row(li, i) * p.ld_dqkv + h * 64;
+}
+
+// LDS-DMA requests of wave 7 of the two streamed kernels, without vector-ALU work: row r = 8 G + lane / 8 of a sequence sits
+// r * rs bytes behind the sequence's (virtual) row 0 on the token line, so a request is `buffer_load_dwordx4 voff, desc, soff
+// offen lds` with a per-lane constant voff (the lane's row of the first 8 + the source chunk that the destination swizzle
+// asks for: it only depends on the parity of G), a scalar soff = 8 G rs and a per-(item, tensor) descriptor whose range ends
+// behind row L - 1 (rows beyond it read as zeros).  Only the first 8 rows use per-lane pointers: the sequence's row 0 is not
+// on the line.  (A 64-bit multiply-add per request: 1600 cycles for the 13 requests of a step; pointer increments: 850.)
+// (Why the requests are inline asm: the wave-7 comment of attn_bwd_stream_mfma_kernel.)
+typedef __attribute__((address_space(3))) char lds_char;
+// The lane's constants: its row of 8 and its source chunk (elements) for even / odd G.  A kernel forms them ONCE, in its own
+// body and not inside a lambda: sw_of and crow are shared with the short-sequence kernels, and with `lane` reaching sw_of
+// through a closure the compiler no longer knows its range in ANY caller -- attn_bwd_small_kernel then compiled to 128
+// registers + 30 spilled (124 and none before).
+struct DmaLane { int rl8, swz[2]; };
+__device__ inline DmaLane dma_lane(int lane) {
+  const int rl8 = lane >> 3, pc = lane & 7;
+  return DmaLane{rl8, {(pc ^ sw_of(rl8)) << 3, (pc ^ sw_of(8 + rl8)) << 3}};
+}
+struct DmaSrc {
+  const bf16raw* p1;      // the lane's row of rows 1 .. 7 (lane / 8)
+  const bf16raw* p0;      // the sequence's row 0
+  u32x4 desc;
+  unsigned rs;            // bytes per token
+};
+// columns col0 .. col0 + 63 of the L rows `rl` of a [.., ld] matrix; tok = rows between consecutive tokens of a sequence
+__device__ inline DmaSrc dma_src(const bf16raw* base, long ld, int col0, const RowLin& rl, int L, long tok, const DmaLane& dn) {
+  DmaSrc x;
+  x.p1 = base + (rl.base + (long)dn.rl8 * rl.stride) * ld + col0;
+  x.p0 = base + rl.row0 * ld + col0;
+  const unsigned long a = reinterpret_cast<unsigned long>(base + rl.base * ld + col0);
+  x.desc[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
+  x.desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
+  x.desc[2] = __builtin_amdgcn_readfirstlane((unsigned)((L - 1) * tok * ld * 2 + 128));
+  x.desc[3] = 0x00020000u;
+  x.rs = (unsigned)(tok * ld * 2);
+  return x;
+}
+// rows 8 G .. 8 G + 7 of the sequence -> the 1 KB at dst (8 rows of a swizzled [..][64] tile whose row 0 is a multiple of 16
+// rows before or at row 8 G of the sequence: the swizzle of tile row 8 (G & 1) + lane / 8)
+__device__ inline void dma_rows8(const DmaSrc& x, int G, bf16raw* dst, const DmaLane& dn) {
+  const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_char*)dst);
+  if (G == 0) {
+    const bf16raw* src = (dn.rl8 == 0 ? x.p0 : x.p1) + dn.swz[0];
+    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory", "m0");
+  } else {
+    const unsigned voff = (unsigned)dn.rl8 * x.rs + 2u * (unsigned)dn.swz[G & 1];
+    const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(8 * G) * x.rs);
+    asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(x.desc), "s"(soff), "s"(m0v)
+                 : "memory", "m0");
+  }
+}
 
 // Direct variant (8-byte pieces, no staging) for the packed short-sequence kernels below.
 __device__ inline void store_rows_direct(bf16raw* dst_row, const f32x16 (&acc)[2], float mul, int lane) {
@@ -76,73 +305,12 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_fwd_mfma_kernel(AttnP p, c
   const float c2 = p.scale * LOG2E;
   const int ragged = (p.L & 31) ? nt - 1 : -1;     // the key tile that holds padded keys
   const FragOff fo = make_frag_off(lane);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int qt = wave; qt < nt; qt += 4) {
     bf16x8 qn[4];                                  // next query tile's fragments, in flight during this one
     load_row_frags(qn, qkv, p.ld_qkv, h * 64, li, (qt + 4) * 32 + (lane & 31), p.L, lane);
     f32x16 acc[2];
-    zero16(acc[0]);
-    zero16(acc[1]);
-    float m = -1e30f, l = 0.f;                     // running max of the RAW scores (scale > 0)
-#pragma unroll(NT_ > 0 ? (NT_ + MA_KB - 1) / MA_KB : 1)
-    for (int kb = 0; kb < nt; kb += MA_KB) {
-      f32x16 st[MA_KB];                            // (tiles beyond nt stay undefined: every use below is guarded)
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t) {
-        if (kb + t < nt) {
-          st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, 0, fo), qf[0], zero, 0, 0, 0);
-#pragma unroll
-          for (int ks = 1; ks < 4; ++ks)
-            st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, ks, fo), qf[ks], st[t], 0, 0, 0);
-        }
-      }
-      float bm = -1e30f;
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < nt) {
-          if (kb + t == ragged) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if ((kb + t) * 32 + crow(r, lane) >= p.L) st[t][r] = -1e30f;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) bm = fmaxf(bm, st[t][r]);
-        }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
-      const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
-      m = mn;
-      const float mc = mn * c2;
-      float bl = 0.f;
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < nt) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { const float e = __builtin_amdgcn_exp2f(fmaf(st[t][r], c2, -mc)); st[t][r] = e; bl += e; }
-        }
-      bl += __shfl_xor(bl, 32, 64);
-      l = l * alpha + bl;
-      if (kb > 0) {
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[n2][r] *= alpha;
-      }
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < nt) {
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            float pf[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = st[t][8 * s2 + j];
-            const bf16x8 pb = pack8(pf);
-#pragma unroll
-            for (int n2 = 0; n2 < 2; ++n2)
-              acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Vs, (kb + t) * 32 + 16 * s2, n2, fo), pb, acc[n2], 0, 0, 0);
-          }
-        }
-    }
+    float m, l;
+    fwd_query_tile<NT_>(Ks, Vs, qf, fo, nt, ragged, p.L, c2, lane, acc, m, l);
     const int q = qt * 32 + (lane & 31);
     store_rows_T(stg, acc, 1.0f / l, lane, [&](int r) -> bf16raw* {
       const int qq = qt * 32 + r;
@@ -188,17 +356,13 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dq_mfma_kernel(AttnP p
   const float c2 = p.scale * LOG2E;
   const int ragged = (p.L & 31) ? nt - 1 : -1;
   const FragOff fo = make_frag_off(lane);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int qt = wave; qt < nt; qt += 4) {
     const int q = qt * 32 + (lane & 31);
     bf16x8 qn[4], dn[4], on[4];                    // the next query tile's rows, in flight during this one
     load_row_frags(qn, qkv, p.ld_qkv, h * 64, li, q + 128, p.L, lane);
     load_row_frags(dn, dout, p.ld_dout, h * 64, lo, q + 128, p.L, lane);
     load_row_frags(on, o, p.ld_out, h * 64, lo, q + 128, p.L, lane);
-    float dl = 0.f;                                // delta = rowsum(dO * O): this lane's 32 of the row's 64 columns
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) dl = frag_dot2(df[ks], of[ks], dl);
-    dl += __shfl_xor(dl, 32, 64);
+    const float dl = row_delta([&](int ks) { return df[ks]; }, [&](int ks) { return of[ks]; });
     const long lidx = ((long)s * p.H + h) * p.L + q;
     float l2 = 0.f;
     if (q < p.L) {
@@ -210,38 +374,14 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dq_mfma_kernel(AttnP p
     zero16(acc[1]);
 #pragma unroll(NT_ > 0 ? NT_ : 1)
     for (int kt = 0; kt < nt; ++kt) {
-      f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, kt * 32, 0, fo), qf[0], zero, 0, 0, 0);
-      f32x16 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Vs, kt * 32, 0, fo), df[0], zero, 0, 0, 0);
-#pragma unroll
-      for (int ks = 1; ks < 4; ++ks) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, kt * 32, ks, fo), qf[ks], st, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Vs, kt * 32, ks, fo), df[ks], dp, 0, 0, 0);
-      }
-      // dS = P (dP - delta); the softmax scale is applied once to dq at the store.  Padded keys have
-      // zero K rows, so only their probability needs masking (they would otherwise poison nothing but
-      // cost accuracy in the bf16 pack), and only in the ragged tile.
+      f32x16 st, dp;
+      score_pair(Ks, Vs, kt * 32, qf, df, fo, st, dp);
       float ds[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -l2)) * (dp[r] - dl);
-      if (kt == ragged) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kt * 32 + crow(r, lane) >= p.L) ds[r] = 0.f;
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2)
-          acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Ks, kt * 32 + 16 * s2, n2, fo), db, acc[n2], 0, 0, 0);
-      }
+      dq_ds(st, dp, c2, l2, dl, ds);
+      if (kt == ragged) dq_mask_keys(ds, kt * 32, p.L, lane);
+      dq_accumulate(Ks, kt * 32, ds, fo, acc);
     }
-    store_rows_T(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
-      const int qq = qt * 32 + r;
-      if (qq >= p.L) return nullptr;
-      return attn_cls_row(p, qq) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
-                                                    : dqkv + lin_row(li, qq) * p.ld_dqkv + h * 64;
-    });
+    store_rows_T(stg, acc, p.scale, lane, [&](int r) { return dq_dst_row(p, s, h, li, qt * 32 + r, dqkv, dqkv_cls); });
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) { qf[ks] = qn[ks]; df[ks] = dn[ks]; of[ks] = on[ks]; }
   }
@@ -280,7 +420,6 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dkv_mfma_kernel(AttnP 
   __syncthreads();
   const float c2 = p.scale * LOG2E;
   const FragOff fo = make_frag_off(lane);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (int kt = wave; kt < nt; kt += 4) {
     bf16x8 kn[4], vn[4];                           // next key tile's fragments, in flight during this one
     if (!(VAR_ & 2)) {
@@ -294,45 +433,14 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dkv_mfma_kernel(AttnP 
       // unrolled: keep the instruction scheduler from hoisting the next query tile's fragment reads over this one's tail
       // (32 more live registers: the kernel sits at the 256-register limit of two waves per SIMD and spilled)
       if (VAR_ & 1) __builtin_amdgcn_sched_barrier(0);
-      f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, 0, fo), kf[0], zero, 0, 0, 0);
-      f32x16 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, 0, fo), vf[0], zero, 0, 0, 0);
-#pragma unroll
-      for (int ks = 1; ks < 4; ++ks) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, ks, fo), kf[ks], st, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, ks, fo), vf[ks], dp, 0, 0, 0);
-      }
-      // padded query rows: Ls = +huge -> P = 0; padded keys only feed dk/dv rows that are never stored
+      f32x16 st, dp;
+      score_pair(Qs, Os, qt * 32, kf, vf, fo, st, dp);
       float pr[16], ds[16];
+      dkv_probs(st, dp, Ls, Ds, qt * 32, c2, lane, pr, ds);
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int qrow = qt * 32 + 8 * g + 4 * (lane >> 5);
-        const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
-        const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
-        const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = 4 * g + j;
-          const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
-          pr[r] = e;
-          ds[r] = e * (dp[r] - dvv[j]);            // the softmax scale is applied once to dk at the store
-        }
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        const bf16x8 pb = pack8(pr + 8 * s2);
-        const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2) {
-          dv[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os, qt * 32 + 16 * s2, n2, fo), pb, dv[n2], 0, 0, 0);
-          dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs, qt * 32 + 16 * s2, n2, fo), db, dk[n2], 0, 0, 0);
-        }
-      }
+      for (int s2 = 0; s2 < 2; ++s2) dkv_accumulate(Os, Qs, qt * 32 + 16 * s2, pack8(pr + 8 * s2), pack8(ds + 8 * s2), fo, dv, dk);
     }
-    auto base_of = [&](int r) -> bf16raw* {
-      const int kk = kt * 32 + r;
-      if (kk >= p.L) return nullptr;
-      return attn_cls_row(p, kk) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
-    };
+    auto base_of = [&](int r) { return dkv_dst_base(p, s, li, kt * 32 + r, dqkv, dqkv_cls); };
     store_rows_T(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * 64 : nullptr; });
     store_rows_T(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * 64 : nullptr; });
     if (VAR_ & 2) {
@@ -356,9 +464,9 @@ __global__ __launch_bounds__(MA_THREADS, 2) void attn_bwd_dkv_mfma_kernel(AttnP 
 //   top:    the worker's Q / dO / O row fragments (already in registers: loaded behind the previous item's last
 //           products) -> delta = rowsum(dO * O), Q and dO fragments copied into the LDS tiles, lse * log2(e) and delta
 //           into LDS;                                                          barrier A
-//   dq:     the dq kernel's tile body on the K / V tiles; then the wave takes its own K / V fragments out of the tiles
+//   dq:     the dq kernel's steps (score_pair, dq_ds, dq_accumulate) on the K / V tiles; then the wave takes its own K / V fragments out of the tiles
 //           (same values and lane layout as the dkv kernel's global loads);     barrier B (K / V tiles are free)
-//   dk/dv:  the dkv kernel's tile body on the Q / dO tiles, WHILE the loader brings the next item's K and V tiles from
+//   dk/dv:  the dkv kernel's steps (score_pair, dkv_probs, dkv_accumulate) on the Q / dO tiles, WHILE the loader brings the next item's K and V tiles from
 //           HBM into the free K / V space (LDS-DMA); behind its last product a worker requests
 //           the next item's row fragments, then stores dk, dv;                  barrier C (Q / dO tiles are free)
 // so the only exposed memory time per item is what the loader / the fragment loads do not finish under the dk/dv phase.
@@ -456,16 +564,6 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
   load_row_frags(of, o, p.ld_out, h * 64, lo, q, p.L, lane);
   float l2 = q < p.L ? lse[((long)s * p.H + h) * p.L + q] * LOG2E : 0.f;
 
-  auto scores_dq = [&](int kt, f32x16& st, f32x16& dp) {
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, kt * 32, 0, fo), qf[0], zero, 0, 0, 0);
-    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Vs, kt * 32, 0, fo), df[0], zero, 0, 0, 0);
-#pragma unroll
-    for (int ks = 1; ks < 4; ++ks) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, kt * 32, ks, fo), qf[ks], st, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Vs, kt * 32, ks, fo), df[ks], dp, 0, 0, 0);
-    }
-  };
-
   while (true) {
     // the lane's fragment offsets are made opaque once per item: every LDS address of the unrolled phases is (offset +
     // constant), loop-invariant, and hoisted out of the item loop they would need a few hundred registers
@@ -473,10 +571,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(fo.rows[i]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(fo.cols[i >> 1][i & 1]));
-    float dl = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) dl = frag_dot2(df[ks], of[ks], dl);
-    dl += __shfl_xor(dl, 32, 64);
+    const float dl = row_delta([&](int ks) { return df[ks]; }, [&](int ks) { return of[ks]; });
     put_tile(Qs + wave * 32 * 64, qf, lane);
     put_tile(Os + wave * 32 * 64, df, lane);
     if (lane < 32) {
@@ -484,16 +579,19 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
       Ds[q] = q < p.L ? dl : 0.f;
     }
     __syncthreads();                                // A: this item's four tiles, lse and delta are in LDS
-    if (!(VTX_FUSED_ABLATE & 1)) {                  // ---- dq of query tile `wave` (attn_bwd_dq_mfma_kernel's tile body)
+    if (!(VTX_FUSED_ABLATE & 1)) {                  // ---- dq of query tile `wave`: the dq kernel's steps, score products one tile ahead
       f32x16 acc[2];
       zero16(acc[0]);
       zero16(acc[1]);
       f32x16 st, dp;
-      scores_dq(0, st, dp);
+      score_pair(Ks, Vs, 0, qf, df, fo, st, dp);
 #pragma unroll(NT_ > 0 ? NT_ : 1)
       for (int kt = 0; kt < nt; ++kt) {
         f32x16 stn = zero, dpn = zero;
-        if (kt + 1 < nt) scores_dq(kt + 1, stn, dpn);
+        if (kt + 1 < nt) score_pair(Ks, Vs, (kt + 1) * 32, qf, df, fo, stn, dpn);
+        // dq_ds and dq_mask_keys, open-coded: through the two calls this kernel's <7> form measured 0.7 % and 1.1 % slower in two
+        // alternated runs (693 -> 698 us at 96 clips; a handful of scalar instructions placed differently), and this text
+        // compiles to the instruction stream it had before the bodies were shared
         float ds[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -l2)) * (dp[r] - dl);
@@ -502,22 +600,11 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
           for (int r = 0; r < 16; ++r)
             if (kt * 32 + crow(r, lane) >= p.L) ds[r] = 0.f;
         }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2)
-            acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Ks, kt * 32 + 16 * s2, n2, fo), db, acc[n2], 0, 0, 0);
-        }
+        dq_accumulate(Ks, kt * 32, ds, fo, acc);
         st = stn;
         dp = dpn;
       }
-      store_rows_T(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
-        const int qq = wave * 32 + r;
-        if (qq >= p.L) return nullptr;
-        return attn_cls_row(p, qq) ? dqkv_cls + (long)s * p.ld_dqkv + h * 64
-                                                      : dqkv + lin_row(li, qq) * p.ld_dqkv + h * 64;
-      });
+      store_rows_T(stg, acc, p.scale, lane, [&](int r) { return dq_dst_row(p, s, h, li, wave * 32 + r, dqkv, dqkv_cls); });
     }
     bf16x8 kf[4], vf[4];
 #pragma unroll
@@ -533,46 +620,15 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
     const RowLin lin = lin_in(p, sn), lon = lin_out(p, sn);
     f32x16 dk[2], dv[2];
     zero16(dk[0]); zero16(dk[1]); zero16(dv[0]); zero16(dv[1]);
-    if (!(VTX_FUSED_ABLATE & 2)) {                  // ---- dk, dv of key tile `wave` (attn_bwd_dkv_mfma_kernel's tile body)
-      auto scores_dkv = [&](int qt, f32x16& st, f32x16& dp) {
-        st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, 0, fo), kf[0], zero, 0, 0, 0);
-        dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, 0, fo), vf[0], zero, 0, 0, 0);
-#pragma unroll
-        for (int ks = 1; ks < 4; ++ks) {
-          st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, ks, fo), kf[ks], st, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, ks, fo), vf[ks], dp, 0, 0, 0);
-        }
-      };
+    if (!(VTX_FUSED_ABLATE & 2)) {                  // ---- dk, dv of key tile `wave`: the dk / dv kernel's steps
 #pragma unroll(NT_ > 0 ? NT_ : 1)
       for (int qt = 0; qt < nt; ++qt) {
         f32x16 st, dp;
-        scores_dkv(qt, st, dp);
-        // padded query rows: Ls = +huge -> P = 0; padded keys only feed dk/dv rows that are never stored
+        score_pair(Qs, Os, qt * 32, kf, vf, fo, st, dp);
         float pr[16], ds[16];
+        dkv_probs(st, dp, Ls, Ds, qt * 32, c2, lane, pr, ds);
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int qrow = qt * 32 + 8 * g + 4 * (lane >> 5);
-          const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
-          const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
-          const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int r = 4 * g + j;
-            const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
-            pr[r] = e;
-            ds[r] = e * (dp[r] - dvv[j]);            // the softmax scale is applied once to dk at the store
-          }
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          const bf16x8 pb = pack8(pr + 8 * s2);
-          const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) {
-            dv[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os, qt * 32 + 16 * s2, n2, fo), pb, dv[n2], 0, 0, 0);
-            dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs, qt * 32 + 16 * s2, n2, fo), db, dk[n2], 0, 0, 0);
-          }
-        }
+        for (int s2 = 0; s2 < 2; ++s2) dkv_accumulate(Os, Qs, qt * 32 + 16 * s2, pack8(pr + 8 * s2), pack8(ds + 8 * s2), fo, dv, dk);
       }
     }
     // the next item's row fragments, in flight under the dk / dv stores
@@ -581,11 +637,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
     load_row_frags(of, o, p.ld_out, hn * 64, lon, q, p.L, lane);
     l2 = q < p.L ? lse[((long)sn * p.H + hn) * p.L + q] * LOG2E : 0.f;
     if (!(VTX_FUSED_ABLATE & 2)) {
-      auto base_of = [&](int r) -> bf16raw* {
-        const int kk = wave * 32 + r;
-        if (kk >= p.L) return nullptr;
-        return attn_cls_row(p, kk) ? dqkv_cls + (long)s * p.ld_dqkv : dqkv + lin_row(li, kk) * p.ld_dqkv;
-      };
+      auto base_of = [&](int r) { return dkv_dst_base(p, s, li, wave * 32 + r, dqkv, dqkv_cls); };
       store_rows_T(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * 64 : nullptr; });
       store_rows_T(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * 64 : nullptr; });
     }
@@ -601,8 +653,8 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_fused_mfma_kernel(Attn
 // load time, dq phase and dk / dv phase ADD.  This kernel runs ONE phase per (sequence, head):
 //   * worker w (waves 0 .. 6) owns key tile w for the whole item: K_w, V_w as row fragments in registers, dK^T / dV^T
 //     accumulators in registers; it walks the query tiles 0 .. 6 exactly like the dk / dv kernel (S = Q K^T with lanes =
-//     keys, P, dS, dV^T += dO^T P, dK^T += Q^T dS: same products, same order -- dk and dv are bit-identical to the kernels
-//     above) -- one exp, one score product and one dP product per score instead of two;
+//     keys, P, dS, dV^T += dO^T P, dK^T += Q^T dS: the same score_pair / dkv_probs / dkv_accumulate calls -- dk and dv are
+//     bit-identical to the kernels above) -- one exp, one score product and one dP product per score instead of two;
 //   * dq needs dS with lanes = queries and a sum over ALL key tiles.  Each worker drops its packed bf16 dS tile (2 KB, as
 //     [key][query]) into a double-buffered LDS exchange area; after the step's barrier WAVE 7 reads the seven tiles back
 //     through `ds_read_b64_tr_b16` as B operands and runs the whole dQ^T tile of the step, 28 MFMAs against the item's K^T
@@ -749,10 +801,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
   // parity `par`; the lanes of row group `grp` (rows 8 grp .. + 7; -1: all) write.  Row-per-lane arithmetic of the other kernels
   // (same delta bit for bit).
   auto finish_tile = [&](int t, const bf16raw* ost, int par, int grp, const FragOff& f) {
-    float dl = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) dl = frag_dot2(frag_rows_o(Os, t * 32, ks, f), frag_rows_o(ost, 0, ks, f), dl);
-    dl += __shfl_xor(dl, 32, 64);
+    const float dl = row_delta([&](int ks) { return frag_rows_o(Os, t * 32, ks, f); }, [&](int ks) { return frag_rows_o(ost, 0, ks, f); });
     if (lane < 32 && (grp < 0 || (lane >> 3) == grp)) {
       const int row = t * 32 + lane;
       float* lp = LD + par * 2 * MG_LP + row;
@@ -778,58 +827,25 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
     // item boundary: tile j = i - 2 (mod 7), so tiles 5 and 6 of an item are finished during steps 0 and 1 of that item
     // (their first readers are steps 5 and 6).  The requests are inline asm: hipcc waits `vmcnt(0)` before LDS reads while
     // a DMA it knows of is in flight, which would park this wave -- and with it every barrier -- on what it has just issued.
-    typedef __attribute__((address_space(3))) char lds_char;
     FragOff ffo = make_frag_off(lane);
-    // Requests without vector-ALU work: row r = 8 G + lane / 8 of a sequence sits r * rs bytes behind the sequence's (virtual) row
-    // 0 on the token line, so a request is `buffer_load_dwordx4 voff, desc, soff offen lds` with a per-lane constant voff (the
-    // lane's row of the first 8 + the source chunk that the destination swizzle asks for: it only depends on the parity of G), a
-    // scalar soff = 8 G rs and a per-(item, tensor) descriptor whose range ends behind row L - 1 (rows beyond it read as zeros: their
-    // lse is +huge).  Only the first 8 rows use per-lane pointers: the sequence's row 0 is not on the line.  (A 64-bit multiply-add
-    // per request: 1600 cycles for the 13 requests of a step; pointer increments: 850.)
-    struct Src { const bf16raw* p1; const bf16raw* p0; u32x4 desc; };
-    const int rl8 = lane >> 3, pc = lane & 7;
-    const int swz[2] = {(pc ^ sw_of(rl8)) << 3, (pc ^ sw_of(8 + rl8)) << 3};
     const long tok = p.mode == VTX_ATTN_SPACE ? p.T : 1;          // rows between consecutive tokens of a sequence
-    auto make_src = [&](const bf16raw* base, long ld, int col0, const RowLin& rl) {
-      Src x;
-      x.p1 = base + (rl.base + (long)rl8 * rl.stride) * ld + col0;
-      x.p0 = base + rl.row0 * ld + col0;
-      const unsigned long a = reinterpret_cast<unsigned long>(base + rl.base * ld + col0);
-      x.desc[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-      x.desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-      x.desc[2] = __builtin_amdgcn_readfirstlane((unsigned)((p.L - 1) * tok * ld * 2 + 128));
-      x.desc[3] = 0x00020000u;
-      return x;
-    };
-    auto dma_tile = [&](const Src& x, long ld, int t, bf16raw* dst) {
-      const unsigned rs = (unsigned)(tok * ld * 2);               // bytes per token
+    const DmaLane dn = dma_lane(lane);
+    auto dma_tile = [&](const DmaSrc& x, int t, bf16raw* dst) {   // query tile t (rows 32 t .. + 31) of a tensor -> the [32][64] tile dst
 #pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int G = 4 * t + g;
-        const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_char*)(dst + g * 512));
-        if (G == 0) {
-          const bf16raw* src = (rl8 == 0 ? x.p0 : x.p1) + swz[0];
-          asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory", "m0");
-        } else {
-          const unsigned voff = (unsigned)rl8 * rs + 2u * (unsigned)swz[g & 1];
-          const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(8 * G) * rs);
-          asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(x.desc), "s"(soff), "s"(m0v)
-                       : "memory", "m0");
-        }
-      }
+      for (int g = 0; g < 4; ++g) dma_rows8(x, 4 * t + g, dst + g * 512, dn);
     };
-    Src sq, sd, so;
+    DmaSrc sq, sd, so;
     const float* slse = nullptr;                    // lse row of the item the requests are for
     auto set_item = [&](int s, int h, const RowLin& li, const RowLin& lo) {
-      sq = make_src(qkv, p.ld_qkv, h * 64, li);
-      sd = make_src(dout, p.ld_dout, h * 64, lo);
-      so = make_src(o, p.ld_out, h * 64, lo);
+      sq = dma_src(qkv, p.ld_qkv, h * 64, li, p.L, tok, dn);
+      sd = dma_src(dout, p.ld_dout, h * 64, lo, p.L, tok, dn);
+      so = dma_src(o, p.ld_out, h * 64, lo, p.L, tok, dn);
       slse = lse + ((long)s * p.H + h) * p.L;
     };
     auto dma_item_tile = [&](int t, bf16raw* ost, float* lsd) {
-      dma_tile(sq, p.ld_qkv, t, Qs + t * MG_TILE);
-      dma_tile(sd, p.ld_dout, t, Os + t * MG_TILE);
-      dma_tile(so, p.ld_out, t, ost);
+      dma_tile(sq, t, Qs + t * MG_TILE);
+      dma_tile(sd, t, Os + t * MG_TILE);
+      dma_tile(so, t, ost);
       const int row = t * 32 + (lane & 31);
       const float* src = slse + (row < p.L ? row : p.L - 1);
       const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_char*)(lsd + t * 32));
@@ -945,15 +961,6 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
   // this worker's part of the exchange area: two dS buffers ([key][query], 8-byte stores of 4 queries), also its V tile at the top
   char* myx = xch + wave * 2 * MG_SCR_BYTES;
   const unsigned scr_w = (unsigned)((lane & 31) * (MG_SCR_LD * 2) + 8 * (lane >> 5));
-  auto scores = [&](int qt, f32x16& st, f32x16& dp) {
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, 0, fo), kf[0], zero, 0, 0, 0);
-    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, 0, fo), vf[0], zero, 0, 0, 0);
-#pragma unroll
-    for (int ks = 1; ks < 4; ++ks) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, qt * 32, ks, fo), kf[ks], st, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, qt * 32, ks, fo), vf[ks], dp, 0, 0, 0);
-    }
-  };
   // dq rows: staging tile row r = 8 g + lane / 8 of query tile t -> dq_lin + (4 t + g) * dq_step8, row 0 of the sequence -> dq_row0
   bf16raw *dq_lin = nullptr, *dq_row0 = nullptr, *dq_lin_prev = nullptr, *dq_row0_prev = nullptr;
   long dq_step8 = 0, dq_step8_prev = 0;
@@ -1008,7 +1015,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
     f32x16 dk[2], dv[2];
     zero16(dk[0]); zero16(dk[1]); zero16(dv[0]); zero16(dv[1]);
     f32x16 st = zero, dp = zero;
-    if (!(VTX_STREAM_ABLATE & 2)) scores(0, st, dp);
+    if (!(VTX_STREAM_ABLATE & 2)) score_pair(Qs, Os, 0, kf, vf, fo, st, dp);
     wave_lds_sync();                                // V fragments are in registers before step 0 writes dS over the V tile
     MG_STAMP(0, 7, 1)
 #pragma unroll
@@ -1020,20 +1027,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
       f32x16 stn = zero, dpn = zero;
       if (!(VTX_STREAM_ABLATE & 2)) {
         float pr[16], ds[16];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int qrow = i * 32 + 8 * g + 4 * (lane >> 5);
-          const float4 l4 = *reinterpret_cast<const float4*>(Lc + qrow);
-          const float4 d4 = *reinterpret_cast<const float4*>(Dc + qrow);
-          const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int r = 4 * g + j;
-            const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
-            pr[r] = e;
-            ds[r] = e * (dp[r] - dvv[j]);            // the softmax scale is applied once, at the stores
-          }
-        }
+        dkv_probs(st, dp, Lc, Dc, i * 32, c2, lane, pr, ds);
         bf16x8 pb[2], db[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) db[s2] = pack8(ds + 8 * s2);
@@ -1054,14 +1048,9 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
         for (int s2 = 0; s2 < 2; ++s2) pb[s2] = pack8(pr + 8 * s2);
         MG_STAMP(0, i, 1)
 #pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-          for (int n2 = 0; n2 < 2; ++n2) {
-            dv[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os, i * 32 + 16 * s2, n2, fo), pb[s2], dv[n2], 0, 0, 0);
-            dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs, i * 32 + 16 * s2, n2, fo), db[s2], dk[n2], 0, 0, 0);
-          }
+        for (int s2 = 0; s2 < 2; ++s2) dkv_accumulate(Os, Qs, i * 32 + 16 * s2, pb[s2], db[s2], fo, dv, dk);
         MG_STAMP(0, i, 2)
-        if (i + 1 < NT_) scores(i + 1, stn, dpn);   // the next query tile's products are on the matrix pipe across the barrier
+        if (i + 1 < NT_) score_pair(Qs, Os, (i + 1) * 32, kf, vf, fo, stn, dpn);   // the next query tile's products are on the matrix pipe across the barrier
       }
       if ((i == NT_ - 1 - VTX_STREAM_KV_AHEAD || i == NT_ - VTX_STREAM_KV_AHEAD) && !(VTX_STREAM_ABLATE & 8)) {
         // the next item's K_w rows are requested two steps, its V_w rows one step before the item ends (no gain from more; 8 requests per worker in
@@ -1126,7 +1115,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_bwd_stream_mfma_kernel(Att
 // The forward kernel at the top of this file is a workgroup per (sequence, head): fetch K and V (global -> registers -> LDS),
 // barrier, seven query tiles on four waves (2 + 2 + 2 + 1), stores -- load, compute and store phases of a workgroup follow each
 // other and only the second workgroup of the CU covers them.  Here one workgroup per CU is persistent over the items like the
-// backward kernel above: waves 0 .. 6 own one query tile each (the tile body of the kernel above, unchanged: bit-identical
+// backward kernel above: waves 0 .. 6 own one query tile each (fwd_query_tile<7>, as attn_fwd_mfma_kernel<7> calls it: bit-identical
 // results), wave 7 brings the NEXT item's K and V tiles into the other half of a double buffer by LDS-DMA (56 requests, range-
 // checked buffer loads: padded key rows read as zeros) while the workers run; one barrier per item.
 constexpr size_t MGF_LDS_BYTES = (size_t)2 * 2 * 7 * MG_TILE * 2 + 8 * MA_STAGE_ELEMS * 2;
@@ -1145,39 +1134,17 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_fwd_stream_mfma_kernel(Att
   const float invH = 1.0f / (float)p.H, invT = p.mode == VTX_ATTN_SPACE ? 1.0f / (float)p.T : 1.0f;
 
   if (wave == MF_LOADER) {                          // ------------------------------------------------------------- wave 7
-    typedef __attribute__((address_space(3))) char lds_char;
-    const int rl8 = lane >> 3, pc = lane & 7;
-    const int swz[2] = {(pc ^ sw_of(rl8)) << 3, (pc ^ sw_of(8 + rl8)) << 3};
     const long tok = p.mode == VTX_ATTN_SPACE ? p.T : 1;
-    const unsigned rs = (unsigned)(tok * p.ld_qkv * 2);           // bytes per token
-    const unsigned voff[2] = {(unsigned)rl8 * rs + 2u * (unsigned)swz[0], (unsigned)rl8 * rs + 2u * (unsigned)swz[1]};
-    auto request = [&](int item, int buf) {
+    const DmaLane dn = dma_lane(lane);
+    auto request = [&](int item, int buf) {       // all rows of the K and V tiles of `item` -> buffer `buf`
       const int s = mg_div(item, p.H, invH), h = item - s * p.H;
       const RowLin li = mg_lin_in(p, s, invT);
 #pragma unroll
       for (int kv = 0; kv < 2; ++kv) {
-        const int col0 = (1 + kv) * D + h * 64;
-        const bf16raw* p1 = qkv + (li.base + (long)rl8 * li.stride) * p.ld_qkv + col0;
-        const bf16raw* p0 = qkv + li.row0 * p.ld_qkv + col0;
-        const unsigned long a = reinterpret_cast<unsigned long>(qkv + li.base * p.ld_qkv + col0);
-        u32x4 desc;
-        desc[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-        desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-        desc[2] = __builtin_amdgcn_readfirstlane((unsigned)((p.L - 1) * tok * p.ld_qkv * 2 + 128));
-        desc[3] = 0x00020000u;
+        const DmaSrc x = dma_src(qkv, p.ld_qkv, (1 + kv) * D + h * 64, li, p.L, tok, dn);
         bf16raw* dst = KV + (buf * 2 + kv) * NT_ * MG_TILE;
 #pragma unroll
-        for (int G = 0; G < 4 * NT_; ++G) {
-          const unsigned m0v = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(lds_char*)(dst + G * 512));
-          if (G == 0) {
-            const bf16raw* src = (rl8 == 0 ? p0 : p1) + swz[0];
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(m0v) : "memory", "m0");
-          } else {
-            const unsigned soff = __builtin_amdgcn_readfirstlane((unsigned)(8 * G) * rs);
-            asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff[G & 1]), "s"(desc), "s"(soff), "s"(m0v)
-                         : "memory", "m0");
-          }
-        }
+        for (int G = 0; G < 4 * NT_; ++G) dma_rows8(x, G, dst + G * 512, dn);
       }
     };
     int item = blockIdx.x, buf = 0;
@@ -1199,7 +1166,6 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_fwd_stream_mfma_kernel(Att
   const float c2 = p.scale * LOG2E;
   const int ragged = (p.L & 31) ? NT_ - 1 : -1;    // the key tile that holds padded keys
   const FragOff fo0 = make_frag_off(lane);
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   int item = blockIdx.x, buf = 0;
   int s = mg_div(item, p.H, invH), h = item - s * p.H;
   RowLin li = mg_lin_in(p, s, invT);
@@ -1223,68 +1189,8 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_fwd_stream_mfma_kernel(Att
     bf16x8 qn[4];                                   // the next item's query rows, in flight during this one
     load_row_frags(qn, qkv, p.ld_qkv, hn * 64, lin, q, p.L, lane);
     f32x16 acc[2];
-    zero16(acc[0]);
-    zero16(acc[1]);
-    float m = -1e30f, l = 0.f;                      // running max of the RAW scores (scale > 0)
-#pragma unroll
-    for (int kb = 0; kb < NT_; kb += MA_KB) {
-      f32x16 st[MA_KB];
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t) {
-        if (kb + t < NT_) {
-          st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, 0, fo), qf[0], zero, 0, 0, 0);
-#pragma unroll
-          for (int ks = 1; ks < 4; ++ks)
-            st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Ks, (kb + t) * 32, ks, fo), qf[ks], st[t], 0, 0, 0);
-        }
-      }
-      float bm = -1e30f;
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < NT_) {
-          if (kb + t == ragged) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-              if ((kb + t) * 32 + crow(r, lane) >= p.L) st[t][r] = -1e30f;
-          }
-#pragma unroll
-          for (int r = 0; r < 16; ++r) bm = fmaxf(bm, st[t][r]);
-        }
-      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
-      const float mn = fmaxf(m, bm);
-      const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
-      m = mn;
-      const float mc = mn * c2;
-      float bl = 0.f;
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < NT_) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) { const float e = __builtin_amdgcn_exp2f(fmaf(st[t][r], c2, -mc)); st[t][r] = e; bl += e; }
-        }
-      bl += __shfl_xor(bl, 32, 64);
-      l = l * alpha + bl;
-      if (kb > 0) {
-#pragma unroll
-        for (int n2 = 0; n2 < 2; ++n2)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) acc[n2][r] *= alpha;
-      }
-#pragma unroll
-      for (int t = 0; t < MA_KB; ++t)
-        if (kb + t < NT_) {
-#pragma unroll
-          for (int s2 = 0; s2 < 2; ++s2) {
-            float pf[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) pf[j] = st[t][8 * s2 + j];
-            const bf16x8 pb = pack8(pf);
-#pragma unroll
-            for (int n2 = 0; n2 < 2; ++n2)
-              acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Vs, (kb + t) * 32 + 16 * s2, n2, fo), pb, acc[n2], 0, 0, 0);
-          }
-        }
-    }
+    float m, l;
+    fwd_query_tile<NT_>(Ks, Vs, qf, fo, NT_, ragged, p.L, c2, lane, acc, m, l);
     {
       const RowLin lo = mg_lin_out(p, s, invT);
       const long orow = wave * 32 + (lane >> 3);
