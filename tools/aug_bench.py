@@ -15,6 +15,14 @@ the training step (not measured here).
 times the RandAugment kernels (csrc/randaug.hip) at 96 clips x 8 frames x 224x224 with every clip selected, one launch of the
 single-op jitter as the same-run yardstick, and the whole ClipAugment(auto_augment=True) call from 256x340 sources.  Beside
 each time: the bytes the op has to move and the rate the jitter reached in profiles/clip_aug_bench.txt.
+
+    python tools/aug_bench.py --views [--out profiles/clip_views_bench.txt]
+
+times the test-time views (csrc/views.hip): 32 clips, 8 of 32 decoded frames each, 256x340 -> 3 x 224x224 (ClipTest: Resize(256) +
+ThreeCrop, bilinear), `vtx.ops.clip_views_u8` against the composition the other kernels offer for the same bytes -- index_select
+of the frames, three `clip_resample_u8` passes, one stacking copy -- in alternating rounds of the same run, after checking that
+both give the same bytes.  256x340 sources make Resize(256) the identity, so a second block repeats it from 240x320 sources
+(-> 256x341, a real resize).
 """
 import argparse
 import os
@@ -160,10 +168,85 @@ def randaug_main(a):
         f.write(text)
 
 
+def views_main(a):
+    import numpy as np
+    dev = 'cuda:0'
+    B, Ts, T, S, k = a.clips, a.decoded, a.frames, a.size, a.sets
+    t = aug.ClipTest(img_size=S, short_side=a.short_side)
+    g = torch.Generator().manual_seed(0)
+    lines = [f'test-time views, {B} clips, {T} of {Ts} decoded frames each, ClipTest({S}, short_side={a.short_side}), bilinear, antialias off; '
+             f'{torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} calls per path, the two paths in alternating rounds of one run, after {a.warmup} warm-up calls each, HIP events; '
+             f'{k} source sets in rotation (together larger than the 256 MiB Infinity Cache)',
+             'bytes = what each path has to move, whole source frames counted (the rows outside the crop window are never read by either)',
+             '']
+    shapes = [tuple(a.src)] + ([(240, 320)] if tuple(a.src) == (256, 340) else [])
+    for Hs, Ws in shapes:
+        srcs = [torch.randint(0, 256, (B, Ts, Hs, Ws, 3), generator=g, dtype=torch.uint8).to(dev) for _ in range(k)]
+        frames = np.stack([aug.sample_frames(Ts, T, Ts // T, generator=g) for _ in range(B)]).astype(np.int32)
+        (Hr, Wr), (top, lefts) = t.resized_hw(Hs, Ws), t.offsets(Hs, Ws)
+        up = lambda tab: tuple(torch.from_numpy(x).to(dev) for x in tab)
+        ytab = up(aug._tables([(Hs, 0, Hs, Hr, False, top, S)] * B, 'bilinear', False))
+        xall = up(aug._tables([(Ws, 0, Ws, Wr, False, 0, Wr)] * B, 'bilinear', False))
+        xcut = [up(aug._tables([(Ws, 0, Ws, Wr, False, l, S)] * B, 'bilinear', False)) for l in lefts]
+        fdev = torch.from_numpy(frames).to(dev)
+        ldev = torch.tensor([lefts] * B, dtype=torch.int32, device=dev)
+        flat = (torch.arange(B).view(B, 1) * Ts + torch.from_numpy(frames).long()).reshape(-1).to(dev)
+        out = torch.empty(B, 3, T, S, S, 3, dtype=torch.uint8, device=dev)
+
+        def one_launch(i):
+            return ops.clip_views_u8(srcs[i % k], fdev, ldev, S, xall, ytab, out=out)
+
+        def composition(i):
+            sel = srcs[i % k].view(B * Ts, Hs, Ws, 3).index_select(0, flat).view(B, T, Hs, Ws, 3)
+            return torch.stack([ops.clip_resample_u8(sel, (S, S), x, ytab) for x in xcut], dim=1)
+        same = torch.equal(one_launch(0), composition(0))
+        assert same, 'clip_views_u8 and the composition differ'
+        for i in range(a.warmup):
+            one_launch(i)
+            composition(i)
+        torch.cuda.synchronize()
+        new, old = [], []
+        for r in range(a.rounds):                              # alternating: what else runs on the machine hits both alike
+            for fn, acc in ((one_launch, new), (composition, old)):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for i in range(a.iters):
+                    fn(r * a.iters + i)
+                e1.record()
+                e1.synchronize()
+                acc.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+        fr, src_b, view_b = B * T, Hs * Ws * 3, 3 * S * S * 3
+        new_bytes = fr * (src_b + view_b)
+        old_bytes = fr * (2 * src_b + 3 * src_b + view_b + 2 * view_b)
+        lines.append(f'{Hs}x{Ws} -> {Hr}x{Wr} -> 3 x {S}x{S}, rows from {top}, columns from {lefts}: {len(set(c for l in lefts for c in range(l, l + S)))} of {Wr} '
+                     f'columns in a view, {3 * S} stored; source set {srcs[0].numel() / 2**20:.0f} MiB; same bytes from both paths: {same}')
+
+        def row(name, us, nbytes, what):
+            med, lo = statistics.median(us), min(us)
+            lines.append(f'{name:<34} median {med:8.1f} us  min {lo:8.1f} us  {nbytes / 1e6:7.1f} MB ({what})  {nbytes / med / 1e6:5.2f} TB/s '
+                         f'= {nbytes / (med * 1e-6) / HBM:5.3f} of 8 TB/s')
+            return med
+        m_new = row('vtx_clip_views_u8', new, new_bytes, 'selected frames read, three views written')
+        m_old = row('index_select + 3 resample + stack', old, old_bytes, 'gather: read + write; three passes: frame read, view written; stack: read + write')
+        lines.append(f'one launch / composition: {m_new / m_old:.3f} of the time, {new_bytes / old_bytes:.3f} of the bytes'
+                     + ('' if m_new <= m_old else '   <-- the one launch is SLOWER than the composition it replaces'))
+        lines.append('')
+        del srcs
+    text = '\n'.join(lines)
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
+    ap.add_argument('--decoded', type=int, default=32, help='--views: decoded frames per clip')
+    ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
     ap.add_argument('--randaug', action='store_true', help='time the RandAugment kernels instead (-> profiles/clip_randaug_bench.txt)')
-    ap.add_argument('--clips', type=int, default=96)
+    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views')
     ap.add_argument('--frames', type=int, default=8)
     ap.add_argument('--src', type=int, nargs=2, default=(256, 340))
     ap.add_argument('--size', type=int, default=224)
@@ -174,9 +257,13 @@ def main():
     ap.add_argument('--step-ms', type=float, default=None)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
+    if a.clips is None:
+        a.clips = 32 if a.views else 96
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
+        a.out = os.path.join(ROOT, 'profiles', 'clip_views_bench.txt' if a.views else 'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.views:
+        return views_main(a)
     if a.randaug:
         return randaug_main(a)
     dev = 'cuda:0'

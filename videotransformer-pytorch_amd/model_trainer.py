@@ -310,6 +310,8 @@ class VideoTransformer(pl.LightningModule):
         if not self.do_test:
             return
         inputs, labels = self.parse_batch(batch, train=False)
+        if inputs.ndim == 6:                             # [B, n_crops, ...] as ThreeCrop stacks the views: crop b * n_crops + v
+            inputs = inputs.reshape((-1,) + tuple(inputs.shape[2:]))
         preds = self.cls_head(self.model(inputs))
         preds = preds.view(-1, self.n_crops, self.configs.num_class).mean(1)     # average the crops of a clip
         self.test_top1_acc(preds, labels)

@@ -201,9 +201,19 @@ RANDAUG_SIGNATURES = {
     'vtx_clip_equalize_u8': (ci, [ci, ci, ci, ci, vp, vp, vp, sz, vp]),
 }
 
+# libvtx_views.so (include/vtx_views.h, csrc/views.hip): frame selection + resize + crops, the fourth library.  Must list every symbol the header declares.
+VIEWS_LIB_PATH = os.environ.get('VTX_VIEWS_LIB', os.path.join(_PKG, 'libvtx_views.so'))
+VIEWS_MAX = 8
+VIEWS_SIGNATURES = {
+    'vtx_views_version': (ci, []),
+    'vtx_views_last_error_string': (C.c_char_p, []),
+    'vtx_clip_views_u8': (ci, [ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+}
+
 _lib = None
 _aug = None
 _randaug = None
+_views = None
 
 
 class VtxError(RuntimeError):
@@ -266,6 +276,34 @@ def randaug_call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.vtx_randaug_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def load_views():
+    """Load libvtx_views.so and bind every symbol of include/vtx_views.h.  Raises if anything is missing: there is no fallback."""
+    global _views
+    if _views is not None:
+        return _views
+    if not os.path.isfile(VIEWS_LIB_PATH):
+        raise VtxError(f'libvtx_views.so not found at {VIEWS_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(VIEWS_LIB_PATH)
+    for name, (res, args) in VIEWS_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_views.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _views = lib
+    return lib
+
+
+def views_call(name, *args):
+    lib = load_views()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_views_last_error_string()
         raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 

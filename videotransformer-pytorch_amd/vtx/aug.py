@@ -1,22 +1,28 @@
 """Clip augmentation on the device: the transforms of the reference's ``transforms_train`` / ``transforms_eval``
-(data_transform.py:495-574) that run before ToTensor + Normalize, on decoded uint8 clips [B,T,H,W,3].
+(data_transform.py:495-574) and of its test pipeline (data_trainer.py:108-121) that run before ToTensor + Normalize, on decoded
+uint8 clips [B,T,H,W,3].
 
     aug = vtx.aug.ClipAugment(img_size=224)             # RandomResizedCrop (bicubic) + flip + ColorJitter(0.4, 0.4, 0.4)
     aug = vtx.aug.ClipAugment(img_size=224, auto_augment='rand-m9-mstd0.5-inc1')      # ... + RandAugment() instead of the jitter
     vtx.set_input_normalization(mean, std)              # ToTensor + Normalize: fused into the patch gather
     out = model(aug(clip_u8.cuda()))
 
+    idx = vtx.aug.sample_frames(len(video), num_frames=8, frame_interval=32)           # TemporalRandomCrop + np.linspace
+    views = vtx.aug.ClipTest(img_size=224)(decoded_u8.cuda(), frames=[idx])             # Resize(256) + ThreeCrop: [B*3,T,224,224,3]
+    preds = head(model(views)).view(-1, 3, num_class).mean(1)
+
 What is random is drawn on the host (``sample_params``: torchvision's draws restated, under a ``torch.Generator``), once per
 clip -- every frame of a clip gets the same crop, flip and colour factors, as the reference's single call on a [T,C,H,W]
 tensor does.  The pixels are touched by libvtx_aug.so (csrc/aug.hip, include/vtx_aug.h): ``vtx_clip_resample_u8`` and
-``vtx_clip_jitter_u8``, and, under ``auto_augment``, by libvtx_randaug.so (csrc/randaug.hip, include/vtx_randaug.h).
+``vtx_clip_jitter_u8``, and, under ``auto_augment``, by libvtx_randaug.so (csrc/randaug.hip, include/vtx_randaug.h).  Every
+pipeline takes ``frames=``, indices into the decoded frames (``sample_frames``); with it, and in ``ClipTest`` always, the
+resampling is libvtx_views.so's (csrc/views.hip, include/vtx_views.h): frame gather, resize and all crops in one launch.
 
 ``auto_augment``: as in the reference (data_transform.py:520-521) any truthy value selects ``RandAugment()`` with its defaults
 (two ops of fourteen at magnitude bin 9 of 31, nearest interpolation, no fill) and the content of the string is ignored.  What
 is restated is torchvision's tensor path as of 0.13 .. 0.20; torchvision is not a dependency and no version is pinned.
 
-Not built: ThreeCrop, RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations, and the temporal sampling of
-the dataset.
+Not built: RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations.
 """
 import math
 from collections import namedtuple
@@ -36,6 +42,43 @@ RANDAUG_OPS = ('Identity', 'ShearX', 'ShearY', 'TranslateX', 'TranslateY', 'Rota
                'Posterize', 'Solarize', 'AutoContrast', 'Equalize')
 _RA_SIGNED = frozenset(range(1, 10))
 _RA_JITTER = {6: 0, 7: 2, 8: 1}          # Brightness, Color, Contrast -> op of vtx_clip_jitter_u8 (0 brightness, 2 saturation, 1 contrast)
+
+
+def sample_frames(total_frames, num_frames, frame_interval, generator=None):
+    """The frame indices the reference's datasets read of a video of ``total_frames`` decoded frames (dataset.py:160-162):
+    ``TemporalRandomCrop(num_frames * frame_interval)`` (data_transform.py:475-489) -- a window of that many frames that begins
+    uniformly on 0 .. max(0, total - size - 1) and is cut at the end of the video -- then
+    ``np.linspace(begin, end - 1, num_frames, dtype=int)``.  The draw comes from ``generator`` (None = torch's default CPU
+    generator), not from Python's ``random``.  -> int64 array [num_frames].  ValueError where the reference's
+    ``assert end - begin >= num_frames`` fires (it then draws another video)."""
+    total, n = int(total_frames), int(num_frames)
+    size = n * int(frame_interval)
+    if n < 1 or size < n or total < 1:
+        raise ValueError(f'sample_frames: num_frames={num_frames}, frame_interval={frame_interval}, total_frames={total_frames} must be positive')
+    rand_end = max(0, total - size - 1)
+    begin = int(torch.randint(0, rand_end + 1, (1,), generator=generator))
+    end = min(begin + size, total)
+    if end - begin < n:
+        raise ValueError(f'sample_frames: a video of {total} frames is shorter than the {n} frames asked for')
+    return np.linspace(begin, end - 1, n, dtype=int)
+
+
+def _check_frames(frames, B, Ts):
+    """frames= of the pipelines: host integers [B,T], or [T] for every clip alike, indices into the Ts decoded frames -> int32 [B,T]."""
+    if isinstance(frames, torch.Tensor):
+        if frames.is_cuda:
+            raise TypeError('frames: host integers expected (a list, an array or a CPU tensor), got a device tensor')
+        frames = frames.numpy()
+    a = np.asarray(frames)
+    if a.dtype.kind not in 'iu' or a.ndim not in (1, 2) or a.size == 0:
+        raise TypeError(f'frames: integers [T] or [{B},T] expected, got {a.dtype} {a.shape}')
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (B, a.shape[0]))
+    if a.shape[0] != B:
+        raise ValueError(f'frames: {a.shape[0]} rows for {B} clips')
+    if a.min() < 0 or a.max() >= Ts:
+        raise ValueError(f'frames: indices {int(a.min())} .. {int(a.max())} outside the {Ts} decoded frames')
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def _uniform(lo, hi, generator):
@@ -258,8 +301,10 @@ def _randaug_plan(draws, H, W):
     return plan
 
 
-def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
-    """Tables (and colour / RandAugment records) to the device in one copy, then the kernels."""
+def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None, lefts=None):
+    """Tables (and colour / RandAugment records) to the device in one copy, then the kernels.  With ``frames`` (int32 [B,T]) or
+    ``lefts`` (int32 [B,V]: the x tables then cover the whole resized row and out_hw[1] is the width of a view) the resampling is
+    clip_views_u8's, and its [B,V,T,H,W,3] is returned as [B*V,T,H,W,3]."""
     xf, xc, xw = _tables(xspecs, mode, antialias)
     yf, yc, yw = _tables(yspecs, mode, antialias)
     parts = [xf, xc, xw.view(np.int32), yf, yc, yw.view(np.int32)]
@@ -277,13 +322,24 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None):
     plan = _randaug_plan(draws, out_hw[0], out_hw[1]) if draws is not None and any(d.randaug for d in draws) else []
     for _, recs in plan:
         parts += [r.view(np.int32) for r in recs]
+    gather = frames is not None or lefts is not None
+    if gather:
+        if lefts is None:
+            lefts = np.zeros((len(xspecs), 1), dtype=np.int32)
+        parts += [lefts] + ([frames] if frames is not None else [])
     dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.device)
     views, at = [], 0
     for p in parts:
         views.append(dev[at:at + p.size].view(p.shape))
         at += p.size
     f32 = lambda t: t.view(torch.float32)
-    out = ops.clip_resample_u8(clips, out_hw, (views[0], views[1], f32(views[2])), (views[3], views[4], f32(views[5])))
+    xtab, ytab = (views[0], views[1], f32(views[2])), (views[3], views[4], f32(views[5]))
+    if gather:
+        at = len(parts) - (1 if frames is None else 2)
+        out = ops.clip_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab)
+        out = out.view((-1,) + tuple(out.shape[2:]))
+    else:
+        out = ops.clip_resample_u8(clips, out_hw, xtab, ytab)
     if jitter:
         ops.clip_jitter_u8_(out, views[6], f32(views[7]))
     at = 8 if jitter else 6
@@ -325,8 +381,12 @@ class ClipAugment:
         _jitter_ranges(color_jitter)
         self.interpolation, self.antialias = interpolation, bool(antialias)
 
-    def __call__(self, clips_u8, generator=None, params=None):
+    def __call__(self, clips_u8, generator=None, params=None, frames=None):
+        """``frames``: host integers [B,T] (or [T] for every clip alike), the decoded frames to take (``sample_frames``); the result
+        is that of the call on ``clips_u8[b, frames[b]]`` under the same draws, without the gathered copy."""
         B, Hs, Ws = _check_clips(clips_u8)
+        if frames is not None:
+            frames = _check_frames(frames, B, clips_u8.shape[1])
         if params is None:
             params = sample_params(B, (Hs, Ws), self.scale, self.ratio, self.hflip, self.color_jitter, generator,
                                    auto_augment=self.auto_augment, out_hw=self.out_hw)
@@ -334,7 +394,7 @@ class ClipAugment:
         H, W = self.out_hw
         xs = [(Ws, d.left, d.width, W, d.flip, 0, W) for d in params]
         ys = [(Hs, d.top, d.height, H, False, 0, H) for d in params]
-        return _run(clips_u8, xs, ys, self.out_hw, self.interpolation, self.antialias, params)
+        return _run(clips_u8, xs, ys, self.out_hw, self.interpolation, self.antialias, params, frames=frames)
 
 
 class ClipEval:
@@ -354,8 +414,11 @@ class ClipEval:
         new_short, new_long = self.scale_size, int(self.scale_size * long / short)
         return (new_long, new_short) if Ws <= Hs else (new_short, new_long)
 
-    def __call__(self, clips_u8):
+    def __call__(self, clips_u8, frames=None):
+        """``frames``: as ClipAugment's."""
         B, Hs, Ws = _check_clips(clips_u8)
+        if frames is not None:
+            frames = _check_frames(frames, B, clips_u8.shape[1])
         Hr, Wr = self.resized_hw(Hs, Ws)
         S = self.img_size
         if Hr < S or Wr < S:
@@ -363,4 +426,53 @@ class ClipEval:
         top, left = int(round((Hr - S) / 2.0)), int(round((Wr - S) / 2.0))
         xs = [(Ws, 0, Ws, Wr, False, left, S)] * B
         ys = [(Hs, 0, Hs, Hr, False, top, S)] * B
-        return _run(clips_u8, xs, ys, (S, S), self.interpolation, self.antialias)
+        return _run(clips_u8, xs, ys, (S, S), self.interpolation, self.antialias, frames=frames)
+
+
+class ClipTest:
+    """The reference's test pipeline (data_trainer.py:108-121) without ToTensor + Normalize: ``Resize(short side short_side)``, then
+    ``ThreeCrop(img_size)`` (data_transform.py:412-461) -- three img_size x img_size windows of the resized frame that share the
+    rows from (Hr - S) // 2 and begin at columns 0, Wr - S and (Wr - S) // 2: left, right, centre, the order the reference stacks
+    them in.  One launch: each column of the resized frame that a window holds is resampled once, with the tables of the whole
+    resized frame, and stored to every window that holds it.  uint8 CUDA [B,Ts,Hs,Ws,3] -> uint8 CUDA [B*3,T,S,S,3], view v of clip
+    b in row b*3 + v: what ``test_step``'s ``preds.view(-1, n_crops, num_class).mean(1)`` averages.  (The reference's own collate
+    yields [B,3,T,C,H,W], which its models cannot take; ``test_step`` here flattens such a batch.)
+
+    ``interpolation='bilinear'`` is the default of the torchvision ``Resize`` the pipeline calls.  ``antialias``: torchvision's
+    default for tensors changed between versions (off up to 0.16, on from 0.17), so it is an argument here; torchvision is not a
+    dependency and no version is pinned."""
+    n_crops = 3
+
+    def __init__(self, img_size=224, short_side=256, interpolation='bilinear', antialias=False):
+        self.img_size, self.short_side = int(img_size), int(short_side)
+        if self.img_size < 1 or self.short_side < 1:
+            raise ValueError(f'ClipTest: img_size={img_size} and short_side={short_side} must be positive')
+        ops._resample_mode(interpolation)
+        self.interpolation, self.antialias = interpolation, bool(antialias)
+
+    def resized_hw(self, Hs, Ws):
+        """torchvision Resize(int): the short side becomes short_side, the long side int(short_side * long / short)."""
+        short, long = (Ws, Hs) if Ws <= Hs else (Hs, Ws)
+        new_short, new_long = self.short_side, int(self.short_side * long / short)
+        return (new_long, new_short) if Ws <= Hs else (new_short, new_long)
+
+    def offsets(self, Hs, Ws):
+        """-> (top, (left, right, centre) first columns) of the three windows in the resized frame."""
+        Hr, Wr = self.resized_hw(Hs, Ws)
+        S = self.img_size
+        if S > Hr or S > Wr:
+            raise ValueError('Requested crop size {} is bigger than input size {}'.format(S, (Hr, Wr)))
+        return (Hr - S) // 2, (0, Wr - S, (Wr - S) // 2)
+
+    def __call__(self, clips_u8, frames=None):
+        """``frames``: as ClipAugment's; None takes every frame."""
+        B, Hs, Ws = _check_clips(clips_u8)
+        if frames is not None:
+            frames = _check_frames(frames, B, clips_u8.shape[1])
+        Hr, Wr = self.resized_hw(Hs, Ws)
+        top, lefts = self.offsets(Hs, Ws)
+        S = self.img_size
+        xs = [(Ws, 0, Ws, Wr, False, 0, Wr)] * B
+        ys = [(Hs, 0, Hs, Hr, False, top, S)] * B
+        return _run(clips_u8, xs, ys, (S, S), self.interpolation, self.antialias, frames=frames,
+                    lefts=np.tile(np.array(lefts, dtype=np.int32), (B, 1)))

@@ -756,6 +756,68 @@ def clip_equalize_u8_(clip, sel):
     return _randaug_two_pass('clip_equalize_u8', 'clip_equalize', clip, sel)
 
 
+# ------------------------------------------------- test-time views (csrc/views.hip -> libvtx_views.so)
+def _views_index(t, B, lo, hi, what, device):
+    """frames / left: an int32 [B,n] device tensor is taken as it is (the kernel clamps what it reads; whoever built it validated
+    it); host values -- a CPU integer tensor, an array or nested lists -- are checked against lo <= v <= hi and uploaded."""
+    import numpy as np
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        need_cuda(t)
+        if t.dtype != torch.int32 or t.ndim != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
+            raise TypeError(f'clip_views_u8: {what} must be int32 [{B},n] contiguous, got {t.dtype} {tuple(t.shape)}')
+        return t
+    a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if a.dtype.kind not in 'iu' or a.ndim != 2 or a.shape[0] != B or a.shape[1] < 1:
+        raise TypeError(f'clip_views_u8: {what} must be integers [{B},n], got {a.dtype} {a.shape}')
+    if a.min() < lo or a.max() > hi:
+        raise ValueError(f'clip_views_u8: {what} must lie in {lo} .. {hi}, got {int(a.min())} .. {int(a.max())}')
+    return upload_i32(a, device).view(a.shape)
+
+
+def clip_views_u8(src, frames, left, width, xtab, ytab, out=None):
+    """Frame selection, resize and V crops of ``width`` columns in one launch: src uint8 [B,Ts,Hs,Ws,3] -> uint8 [B,V,T,H,width,3],
+    view v of clip b = columns left[b,v] .. left[b,v] + width of the resized frames src[b, frames[b]].  frames: [B,T] indices into
+    Ts, or None for every frame; left: [B,V], V <= 8 (both: int32 device tensors, or host integers, which are validated and
+    uploaded).  xtab = (first [B,Wr] int32, count [B,Wr] int32, weights [B,Wr,K] float32) device tensors for ALL columns of the
+    resized frame, ytab likewise for the H output rows.  Byte for byte clip_resample_u8 on the gathered frames, sliced.
+    ``out``: a contiguous uint8 [B,V,T,H,width,3] device tensor to write into."""
+    _check_u8_clip(src, 'clip_views_u8')
+    src = src.contiguous()
+    B, Ts, Hs, Ws, _ = src.shape
+    W = int(width)
+    for tab in (xtab, ytab):
+        f, c, w = tab
+        need_cuda(f, c, w)
+        n = f.shape[1] if f.ndim == 2 else -1
+        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
+                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n) or n < 1 or w.shape[2] < 1
+                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
+            raise TypeError(f'clip_views_u8: a table is (int32 [{B},n], int32 [{B},n], float32 [{B},n,taps]), contiguous')
+    Wr, H = xtab[0].shape[1], ytab[0].shape[1]
+    if not 0 < W <= Wr:
+        raise ValueError(f'clip_views_u8: views of {W} columns do not fit the resized row of {Wr}')
+    left = _views_index(left, B, 0, Wr - W, f'left (left + width <= {Wr})', src.device)
+    V = left.shape[1]
+    if V > _lib.VIEWS_MAX:
+        raise ValueError(f'clip_views_u8: {V} views, at most {_lib.VIEWS_MAX}')
+    if frames is None:
+        T = Ts
+    else:
+        frames = _views_index(frames, B, 0, Ts - 1, f'frame indices into {Ts} frames', src.device)
+        T = frames.shape[1]
+    if out is None:
+        out = torch.empty(B, V, T, H, W, 3, dtype=torch.uint8, device=src.device)
+    else:
+        need_cuda(out)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (B, V, T, H, W, 3) or not out.is_contiguous():
+            raise TypeError(f'clip_views_u8: out must be a contiguous uint8 {(B, V, T, H, W, 3)} tensor, got {out.dtype} {tuple(out.shape)}')
+    with _timed('clip_views', nbytes=B * T * Hs * Ws * 3 + out.numel(), key=f'{B}x{T}/{Ts} {Hs}x{Ws}->{V}x{H}x{W}'):
+        _lib.views_call('vtx_clip_views_u8', B, Ts, T, Hs, Ws, H, Wr, V, W, ptr(src), ptr(out), ptr(frames), ptr(left),
+                        ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]), xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]), ptr(ytab[2]),
+                        ytab[2].shape[2], stream())
+    return out
+
+
 # ------------------------------------------------- clip-batch mixing, accuracy (csrc/head.hip)
 def mixup_batch_(x, lam):
     """In place: x[b] = x[b]*lam + x[B-1-b]*(1-lam) on a contiguous fp32 [B, ...] batch (reference mixup.py:112-113)."""
