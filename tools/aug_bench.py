@@ -23,6 +23,13 @@ ThreeCrop, bilinear), `vtx.ops.clip_views_u8` against the composition the other 
 of the frames, three `clip_resample_u8` passes, one stacking copy -- in alternating rounds of the same run, after checking that
 both give the same bytes.  256x340 sources make Resize(256) the identity, so a second block repeats it from 240x320 sources
 (-> 256x341, a real resize).
+
+    python tools/aug_bench.py --mix [--out profiles/clip_mix_bench.txt]
+
+times Mixup / CutMix on uint8 clips (csrc/mix.hip) at 96 clips x 8 frames x 224x224, patch 16, bf16 rows: (a) the mixing gather
+`vtx_patch_rows_mix_u8`, (b) the plain gather `vtx_patch_rows_u8` on the same clips (the floor), (c) the float route -- normalise
+with torch, `ops.mixup_batch_`, `ops.patch_rows` -- after checking that (a) and (c) give the same rows; and `cutmix_batch_u8_`
+for a half-area box against `ops.cutmix_batch_` on the float batch.  All paths in alternating rounds of one run.
 """
 import argparse
 import os
@@ -240,8 +247,127 @@ def views_main(a):
         f.write(text)
 
 
+def mix_main(a):
+    dev = 'cuda:0'
+    B, T, S, k, ps = a.clips, a.frames, a.size, a.sets, 16
+    mean, std = [0.45, 0.456, 0.406], [0.225, 0.224, 0.229]
+    lam = 0.3
+    g = torch.Generator().manual_seed(0)
+    clips = [torch.randint(0, 256, (B, T, S, S, 3), generator=g, dtype=torch.uint8).to(dev) for _ in range(k)]
+    n = clips[0].numel()
+    m_dev = torch.tensor(mean, device=dev).view(1, 1, 3, 1, 1)
+    s_dev = torch.tensor(std, device=dev).view(1, 1, 3, 1, 1)
+    c255 = torch.tensor(255.0, device=dev)                   # a device tensor: a true division, not a product with 1/255
+    xf = torch.empty(B, T, 3, S, S, dtype=torch.float32, device=dev)
+
+    def normalise(i, out=xf):
+        out.copy_(clips[i % k].permute(0, 1, 4, 2, 3))        # uint8 channels-last -> float32 planes in one pass
+        return out.div_(c255).sub_(m_dev).div_(s_dev)
+
+    def fused(i):
+        return ops.patch_rows(ops.MixedClip(clips[i % k], lam), torch.bfloat16, ps, 1, frame_major=False)
+
+    def plain(i):
+        return ops.patch_rows(clips[i % k], torch.bfloat16, ps, 1, frame_major=False)
+
+    def today(i):
+        x = normalise(i)
+        ops.mixup_batch_(x.view(B, -1, S, S), lam)
+        return ops.patch_rows(x, torch.bfloat16, ps, 1, frame_major=False)
+    floats = [normalise(i, torch.empty_like(xf)) for i in range(k)]
+
+    def today_mix_and_gather(i):                               # without the normalisation: 8 + 6 bytes per sample
+        x = floats[i % k]
+        ops.mixup_batch_(x.view(B, -1, S, S), lam)
+        return ops.patch_rows(x, torch.bfloat16, ps, 1, frame_major=False)
+    box = (33, 191, 35, 194)                                   # 158 x 159 of 224 x 224: half the area, no edge on a 4-byte boundary
+    if S != 224:
+        box = (S // 7, S // 7 + int(S * 0.7071), S // 6, S // 6 + int(S * 0.7071))
+    box_samples = B * T * (box[1] - box[0]) * (box[3] - box[2]) * 3
+
+    def cut_u8(i):
+        return ops.cutmix_batch_u8_(clips[i % k], *box)
+
+    def cut_f32(i):
+        return ops.cutmix_batch_(floats[i % k].view(B, -1, S, S), *box)
+
+    vtx.set_input_normalization(mean, std)
+    # the same rows?  exactly, on four clips normalised on the CPU (the reference's ToTensor + Normalize), and on the whole batch
+    # normalised by the torch expression that is timed
+    small = clips[0][[0, 1, B - 2, B - 1]].contiguous()
+    xs = small.cpu().permute(0, 1, 4, 2, 3).float().div(255)
+    xs = xs.sub(torch.tensor(mean).view(1, 1, 3, 1, 1)).div(torch.tensor(std).view(1, 1, 3, 1, 1)).contiguous().to(dev)
+    ops.mixup_batch_(xs.view(4, -1, S, S), lam)
+    same = {}
+    for dt_ in (torch.float32, torch.bfloat16):
+        same[dt_] = torch.equal(ops.patch_rows(ops.MixedClip(small, lam), dt_, ps, 1, frame_major=False), ops.patch_rows(xs, dt_, ps, 1, frame_major=False))
+        assert same[dt_], f'vtx_patch_rows_mix_u8 and normalise + mixup_batch_ + patch_rows differ ({dt_})'
+    same_dev = torch.equal(fused(0), today(0))
+    cut_a = clips[0].clone()
+    ops.cutmix_batch_u8_(cut_a, *box)
+    cut_b = normalise(0, torch.empty_like(xf))
+    ops.cutmix_batch_(cut_b.view(B, -1, S, S), *box)
+    same_cut = torch.equal(ops.patch_rows(cut_a, torch.float32, ps, 1, frame_major=False), ops.patch_rows(cut_b, torch.float32, ps, 1, frame_major=False))
+    assert same_cut, 'cutmix_batch_u8_ and cutmix_batch_ on the normalised clip give different rows'
+    del cut_a, cut_b
+
+    paths = [(fused, []), (plain, []), (today, []), (today_mix_and_gather, []), (cut_u8, []), (cut_f32, [])]
+    for i in range(a.warmup):
+        for fn, _ in paths:
+            fn(i)
+    torch.cuda.synchronize()
+    for r in range(a.rounds):                                  # alternating: what else runs on the machine hits all alike
+        for fn, acc in paths:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            e1.record()
+            e1.synchronize()
+            acc.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+    vtx.set_input_normalization(None, None)
+    lines = [f'Mixup / CutMix on uint8 clips, {B} clips x {T} frames x {S}x{S}, patch {ps}, bf16 rows, lam {lam}; {torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} calls per path, the paths in alternating rounds of one run, after {a.warmup} warm-up calls each, HIP events; '
+             f'{k} clip sets of {n / 2**20:.0f} MiB in rotation (together larger than the 256 MiB Infinity Cache)',
+             f'same rows from (a) and (c): fp32 {same[torch.float32]}, bf16 {same[torch.bfloat16]} on four clips normalised on the host; '
+             f'{same_dev} on the whole batch with the torch normalisation timed below; CutMix on bytes = CutMix on floats: {same_cut}',
+             'bytes = what each path has to move per sample (one colour value of one pixel), every pass counted once',
+             '']
+    med = {}
+
+    def row(name, key, us, per_sample, what, samples=n):
+        m, lo = statistics.median(us), min(us)
+        nbytes = per_sample * samples
+        med[key] = m
+        lines.append(f'{name:<46} median {m:8.1f} us  min {lo:8.1f} us  {nbytes / 1e6:7.1f} MB ({what})  {nbytes / m / 1e6:5.2f} TB/s')
+    row('(a) vtx_patch_rows_mix_u8', 'a', paths[0][1], 3, '1 read + 2 written: one thread serves both clips of a pair')
+    row('(b) vtx_patch_rows_u8 (no mixing: the floor)', 'b', paths[1][1], 3, '1 read + 2 written')
+    row('(c) torch normalise + mixup_batch_ + patch_rows', 'c', paths[2][1], 5 + 3 * 8 + 8 + 6,
+        'copy to float 1 + 4, three in-place passes 3 x 8, mix 4 + 4, gather 4 + 2; one fused normalising pass would make it 19')
+    row('    mixup_batch_ + patch_rows alone', 'c2', paths[3][1], 8 + 6, 'mix 4 + 4, gather 4 + 2: (c) with a free normalisation')
+    lines.append(f'(a) / (b) = {med["a"] / med["b"]:.3f}   (a) / (c) = {med["a"] / med["c"]:.3f}   (a) / (mix + gather alone) = {med["a"] / med["c2"]:.3f}'
+                 + ('' if med['a'] < med['c'] else '   <-- the fused gather is SLOWER than the route it replaces'))
+    if med['a'] > 2 * med['b']:
+        lines.append('(a) takes more than twice (b).  From the code it has no second read stream (one thread serves both clips of a pair: 1 byte read per '
+                     'sample, as (b)) and divides as often per sample as (b): neither of the two explains it')
+    elif med['a'] < med['b']:
+        lines.append('(a) is below its floor (b): the same bytes and the same two divisions per sample, but patch_rows_u8_kernel (csrc/elementwise.hip, not '
+                     'changed here) writes its rows with one 2-byte store per element where (a) stores 16 bytes at a time')
+    lines.append('')
+    row(f'cutmix_batch_u8_, box {box}', 'ca', paths[4][1], 2, 'both partners read + written, 1 byte each', box_samples)
+    row(f'cutmix_batch_ on the float batch, box {box}', 'cb', paths[5][1], 8, 'both partners read + written, 4 bytes each', box_samples)
+    lines.append(f'bytes / floats = {med["ca"] / med["cb"]:.3f} of the time, 0.250 of the bytes')
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+    assert med['a'] < med['c'], 'the fused gather must beat normalise + mix + gather'
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--mix', action='store_true', help='time Mixup / CutMix on uint8 clips against the float route (-> profiles/clip_mix_bench.txt)')
     ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
     ap.add_argument('--decoded', type=int, default=32, help='--views: decoded frames per clip')
     ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
@@ -260,8 +386,11 @@ def main():
     if a.clips is None:
         a.clips = 32 if a.views else 96
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'clip_views_bench.txt' if a.views else 'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
+        a.out = os.path.join(ROOT, 'profiles', 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
+                             'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.mix:
+        return mix_main(a)
     if a.views:
         return views_main(a)
     if a.randaug:

@@ -8,6 +8,11 @@ Split in two halves:
     and the generator state with the reference's class);
   * the DEVICE half applies the plan in place, one pass each: ``vtx_mixup_batch``, ``vtx_cutmix_batch``,
     ``vtx_mixup_target`` -- bit-identical to the reference's ATen arithmetic (tests/test_gpu_head.py).
+Beyond the reference, ``Mixup.__call__`` also takes the decoded uint8 clip [B,T,H,W,3] of ``vtx.aug`` (libvtx_mix.so,
+csrc/mix.hip), with the same draw from ``np.random``: CutMix swaps the box of bytes in place (``vtx_cutmix_batch_u8`` --
+Normalize acts per sample, so it commutes with the swap) and returns the uint8 tensor; Mixup returns a ``vtx.MixedClip(x,
+lam)``, which the model's patch gather normalises and mixes on the fly (``vtx_patch_rows_mix_u8``) -- the mixed float
+batch is never stored, and its rows are the same bits as on the float route (tests/test_gpu_mix.py).
 CPU tensors raise (vtx.ops.need_cuda): this package has no host fallback.
 """
 import numpy as np
@@ -56,7 +61,9 @@ def cutmix_bbox_and_lam(img_shape, lam, correct_lam=True, count=None):
 
 class Mixup:
     """Batch-mode Mixup / CutMix with label smoothing (reference :59-126; same constructor).
-    ``__call__(x [B,T,C,H,W] or [B,C,H,W], target [B]) -> (x mixed in place, soft targets [B, num_classes])``."""
+    ``__call__(x [B,T,C,H,W] or [B,C,H,W], target [B]) -> (x mixed in place, soft targets [B, num_classes])``;
+    a uint8 [B,T,H,W,3] x comes back with its CutMix box swapped in place, as ``vtx.MixedClip(x, lam)`` for Mixup (x
+    untouched), or as it is when nothing is mixed."""
 
     def __init__(self, mixup_alpha=0.8, cutmix_alpha=1.0, prob=1.0, switch_prob=0.5, mode='batch', correct_lam=True,
                  label_smoothing=0.1, num_classes=1000):
@@ -91,10 +98,26 @@ class Mixup:
         ops.need_cuda(x, target)
         if len(x) % 2:
             raise AssertionError('Batch size should be even when using this')
+        if x.dtype == torch.uint8:
+            return self._call_u8(x, target)
         planes = x.view(x.shape[0], -1, x.shape[-2], x.shape[-1]) if x.ndim == 5 else x        # a view: mixed in place
         lam, box = self.draw(planes.shape)
         if box is not None:
             ops.cutmix_batch_(planes, *box)
         elif lam != 1.:
             ops.mixup_batch_(planes, lam)
+        return x, ops.mixup_target(target, self.num_classes, lam, self.label_smoothing)
+
+    def _call_u8(self, x, target):
+        """The decoded uint8 batch [B,T,H,W,3] of vtx.aug, in front of ToTensor + Normalize (fused into the model's patch
+        gather).  The same draw from the same frame shape (H, W) -- not the tensor's last two dimensions, which are (W, 3)."""
+        if x.ndim != 5 or x.shape[-1] != 3:
+            raise ValueError(f'Mixup: a uint8 batch must be the channels-last clip [B,T,H,W,3], got {tuple(x.shape)}')
+        lam, box = self.draw((x.shape[0], x.shape[1] * 3, x.shape[2], x.shape[3]))
+        if box is not None:
+            if not x.is_contiguous():
+                raise ValueError('Mixup: CutMix swaps the box in place, the uint8 batch must be contiguous')
+            ops.cutmix_batch_u8_(x, *box)                      # bytes swapped before Normalize = floats swapped after it
+        elif lam != 1.:
+            x = ops.MixedClip(x.contiguous(), lam)             # x itself stays as it is: the gather mixes
         return x, ops.mixup_target(target, self.num_classes, lam, self.label_smoothing)

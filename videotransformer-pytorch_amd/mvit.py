@@ -238,6 +238,9 @@ class PatchEmbeding(nn.Module):
         self.patch_model = patch_model
 
     def forward(self, x):
+        if isinstance(x, vtx.MixedClip):
+            raise TypeError('MViT PatchEmbeding: a MixedClip (Mixup of a uint8 batch) is not supported by the im2col stem; '
+                            'mix the normalised float batch instead (TimeSformer and ViViT take a MixedClip)')
         # the reference hands over clip.transpose(1, 2) ([B,C,T,H,W] view of the [B,T,C,H,W] batch): undo the view
         clip = x.transpose(1, 2)
         pm = self.patch_model

@@ -436,7 +436,8 @@ class MaskFeat(nn.Module):
                                   (B, tq, hq, wq, Cc, g))
 
     def forward_features(self, x, mask=None):
-        x = self.patch_embed(x.transpose(1, 2))
+        # (a vtx.MixedClip goes through as it is: PatchEmbeding raises the TypeError that says the MViT stem does not take one)
+        x = self.patch_embed(x if isinstance(x, vtx.MixedClip) else x.transpose(1, 2))
         if mask is not None:
             x = self.blend_mask_tokens(x, mask)
         return self.mvit(x)

@@ -210,10 +210,20 @@ VIEWS_SIGNATURES = {
     'vtx_clip_views_u8': (ci, [ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
 }
 
+# libvtx_mix.so (include/vtx_mix.h, csrc/mix.hip): Mixup / CutMix on uint8 clips, the fifth library.  Must list every symbol the header declares.
+MIX_LIB_PATH = os.environ.get('VTX_MIX_LIB', os.path.join(_PKG, 'libvtx_mix.so'))
+MIX_SIGNATURES = {
+    'vtx_mix_version': (ci, []),
+    'vtx_mix_last_error_string': (C.c_char_p, []),
+    'vtx_cutmix_batch_u8': (ci, [ci, ci, ci, ci, vp, ci, ci, ci, ci, vp]),
+    'vtx_patch_rows_mix_u8': (ci, [ci, ci, ci, ci, ci, ci, ci, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), cf, cf, vp, cl, ci, vp]),
+}
+
 _lib = None
 _aug = None
 _randaug = None
 _views = None
+_mix = None
 
 
 class VtxError(RuntimeError):
@@ -304,6 +314,34 @@ def views_call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.vtx_views_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def load_mix():
+    """Load libvtx_mix.so and bind every symbol of include/vtx_mix.h.  Raises if anything is missing: there is no fallback."""
+    global _mix
+    if _mix is not None:
+        return _mix
+    if not os.path.isfile(MIX_LIB_PATH):
+        raise VtxError(f'libvtx_mix.so not found at {MIX_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(MIX_LIB_PATH)
+    for name, (res, args) in MIX_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_mix.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _mix = lib
+    return lib
+
+
+def mix_call(name, *args):
+    lib = load_mix()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_mix_last_error_string()
         raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 

@@ -7,6 +7,10 @@ uint8 clips [B,T,H,W,3].
     vtx.set_input_normalization(mean, std)              # ToTensor + Normalize: fused into the patch gather
     out = model(aug(clip_u8.cuda()))
 
+    mixup_fn = mixup.Mixup(num_classes=num_class)       # the -mixup flag (model_trainer.py:87-88,142-143), on the same uint8 clips:
+    inputs, soft = mixup_fn(aug(clip_u8.cuda()), labels)  # CutMix swaps the box of bytes in place; Mixup returns a vtx.MixedClip,
+    out = model(inputs)                                 # which the patch gather normalises and mixes on the fly (libvtx_mix.so)
+
     idx = vtx.aug.sample_frames(len(video), num_frames=8, frame_interval=32)           # TemporalRandomCrop + np.linspace
     views = vtx.aug.ClipTest(img_size=224)(decoded_u8.cuda(), frames=[idx])             # Resize(256) + ThreeCrop: [B*3,T,224,224,3]
     preds = head(model(views)).view(-1, 3, num_class).mean(1)

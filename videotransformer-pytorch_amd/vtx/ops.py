@@ -526,8 +526,41 @@ def set_input_normalization(mean, std):
     _input_norm = (mean, std)
 
 
+class MixedClip:
+    """The Mixup of a decoded uint8 batch, not yet computed: stands for the float batch
+    ``n(clip) * lam + n(clip.flip(0)) * (1 - lam)`` the reference's Mixup would have produced from the normalised clips
+    (mixup.py:111-113; n = ToTensor + Normalize, set_input_normalization).  A mixed clip has no uint8 form and is never
+    stored: the patch gather reads both partners and writes the mixed rows (patch_rows -> vtx_patch_rows_mix_u8).
+    A plain carrier, not a tensor: ``clip`` (contiguous uint8 CUDA [B,T,H,W,3], B even -- not copied, not modified) and
+    ``lam`` (float64).  TimeSformer and ViViT take it wherever they take a uint8 clip."""
+    __slots__ = ('clip', 'lam')
+
+    def __init__(self, clip, lam):
+        if not isinstance(clip, torch.Tensor) or clip.dtype != torch.uint8:
+            raise TypeError(f'MixedClip: a uint8 tensor is required, got {getattr(clip, "dtype", type(clip).__name__)}')
+        if clip.ndim != 5 or clip.shape[-1] != 3:
+            raise ValueError(f'MixedClip: the clip must be [B,T,H,W,3], got {tuple(clip.shape)}')
+        if clip.shape[0] % 2:
+            raise ValueError(f'MixedClip: clip b is mixed with clip B-1-b, the batch size must be even, got {clip.shape[0]}')
+        if not clip.is_contiguous():
+            raise ValueError('MixedClip: the clip must be contiguous')
+        need_cuda(clip)
+        self.clip, self.lam = clip, float(lam)
+
+    shape = property(lambda self: self.clip.shape)
+    device = property(lambda self: self.clip.device)
+    dtype = property(lambda self: self.clip.dtype)
+    is_cuda = property(lambda self: self.clip.is_cuda)
+
+    def __len__(self):
+        return len(self.clip)
+
+    def __repr__(self):
+        return f'MixedClip(uint8 {tuple(self.clip.shape)} on {self.clip.device}, lam={self.lam!r})'
+
+
 def clip_dims(clip):
-    """(B, T, C, H, W) of a float [B,T,C,H,W] or a uint8 channels-last [B,T,H,W,3] clip."""
+    """(B, T, C, H, W) of a float [B,T,C,H,W] or a uint8 channels-last [B,T,H,W,3] clip (or the MixedClip of one)."""
     if clip.dtype == torch.uint8:
         B, T, H, W, Cc = clip.shape
         if Cc != 3:
@@ -539,8 +572,23 @@ def clip_dims(clip):
 
 def patch_rows(clip, dtype, ps, ts, frame_major):
     """[B,T,C,H,W] fp32 -> [B*(T/ts)*P, C*ts*ps*ps] rows in `dtype`; a uint8 [B,T,H,W,3] clip is
-    normalised on the fly (ToTensor + Normalize of the reference, see set_input_normalization)."""
+    normalised on the fly (ToTensor + Normalize of the reference, see set_input_normalization), and the
+    MixedClip of one is normalised and mixed on the fly."""
     need_cuda(clip)
+    if isinstance(clip, MixedClip):
+        import numpy as np
+        if _input_norm is None:
+            raise ValueError('MixedClip: call vtx.set_input_normalization(mean, std) first')
+        B, T, Cc, H, W = clip_dims(clip)
+        K = Cc * ts * ps * ps
+        rows = torch.empty(B * (T // ts) * (H // ps) * (W // ps), K, dtype=dtype, device=clip.device)
+        mean = (C.c_float * 3)(*_input_norm[0])
+        std = (C.c_float * 3)(*_input_norm[1])
+        with _timed('patch_rows', nbytes=clip.clip.numel() + rows.numel() * rows.element_size(), key=f'mix u8 {B}x{T}'):
+            # lam and 1 - lam as mixup_batch_ hands them over: 1 - lam in float64, each rounded once
+            _lib.mix_call('vtx_patch_rows_mix_u8', _DT[dtype], B, T, H, W, ps, ts, ptr(clip.clip), mean, std,
+                          float(np.float32(clip.lam)), float(np.float32(1. - clip.lam)), ptr(rows), K, int(frame_major), stream())
+        return rows
     if clip.dtype == torch.uint8:
         if _input_norm is None:
             raise ValueError('uint8 clip: call vtx.set_input_normalization(mean, std) first')
@@ -839,6 +887,17 @@ def cutmix_batch_(x, yl, yh, xl, xh):
     B, Pn, H, W = x.shape
     call('vtx_cutmix_batch', ptr(x), B, Pn, H, W, int(yl), int(yh), int(xl), int(xh), stream())
     return x
+
+
+def cutmix_batch_u8_(clip, yl, yh, xl, xh):
+    """In place: clip[:, :, yl:yh, xl:xh] = clip.flip(0)[:, :, yl:yh, xl:xh] on a contiguous uint8 [B,T,H,W,3] batch -- CutMix
+    before ToTensor + Normalize, which act per sample (libvtx_mix.so: vtx_cutmix_batch_u8)."""
+    need_cuda(clip)
+    if clip.dtype != torch.uint8 or not clip.is_contiguous() or clip.ndim != 5 or clip.shape[-1] != 3:
+        raise TypeError('cutmix_batch_u8_: contiguous uint8 [B,T,H,W,3] batch required')
+    B, T, H, W, _ = clip.shape
+    _lib.mix_call('vtx_cutmix_batch_u8', B, T, H, W, ptr(clip), int(yl), int(yh), int(xl), int(xh), stream())
+    return clip
 
 
 def mixup_target(labels, num_classes, lam, smoothing):
