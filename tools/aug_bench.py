@@ -30,6 +30,14 @@ times Mixup / CutMix on uint8 clips (csrc/mix.hip) at 96 clips x 8 frames x 224x
 `vtx_patch_rows_mix_u8`, (b) the plain gather `vtx_patch_rows_u8` on the same clips (the floor), (c) the float route -- normalise
 with torch, `ops.mixup_batch_`, `ops.patch_rows` -- after checking that (a) and (c) give the same rows; and `cutmix_batch_u8_`
 for a half-area box against `ops.cutmix_batch_` on the float batch.  All paths in alternating rounds of one run.
+
+    python tools/aug_bench.py --stem [--out profiles/stem_u8_bench.txt]
+
+times MaskFeat's input path from uint8 clips (csrc/stem.hip) at 32 clips x 16 frames x 224x224, bf16 rows: (a) the stem gather
+`vtx_im2col3d_u8` against `vtx_im2col3d` on a float clip that is already there (the bar: not slower, within that kernel's spread
+over the rounds) and against the route it replaces, torch normalise + `vtx_im2col3d`; (b) `vtx.hog_targets` with three centre
+frames per clip against index_select + `ops.hog_fwd` + scatter into a zeroed target.  Both pairs are checked for equal results
+first; all paths in alternating rounds of one run.
 """
 import argparse
 import os
@@ -365,15 +373,131 @@ def mix_main(a):
     assert med['a'] < med['c'], 'the fused gather must beat normalise + mix + gather'
 
 
+def stem_main(a):
+    import ctypes as C
+    from vtx import _lib
+    dev = 'cuda:0'
+    B, T, S, k = a.clips, a.frames, a.size, a.sets
+    mean, std = [0.45, 0.456, 0.406], [0.225, 0.224, 0.229]
+    k3, s3, p3 = (3, 7, 7), (2, 4, 4), (1, 3, 3)
+    K = 3 * k3[0] * k3[1] * k3[2]
+    Kp = (K + 63) // 64 * 64                                 # ConvStemFn's row width: 448
+    To, Ho, Wo = ((n + 2 * p - kk) // s + 1 for n, p, kk, s in zip((T, S, S), p3, k3, s3))
+    M = B * To * Ho * Wo
+    g = torch.Generator().manual_seed(0)
+    clips = [torch.randint(0, 256, (B, T, S, S, 3), generator=g, dtype=torch.uint8).to(dev) for _ in range(k)]
+    n = clips[0].numel()
+    m_dev = torch.tensor(mean, device=dev).view(1, 1, 3, 1, 1)
+    s_dev = torch.tensor(std, device=dev).view(1, 1, 3, 1, 1)
+    c255 = torch.tensor(255.0, device=dev)                   # a device tensor: a true division, not a product with 1/255
+    xf = torch.empty(B, T, 3, S, S, dtype=torch.float32, device=dev)
+    rows = torch.empty(M, Kp, dtype=torch.bfloat16, device=dev)
+    i3 = lambda t: (C.c_int * 3)(*t)   # noqa: E731
+    f3 = lambda t: (C.c_float * 3)(*t)   # noqa: E731
+    bf16 = ops._DT[torch.bfloat16]
+
+    def normalise(i, out=xf):
+        out.copy_(clips[i % k].permute(0, 1, 4, 2, 3))        # uint8 channels-last -> float32 planes in one pass
+        return out.div_(c255).sub_(m_dev).div_(s_dev)
+    floats = [normalise(i, torch.empty_like(xf)) for i in range(k)]
+
+    def gather_f32(x, out=rows):
+        ops.call('vtx_im2col3d', bf16, B, T, 3, S, S, i3(k3), i3(s3), i3(p3), Kp, ops.ptr(x), ops.ptr(out), ops.stream())
+        return out
+
+    def u8(i, out=rows):                                       # (a) the new gather
+        _lib.stem_call('vtx_im2col3d_u8', bf16, B, T, S, S, i3(k3), i3(s3), i3(p3), Kp, ops.ptr(clips[i % k]), f3(mean), f3(std), ops.ptr(out),
+                       ops.stream())
+        return out
+
+    def parent(i):                                             # vtx_im2col3d alone, on a float clip that is already there
+        return gather_f32(floats[i % k])
+
+    def today(i):                                              # the route (a) replaces: normalise with torch, then gather
+        return gather_f32(normalise(i))
+
+    # the same rows?  on the whole batch, against the torch normalisation that is timed (the suite holds the CPU-normalised form)
+    same = torch.equal(u8(0, torch.empty_like(rows)), today(0))
+    assert same, 'vtx_im2col3d_u8 and normalise + vtx_im2col3d give different rows'
+
+    # (b) HOG targets: three centre frames per clip
+    markers = [[[0, 2], [2, 2], [5, 2]] for _ in range(B)]     # centres 2, 6, 12 at temporal stride 2
+    flat = torch.tensor(ops.hog_center_frames(markers, T, 2), dtype=torch.int64, device=dev)
+    g16 = S // 16
+
+    def targets_new(i):
+        return vtx.hog_targets(clips[i % k], markers)
+
+    def targets_old(i):
+        frames = clips[i % k].view(B * T, S, S, 3).index_select(0, flat)
+        target = torch.zeros(B * T, g16, g16, 108, dtype=torch.float64, device=dev)
+        target.index_copy_(0, flat, ops.hog_fwd(frames))
+        return target.view(B, T, g16, g16, 108)
+    same_hog = torch.equal(targets_new(0), targets_old(0))
+    assert same_hog, 'hog_targets and index_select + hog_fwd + scatter differ'
+
+    paths = [(u8, []), (parent, []), (today, []), (targets_new, []), (targets_old, [])]
+    for i in range(a.warmup):
+        for fn, _ in paths:
+            fn(i)
+    torch.cuda.synchronize()
+    for r in range(a.rounds):                                  # alternating: what else runs on the machine hits all alike
+        for fn, acc in paths:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            e1.record()
+            e1.synchronize()
+            acc.append(e0.elapsed_time(e1) * 1e3 / a.iters)
+    row_bytes = M * Kp * 2
+    lines = [f'MaskFeat from uint8 clips, {B} clips x {T} frames x {S}x{S}, stem kernel {k3} stride {s3} padding {p3}: {M} rows x {Kp} bf16 columns; '
+             f'{torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} calls per path, the paths in alternating rounds of one run, after {a.warmup} warm-up calls each, HIP events; '
+             f'{k} clip sets of {n / 2**20:.0f} MiB (uint8) / {4 * n / 2**20:.0f} MiB (float) in rotation',
+             f'same rows from vtx_im2col3d_u8 and torch normalise + vtx_im2col3d on the whole batch: {same}; same targets from both HOG routes: {same_hog}',
+             'bytes = what each path has to move, every pass counted once; spread = (max - min) / median over the rounds',
+             '']
+    med, spread = {}, {}
+
+    def row(name, key, us, nbytes, what):
+        m, lo, hi = statistics.median(us), min(us), max(us)
+        med[key], spread[key] = m, (hi - lo) / m
+        lines.append(f'{name:<44} median {m:8.1f} us  min {lo:8.1f}  max {hi:8.1f}  spread {100 * (hi - lo) / m:4.1f} %  {nbytes / 1e6:7.1f} MB ({what})  '
+                     f'{nbytes / m / 1e6:5.2f} TB/s')
+    row('(a) vtx_im2col3d_u8', 'a', paths[0][1], n + row_bytes, 'clip bytes read, rows written')
+    row('    vtx_im2col3d on a ready float clip', 'p', paths[1][1], 4 * n + row_bytes, 'float clip read, rows written')
+    row('    torch normalise + vtx_im2col3d', 't', paths[2][1], (5 + 3 * 8) * n + 4 * n + row_bytes,
+        'copy to float 1 + 4, three in-place passes 3 x 8 per sample; then as the row above')
+    margin = spread['p'] * med['p']
+    verdict = 'not slower' if med['a'] <= med['p'] + margin else 'SLOWER'
+    lines.append(f'(a) / parent kernel alone = {med["a"] / med["p"]:.3f}   (a) / the route it replaces = {med["a"] / med["t"]:.3f}   '
+                 f'bar: (a) <= parent + its spread = {med["p"]:.1f} + {margin:.1f} us: {verdict}')
+    lines.append('')
+    sel_bytes = 3 * B * (S * S * 3 + g16 * g16 * 108 * 8)
+    tgt_bytes = B * T * g16 * g16 * 108 * 8
+    row('(b) vtx.hog_targets, 3 centre frames per clip', 'hn', paths[3][1], tgt_bytes + sel_bytes,
+        'target zeroed; selected frames read, their rows written; one index upload')
+    row('    index_select + vtx_hog_fwd + scatter', 'ho', paths[4][1], tgt_bytes + sel_bytes + 3 * B * 2 * (S * S * 3 + g16 * g16 * 108 * 8),
+        'target zeroed; frames gathered (read + write), HOG, rows scattered (read + write); index already on the device')
+    lines.append(f'(b) new / old = {med["hn"] / med["ho"]:.3f}' + ('' if med['hn'] <= med['ho'] else '   <-- hog_targets is SLOWER than the route it replaces'))
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--stem', action='store_true', help='time the uint8 stem gather and hog_targets against the float routes (-> profiles/stem_u8_bench.txt)')
     ap.add_argument('--mix', action='store_true', help='time Mixup / CutMix on uint8 clips against the float route (-> profiles/clip_mix_bench.txt)')
     ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
     ap.add_argument('--decoded', type=int, default=32, help='--views: decoded frames per clip')
     ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
     ap.add_argument('--randaug', action='store_true', help='time the RandAugment kernels instead (-> profiles/clip_randaug_bench.txt)')
-    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views')
-    ap.add_argument('--frames', type=int, default=8)
+    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views and --stem')
+    ap.add_argument('--frames', type=int, default=None, help='default 8; 16 with --stem')
     ap.add_argument('--src', type=int, nargs=2, default=(256, 340))
     ap.add_argument('--size', type=int, default=224)
     ap.add_argument('--sets', type=int, default=3)
@@ -384,11 +508,15 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.clips is None:
-        a.clips = 32 if a.views else 96
+        a.clips = 32 if a.views or a.stem else 96
+    if a.frames is None:
+        a.frames = 16 if a.stem else 8
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
+        a.out = os.path.join(ROOT, 'profiles', 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
                              'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.stem:
+        return stem_main(a)
     if a.mix:
         return mix_main(a)
     if a.views:

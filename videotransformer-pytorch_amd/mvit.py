@@ -230,7 +230,9 @@ def create_multiscale_vision_transformers(*, spatial_size, temporal_size, cls_em
 
 class PatchEmbeding(nn.Module):
     """Conv3d patch embedding of the MViT stem (reference video_transformer.py:563-584): [B,C,T,H,W] -> [B, T'H'W', D].
-    The Conv3d module holds the parameters (key ``patch_model.{weight,bias}``); the arithmetic is im2col + GEMM."""
+    The Conv3d module holds the parameters (key ``patch_model.{weight,bias}``); the arithmetic is im2col + GEMM.
+    Decoded video goes in as it is: a uint8 [B,T,H,W,3] clip (channels last, what ``vtx.aug.ClipAugment`` returns) is
+    normalised inside the gather (``vtx.set_input_normalization``) and gives the tokens of the normalised float clip bit for bit."""
 
     def __init__(self, *, patch_model=None):
         super().__init__()
@@ -241,8 +243,11 @@ class PatchEmbeding(nn.Module):
         if isinstance(x, vtx.MixedClip):
             raise TypeError('MViT PatchEmbeding: a MixedClip (Mixup of a uint8 batch) is not supported by the im2col stem; '
                             'mix the normalised float batch instead (TimeSformer and ViViT take a MixedClip)')
-        # the reference hands over clip.transpose(1, 2) ([B,C,T,H,W] view of the [B,T,C,H,W] batch): undo the view
-        clip = x.transpose(1, 2)
+        if x.dtype == torch.uint8:
+            clip = x                                     # [B,T,H,W,3]: no channel axis to move, the gather reads the bytes where they lie
+        else:
+            # the reference hands over clip.transpose(1, 2) ([B,C,T,H,W] view of the [B,T,C,H,W] batch): undo the view
+            clip = x.transpose(1, 2)
         pm = self.patch_model
         return F_.ConvStemFn.apply(clip, pm.weight, pm.bias, tuple(pm.stride), tuple(pm.padding), vtx.compute_dtype())
 

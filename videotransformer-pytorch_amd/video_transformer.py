@@ -437,7 +437,8 @@ class MaskFeat(nn.Module):
 
     def forward_features(self, x, mask=None):
         # (a vtx.MixedClip goes through as it is: PatchEmbeding raises the TypeError that says the MViT stem does not take one)
-        x = self.patch_embed(x if isinstance(x, vtx.MixedClip) else x.transpose(1, 2))
+        # (a uint8 [B,T,H,W,3] clip too: the stem's gather normalises the bytes where they lie, there is no channel axis to move)
+        x = self.patch_embed(x if isinstance(x, vtx.MixedClip) or x.dtype == torch.uint8 else x.transpose(1, 2))
         if mask is not None:
             x = self.blend_mask_tokens(x, mask)
         return self.mvit(x)

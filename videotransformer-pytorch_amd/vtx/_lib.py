@@ -219,11 +219,22 @@ MIX_SIGNATURES = {
     'vtx_patch_rows_mix_u8': (ci, [ci, ci, ci, ci, ci, ci, ci, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), cf, cf, vp, cl, ci, vp]),
 }
 
+# libvtx_stem.so (include/vtx_stem.h, csrc/stem.hip): MaskFeat from uint8 clips, the sixth library.  Must list every symbol the header declares.
+STEM_LIB_PATH = os.environ.get('VTX_STEM_LIB', os.path.join(_PKG, 'libvtx_stem.so'))
+STEM_SIGNATURES = {
+    'vtx_stem_version': (ci, []),
+    'vtx_stem_last_error_string': (C.c_char_p, []),
+    'vtx_im2col3d_u8': (ci, [ci, ci, ci, ci, ci, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), ci, vp,
+                             C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp]),
+    'vtx_hog_fwd_sel': (ci, [vp, ci, ci, ci, vp, ci, vp, sz, vp, vp]),
+}
+
 _lib = None
 _aug = None
 _randaug = None
 _views = None
 _mix = None
+_stem = None
 
 
 class VtxError(RuntimeError):
@@ -342,6 +353,34 @@ def mix_call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.vtx_mix_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def load_stem():
+    """Load libvtx_stem.so and bind every symbol of include/vtx_stem.h.  Raises if anything is missing: there is no fallback."""
+    global _stem
+    if _stem is not None:
+        return _stem
+    if not os.path.isfile(STEM_LIB_PATH):
+        raise VtxError(f'libvtx_stem.so not found at {STEM_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(STEM_LIB_PATH)
+    for name, (res, args) in STEM_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_stem.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _stem = lib
+    return lib
+
+
+def stem_call(name, *args):
+    lib = load_stem()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_stem_last_error_string()
         raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 

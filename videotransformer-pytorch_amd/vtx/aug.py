@@ -15,6 +15,11 @@ uint8 clips [B,T,H,W,3].
     views = vtx.aug.ClipTest(img_size=224)(decoded_u8.cuda(), frames=[idx])             # Resize(256) + ThreeCrop: [B*3,T,224,224,3]
     preds = head(model(views)).view(-1, 3, num_class).mean(1)
 
+    aug = vtx.aug.ClipAugment(img_size=224, scale=(0.5, 1.0), color_jitter=None)       # the mim branch (data_trainer.py:61-63)
+    clip = aug(clip_u8.cuda())                          # uint8 [B,16,224,224,3]
+    target = vtx.hog_targets(clip, cube_marker)         # HOG of each masked cube's centre frame (dataset.py:188-196), zeros elsewhere
+    pred, loss = maskfeat(clip, target, mask, cube_marker)   # the MViT stem gathers and normalises the bytes (libvtx_stem.so)
+
 What is random is drawn on the host (``sample_params``: torchvision's draws restated, under a ``torch.Generator``), once per
 clip -- every frame of a clip gets the same crop, flip and colour factors, as the reference's single call on a [T,C,H,W]
 tensor does.  The pixels are touched by libvtx_aug.so (csrc/aug.hip, include/vtx_aug.h): ``vtx_clip_resample_u8`` and

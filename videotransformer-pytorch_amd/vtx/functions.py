@@ -1397,26 +1397,39 @@ class PosEncodingFn(torch.autograd.Function):
 
 class ConvStemFn(torch.autograd.Function):
     """Overlapping, padded Conv3d patch embedding of the MViT stem (create_conv_patch_embed, reference
-    video_transformer.py:585-618, 834-843): im2col gather + GEMM, tokens [B, T'*H'*W', D] out.  clip [B,T,C,H,W]."""
+    video_transformer.py:585-618, 834-843): im2col gather + GEMM, tokens [B, T'*H'*W', D] out.  clip float [B,T,C,H,W], or
+    decoded video as it is: uint8 [B,T,H,W,3] (channels last), normalised inside the gather (vtx.set_input_normalization;
+    ops.im2col3d_u8) -- the same rows bit for bit, so everything behind them (GEMM, saved rows, backward) is one code path."""
 
     @staticmethod
     def forward(ctx, clip, conv_w, conv_b, stride, padding, dtype):
         import ctypes as C
+        u8 = clip.dtype == torch.uint8
+        if u8:
+            clip = ops._u8_clip(clip, 'ConvStemFn')      # [B,T,H,W,3] or ValueError, before anything needs the device
         ops.need_cuda(clip, conv_w)
-        clip = clip.float().contiguous()
-        B, T, Cc, H, W = clip.shape
-        D, _, KT, KH, KW = conv_w.shape
+        if u8:
+            B, T, H, W, Cc = clip.shape
+        else:
+            clip = clip.float().contiguous()
+            B, T, Cc, H, W = clip.shape
+        D, Cw, KT, KH, KW = conv_w.shape
+        if u8 and Cw != 3:
+            raise ValueError(f'ConvStemFn: a uint8 clip has 3 channels, the convolution takes {Cw}')
         K = Cc * KT * KH * KW
         Kp = (K + 63) // 64 * 64                       # whole 64-deep K tiles: the LDS-DMA GEMM kernels apply
         To = (T + 2 * padding[0] - KT) // stride[0] + 1
         Ho = (H + 2 * padding[1] - KH) // stride[1] + 1
         Wo = (W + 2 * padding[2] - KW) // stride[2] + 1
         M = B * To * Ho * Wo
-        rows = torch.empty(M, Kp, dtype=dtype, device=clip.device)
-        i3 = lambda t: (C.c_int * 3)(*[int(v) for v in t])   # noqa: E731
-        from . import ops as _o
-        ops.call('vtx_im2col3d', _o._DT[dtype], B, T, Cc, H, W, i3((KT, KH, KW)), i3(stride), i3(padding), Kp, ops.ptr(clip),
-                 ops.ptr(rows), ops.stream())
+        if u8:
+            rows = ops.im2col3d_u8(clip, (KT, KH, KW), stride, padding, Kp, dtype)
+        else:
+            rows = torch.empty(M, Kp, dtype=dtype, device=clip.device)
+            i3 = lambda t: (C.c_int * 3)(*[int(v) for v in t])   # noqa: E731
+            from . import ops as _o
+            ops.call('vtx_im2col3d', _o._DT[dtype], B, T, Cc, H, W, i3((KT, KH, KW)), i3(stride), i3(padding), Kp, ops.ptr(clip),
+                     ops.ptr(rows), ops.stream())
         w_pad = torch.zeros(D, Kp, dtype=torch.float32, device=conv_w.device)
         w_pad[:, :K].copy_(conv_w.detach().reshape(D, K))
         wc, _ = ops.cast_transpose(w_pad, dtype, want_c=True, want_t=False)

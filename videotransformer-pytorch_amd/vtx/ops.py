@@ -613,6 +613,38 @@ def patch_rows(clip, dtype, ps, ts, frame_major):
     return rows
 
 
+def _u8_clip(clip, who):
+    """The checks every uint8-clip entry makes, shape first (reachable without a device): contiguous uint8 CUDA [B,T,H,W,3]."""
+    if not isinstance(clip, torch.Tensor) or clip.dtype != torch.uint8:
+        raise TypeError(f'{who}: a uint8 tensor is required, got {getattr(clip, "dtype", type(clip).__name__)}')
+    if clip.ndim != 5 or clip.shape[-1] != 3:
+        raise ValueError(f'{who}: the uint8 clip must be [B,T,H,W,3] (channels last), got {tuple(clip.shape)}')
+    need_cuda(clip)
+    return clip.contiguous()
+
+
+def im2col3d_u8(clip, k3, s3, p3, Kp, dtype):
+    """uint8 [B,T,H,W,3] -> the rows [B*To*Ho*Wo, Kp] (`dtype`) of an overlapping, padded Conv3d on the normalised clip (ToTensor +
+    Normalize of the reference on the fly, see set_input_normalization; padding taps and the columns behind 3*kt*kh*kw are
+    +0): bit for bit the rows vtx_im2col3d makes of the normalised float [B,T,3,H,W] clip (vtx_im2col3d_u8, libvtx_stem.so)."""
+    clip = _u8_clip(clip, 'im2col3d_u8')
+    if _input_norm is None:
+        raise ValueError('uint8 clip: call vtx.set_input_normalization(mean, std) first')
+    B, T, H, W, _ = clip.shape
+    k3, s3, p3 = ([int(v) for v in t] for t in (k3, s3, p3))
+    if len(k3) != 3 or len(s3) != 3 or len(p3) != 3:
+        raise ValueError('im2col3d_u8: k3, s3, p3 are (t, h, w) triples')
+    To, Ho, Wo = ((n + 2 * p - k) // s + 1 if s > 0 else 0 for n, p, k, s in zip((T, H, W), p3, k3, s3))
+    rows = torch.empty(max(B * To * Ho * Wo, 0), int(Kp), dtype=dtype, device=clip.device)
+    i3 = lambda t: (C.c_int * 3)(*t)   # noqa: E731
+    mean = (C.c_float * 3)(*_input_norm[0])
+    std = (C.c_float * 3)(*_input_norm[1])
+    with _timed('im2col3d', nbytes=clip.numel() + rows.numel() * rows.element_size(), key=f'u8 {B}x{T}'):
+        _lib.stem_call('vtx_im2col3d_u8', _DT[dtype], B, T, H, W, i3(k3), i3(s3), i3(p3), int(Kp), ptr(clip), mean, std, ptr(rows),
+                       stream())
+    return rows
+
+
 def embed_table(dtype, P, T, D, bias, pos, time_embed, cls, frame_major=False):
     dev = pos.device
     E = torch.empty(P * T, D, dtype=dtype, device=dev)
@@ -648,6 +680,43 @@ def hog_fwd(frames, want_bins=False):
     with _timed('hog', nbytes=frames.numel() + out.numel() * 8, key=f'{F}x{H}x{W}'):
         call('vtx_hog_fwd', ptr(frames), F, H, W, ptr(table), table.numel() * 8, ptr(out), ptr(bins), stream())
     return (out, bins) if want_bins else out
+
+
+def hog_center_frames(cube_marker, num_frames, tstride=2):
+    """The flat frame indices b*T + centre of the centre frames of a batch's masked cubes, sorted, each once: the centre of
+    marker [start, span] is start*tstride + span*tstride//2, the expression of video_transformer.center_frame_mask (reference
+    video_transformer.py:889-896).  A clip with no marker contributes none; a centre outside 0 .. T-1 raises ValueError."""
+    T, ts = int(num_frames), int(tstride)
+    sel = set()
+    for b, markers in enumerate(cube_marker):
+        for start, span in markers:
+            c = int(start) * ts + int(span) * ts // 2
+            if not 0 <= c < T:
+                raise ValueError(f'hog_targets: marker [{int(start)}, {int(span)}] of clip {b} has its centre frame {c} outside 0..{T - 1}')
+            sel.add(b * T + c)
+    return sorted(sel)
+
+
+def hog_targets(clip, cube_marker, tstride=2):
+    """MaskFeat's regression targets from the decoded clip (reference dataset.py:188-196: HOG of the centre frame of every masked
+    cube, computed there on CPU workers): uint8 [B,T,H,W,3] (CUDA) + cube_marker (per clip a list of [start, span]) -> float64
+    [B,T,H/16,W/16,108], zeros outside the centre frames.  One index upload and one launch for the batch (vtx_hog_fwd_sel,
+    libvtx_stem.so); each selected frame equals hog_fwd of that frame bit for bit."""
+    clip = _u8_clip(clip, 'hog_targets')
+    B, T, H, W, _ = clip.shape
+    if len(cube_marker) != B:
+        raise ValueError(f'hog_targets: {len(cube_marker)} marker lists for {B} clips')
+    if H <= 0 or W <= 0 or H % 16 or W % 16 or W > 1024:
+        raise ValueError(f'hog_targets: H={H}, W={W} must be multiples of 16 (W <= 1024)')
+    sel = hog_center_frames(cube_marker, T, tstride)
+    out = torch.zeros(B, T, H // 16, W // 16, 108, dtype=torch.float64, device=clip.device)
+    if not sel:
+        return out
+    table = hog_table(clip.device)
+    idx = upload_i32(sel, clip.device)
+    with _timed('hog', nbytes=len(sel) * (H * W * 3 + out[0, 0].numel() * 8), key=f'sel {len(sel)}x{H}x{W}'):
+        _lib.stem_call('vtx_hog_fwd_sel', ptr(clip), B * T, H, W, ptr(idx), len(sel), ptr(table), table.numel() * 8, ptr(out), stream())
+    return out
 
 
 # ------------------------------------------------- clip augmentation (csrc/aug.hip -> libvtx_aug.so)
