@@ -38,6 +38,16 @@ times MaskFeat's input path from uint8 clips (csrc/stem.hip) at 32 clips x 16 fr
 over the rounds) and against the route it replaces, torch normalise + `vtx_im2col3d`; (b) `vtx.hog_targets` with three centre
 frames per clip against index_select + `ops.hog_fwd` + scatter into a zeroed target.  Both pairs are checked for equal results
 first; all paths in alternating rounds of one run.
+
+    python tools/aug_bench.py --ragged [--out profiles/clip_ragged_bench.txt]
+
+times a batch of clips that differ in source size (csrc/ragged.hip): 32 clips, 8 of 32 decoded frames each, sizes mixed over 256x340,
+340x256, 240x320 and 360x480, ClipEval(224) (Resize(256) + centre crop, bicubic): (a) one call on the list, (b) what there was before
+it -- 32 one-clip calls and a torch.cat --, (c) a uniform [B,Ts,331,320,3] batch of the same total bytes through `vtx_clip_views_u8`,
+the kernel-rate yardstick, and (d) that uniform batch given as a list, i.e. through `vtx_clips_views_u8`: the same work as (c) plus
+one descriptor read per workgroup.  (a) and (b) are checked for equal bytes first, (c) and (d) likewise; all paths in alternating
+rounds of one run; per path the device time (HIP events around the calls of a round), the host clock around the same calls ending
+in a synchronise, and the resampling kernel alone (a pair of HIP events around each launch, in rounds of its own).
 """
 import argparse
 import os
@@ -488,15 +498,119 @@ def stem_main(a):
         f.write(text)
 
 
+def ragged_main(a):
+    import time
+    import numpy as np
+    dev = 'cuda:0'
+    B, Ts, T, S, k = a.clips, a.decoded, a.frames, a.size, a.sets
+    sizes = [(256, 340), (340, 256), (240, 320), (360, 480)]
+    hw = [sizes[b % 4] for b in range(B)]
+    area = sum(h * w for h, w in hw) // B                      # 105920 = 331 x 320 for the four sizes in equal shares
+    uni = next(((area // w, w) for w in (320, 256, 384, 300) if area % w == 0), (int(round(area ** 0.5)),) * 2)
+    ev = aug.ClipEval(img_size=S)
+    g = torch.Generator().manual_seed(0)
+    rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device=dev)
+    lists = [[rnd(Ts, h, w, 3) for h, w in hw] for _ in range(k)]
+    unis = [rnd(B, Ts, uni[0], uni[1], 3) for _ in range(k)]
+    ulists = [list(u) for u in unis]
+    frames = np.stack([aug.sample_frames(Ts, T, Ts // T, generator=g) for _ in range(B)]).astype(np.int32)
+    rows = [frames[b:b + 1] for b in range(B)]
+
+    def one_call(i):
+        return ev(lists[i % k], frames=frames)
+
+    def per_clip(i):
+        return torch.cat([ev(c[None], frames=rows[b]) for b, c in enumerate(lists[i % k])])
+
+    def uniform(i):
+        return ev(unis[i % k], frames=frames)
+
+    def uniform_list(i):
+        return ev(ulists[i % k], frames=frames)
+    same_ab = torch.equal(one_call(0), per_clip(0))
+    same_cd = torch.equal(uniform(0), uniform_list(0))
+    assert same_ab and same_cd, 'the list call and the per-clip calls differ'
+    paths = [('(a) one call on the list', one_call), ('(b) 32 one-clip calls + torch.cat', per_clip),
+             ('(c) uniform 5-D batch, vtx_clip_views_u8', uniform), ('(d) the uniform batch as a list', uniform_list)]
+    for i in range(a.warmup):
+        for _, fn in paths:
+            fn(i)
+    torch.cuda.synchronize()
+    dev_us, wall_us = {n: [] for n, _ in paths}, {n: [] for n, _ in paths}
+    for r in range(a.rounds):                                  # alternating: what else runs on the machine hits all alike
+        for n, fn in paths:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            e0.record()
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            e1.record()
+            e1.synchronize()
+            wall_us[n].append((time.perf_counter() - t0) * 1e6 / a.iters)
+            dev_us[n].append(e0.elapsed_time(e1) * 1e3 / a.iters)
+    # the resampling kernel alone: events around every launch (rounds of their own: the events slow the host)
+    kern = {n: [] for n, _ in paths}
+    for r in range(a.rounds):
+        for n, fn in paths:
+            ops.profile_start(('clips_views', 'clip_views'))
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            torch.cuda.synchronize()
+            tot = ops.profile_totals(ops.profile_stop())
+            kern[n].append(sum(v[1] for v in tot.values()) * 1e3 / a.iters)          # us of kernel time per batch
+    sel = B * T
+    src_list = T * sum(h * w * 3 for h, w in hw)
+    src_uni = sel * uni[0] * uni[1] * 3
+    out_b = sel * S * S * 3
+    lines = [f'clips of differing source size, {B} clips, {T} of {Ts} decoded frames each, sizes {sizes} in equal shares, ClipEval({S}) '
+             f'(Resize({ev.scale_size}) + centre crop), bicubic, antialias off; {torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} batches per path, the paths in alternating rounds of one run, after {a.warmup} warm-up batches each; '
+             f'{k} source sets of {sum(c.numel() for c in lists[0]) / 2**20:.0f} MiB in rotation (together larger than the 256 MiB Infinity Cache)',
+             f'uniform batch of (c), (d): [{B},{Ts},{uni[0]},{uni[1]},3], {unis[0].numel() / 2**20:.0f} MiB per set; same bytes from (a) and (b): {same_ab}; '
+             f'from (c) and (d): {same_cd}',
+             'device = HIP events around the calls of a round; wall = host clock around the same calls, ending in a synchronise; kernel = HIP events '
+             'around each resampling launch, in rounds of their own; all per batch; spread = (max - min) / median over the rounds',
+             f'bytes a batch has to move: selected frames read {src_list / 1e6:.1f} MB (list) / {src_uni / 1e6:.1f} MB (uniform), whole frames counted, '
+             f'{out_b / 1e6:.1f} MB written',
+             '']
+    med, spread = {}, {}
+    for (n, _), nbytes in zip(paths, (src_list + out_b, src_list + out_b, src_uni + out_b, src_uni + out_b)):
+        d, w, kr = dev_us[n], wall_us[n], kern[n]
+        md, mw, mk = statistics.median(d), statistics.median(w), statistics.median(kr)
+        med[n[:3]], spread[n[:3]] = (md, mw, mk), ((max(d) - min(d)) / md, (max(w) - min(w)) / mw, (max(kr) - min(kr)) / mk)
+        lines.append(f'{n:<42} device median {md:8.1f} us  min {min(d):8.1f}  max {max(d):8.1f}  spread {100 * spread[n[:3]][0]:5.1f} %   '
+                     f'wall median {mw:8.1f} us  min {min(w):8.1f}  max {max(w):8.1f}  spread {100 * spread[n[:3]][1]:5.1f} %   '
+                     f'kernel median {mk:7.1f} us  min {min(kr):7.1f}  max {max(kr):7.1f}  spread {100 * spread[n[:3]][2]:5.1f} %  '
+                     f'{nbytes / mk / 1e6:5.2f} TB/s')
+    A, Bp, Cc, D = med['(a)'], med['(b)'], med['(c)'], med['(d)']
+    gap = Bp[1] - A[1]
+    noise = max(spread['(a)'][1] * A[1], spread['(b)'][1] * Bp[1])
+    lines.append('')
+    lines.append(f'(a) / (b): wall {A[1] / Bp[1]:.3f}, device {A[0] / Bp[0]:.3f}; (b) - (a) = {gap:.1f} us of wall time per batch against a spread of '
+                 f'{noise:.1f} us: ' + ('(a) beats (b) by more than the spread' if gap > noise else '(a) does NOT beat (b) by more than the spread'))
+    bar = 2 * spread['(c)'][2] * Cc[2]
+    lines.append(f'(d) - (c), kernel: {D[2] - Cc[2]:+.1f} us ({D[2] / Cc[2]:.3f}); twice the spread of (c): {bar:.1f} us: '
+                 + ('within it' if D[2] - Cc[2] <= bar else 'the ragged kernel is SLOWER than the uniform one by more than that'))
+    lines.append(f'(d) - (c), whole call: {D[1] - Cc[1]:+.1f} us of wall time ({D[1] / Cc[1]:.3f}): both calls are bound by the host (wall = device span > kernel), '
+                 f'and the list costs per-clip host work the tensor does not -- type, shape, device and contiguity of {B} tensors, {B} data_ptr()')
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--ragged', action='store_true', help='time one call on a list of clips of differing size against one call per clip (-> profiles/clip_ragged_bench.txt)')
     ap.add_argument('--stem', action='store_true', help='time the uint8 stem gather and hog_targets against the float routes (-> profiles/stem_u8_bench.txt)')
     ap.add_argument('--mix', action='store_true', help='time Mixup / CutMix on uint8 clips against the float route (-> profiles/clip_mix_bench.txt)')
     ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
-    ap.add_argument('--decoded', type=int, default=32, help='--views: decoded frames per clip')
+    ap.add_argument('--decoded', type=int, default=32, help='--views, --ragged: decoded frames per clip')
     ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
     ap.add_argument('--randaug', action='store_true', help='time the RandAugment kernels instead (-> profiles/clip_randaug_bench.txt)')
-    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views and --stem')
+    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views, --stem and --ragged')
     ap.add_argument('--frames', type=int, default=None, help='default 8; 16 with --stem')
     ap.add_argument('--src', type=int, nargs=2, default=(256, 340))
     ap.add_argument('--size', type=int, default=224)
@@ -508,13 +622,15 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.clips is None:
-        a.clips = 32 if a.views or a.stem else 96
+        a.clips = 32 if a.views or a.stem or a.ragged else 96
     if a.frames is None:
         a.frames = 16 if a.stem else 8
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
+        a.out = os.path.join(ROOT, 'profiles', 'clip_ragged_bench.txt' if a.ragged else 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
                              'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.ragged:
+        return ragged_main(a)
     if a.stem:
         return stem_main(a)
     if a.mix:

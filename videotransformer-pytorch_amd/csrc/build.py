@@ -1,4 +1,4 @@
-"""Build libvtx.so, libvtx_aug.so, libvtx_randaug.so, libvtx_views.so, libvtx_mix.so and libvtx_stem.so (gfx950) with hipcc -- no torch headers, no cmake.
+"""Build libvtx.so, libvtx_aug.so, libvtx_randaug.so, libvtx_views.so, libvtx_mix.so, libvtx_stem.so and libvtx_ragged.so (gfx950) with hipcc -- no torch headers, no cmake.
 
     python videotransformer-pytorch_amd/csrc/build.py [--force]
 
@@ -8,7 +8,8 @@ videotransformer-pytorch_amd/libvtx_aug.so and csrc/randaug.hip (RandAugment, in
 videotransformer-pytorch_amd/libvtx_randaug.so, csrc/views.hip (test-time views, include/vtx_views.h)
 videotransformer-pytorch_amd/libvtx_views.so and csrc/mix.hip (Mixup / CutMix on uint8 clips, include/vtx_mix.h)
 videotransformer-pytorch_amd/libvtx_mix.so, csrc/stem.hip (MaskFeat from uint8 clips: the Conv3d stem gather and the HOG of
-selected frames, include/vtx_stem.h) videotransformer-pytorch_amd/libvtx_stem.so.  hipcc cross-compiles without a GPU.
+selected frames, include/vtx_stem.h) videotransformer-pytorch_amd/libvtx_stem.so, csrc/ragged.hip (views of clips that differ in
+source size, include/vtx_ragged.h) videotransformer-pytorch_amd/libvtx_ragged.so.  hipcc cross-compiles without a GPU.
 """
 import os
 import subprocess
@@ -23,6 +24,7 @@ RANDAUG_OUT = os.path.join(PKG, 'libvtx_randaug.so')
 VIEWS_OUT = os.path.join(PKG, 'libvtx_views.so')
 MIX_OUT = os.path.join(PKG, 'libvtx_mix.so')
 STEM_OUT = os.path.join(PKG, 'libvtx_stem.so')
+RAGGED_OUT = os.path.join(PKG, 'libvtx_ragged.so')
 OBJ = os.path.join(HERE, '_obj')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_mfma.hip', 'attn_long.hip', 'attn_f32.hip', 'elementwise.hip', 'hog.hip', 'optim.hip', 'head.hip', 'mvit.hip', 'wprod.hip', 'xattn_mfma.hip']
@@ -36,6 +38,7 @@ RANDAUG_SOURCES = ['randaug.hip']  # the third: libvtx_aug.so keeps its seven sy
 VIEWS_SOURCES = ['views.hip']      # the fourth: frame selection + resize + ThreeCrop in one launch
 MIX_SOURCES = ['mix.hip']          # the fifth: CutMix on bytes, Mixup inside the patch gather
 STEM_SOURCES = ['stem.hip']        # the sixth: the MViT stem gather from bytes, HOG of selected frames (hog_kernel.h, shared with hog.hip)
+RAGGED_SOURCES = ['ragged.hip']    # the seventh: views.hip's kernel with per-clip base pointer and geometry
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result', '-Wno-unused-value', '-Wno-inline-asm',
          '-Wno-cuda-compat']
 EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contraction
@@ -43,7 +46,8 @@ EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contr
          'randaug.hip': ['-ffp-contract=off'],     # likewise: sharpness blend, autocontrast scale, warp coordinates
          'views.hip': ['-ffp-contract=off'],       # the weighted sums of aug.hip's resampler, byte for byte
          'mix.hip': ['-ffp-contract=off'],         # normalise then blend: five roundings per operand pair
-         'stem.hip': ['-ffp-contract=off']}        # hog_kernel.h as hog.hip compiles it; normalise: three roundings per tap
+         'stem.hip': ['-ffp-contract=off'],        # hog_kernel.h as hog.hip compiles it; normalise: three roundings per tap
+         'ragged.hip': ['-ffp-contract=off']}      # views.hip's weighted sums, byte for byte
 
 
 def _deps():
@@ -54,6 +58,7 @@ def _deps():
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_views.h'))
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_mix.h'))
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_stem.h'))
+    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_ragged.h'))
     hdrs.append(os.path.abspath(__file__))                       # the flags live here
     return max(os.path.getmtime(h) for h in hdrs)
 
@@ -123,20 +128,22 @@ def _link(out, res, extra, verbose):
 
 
 def _build_locked(force, verbose):
-    every = SOURCES + AUG_SOURCES + RANDAUG_SOURCES + VIEWS_SOURCES + MIX_SOURCES + STEM_SOURCES
+    every = SOURCES + AUG_SOURCES + RANDAUG_SOURCES + VIEWS_SOURCES + MIX_SOURCES + STEM_SOURCES + RAGGED_SOURCES
     with ThreadPoolExecutor(max_workers=min(8, len(every))) as ex:
         res = list(ex.map(lambda s: _compile(s, force), every))
     n, m = len(SOURCES), len(SOURCES) + len(AUG_SOURCES)
     k = m + len(RANDAUG_SOURCES)
     j = k + len(VIEWS_SOURCES)
     i = j + len(MIX_SOURCES)
+    h = i + len(STEM_SOURCES)
     _link(OUT, res[:n], [], verbose)
     # -Bsymbolic: the library's own definitions of the helpers common.h declares, whatever else the process has loaded
     _link(AUG_OUT, res[n:m], ['-Wl,-Bsymbolic'], verbose)
     _link(RANDAUG_OUT, res[m:k], ['-Wl,-Bsymbolic'], verbose)
     _link(VIEWS_OUT, res[k:j], ['-Wl,-Bsymbolic'], verbose)
     _link(MIX_OUT, res[j:i], ['-Wl,-Bsymbolic'], verbose)
-    _link(STEM_OUT, res[i:], ['-Wl,-Bsymbolic'], verbose)
+    _link(STEM_OUT, res[i:h], ['-Wl,-Bsymbolic'], verbose)
+    _link(RAGGED_OUT, res[h:], ['-Wl,-Bsymbolic'], verbose)
     return OUT
 
 

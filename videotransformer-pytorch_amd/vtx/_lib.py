@@ -229,12 +229,21 @@ STEM_SIGNATURES = {
     'vtx_hog_fwd_sel': (ci, [vp, ci, ci, ci, vp, ci, vp, sz, vp, vp]),
 }
 
+# libvtx_ragged.so (include/vtx_ragged.h, csrc/ragged.hip): views of clips that differ in source size, the seventh library.  Must list every symbol the header declares.
+RAGGED_LIB_PATH = os.environ.get('VTX_RAGGED_LIB', os.path.join(_PKG, 'libvtx_ragged.so'))
+RAGGED_SIGNATURES = {
+    'vtx_ragged_version': (ci, []),
+    'vtx_ragged_last_error_string': (C.c_char_p, []),
+    'vtx_clips_views_u8': (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+}
+
 _lib = None
 _aug = None
 _randaug = None
 _views = None
 _mix = None
 _stem = None
+_ragged = None
 
 
 class VtxError(RuntimeError):
@@ -381,6 +390,34 @@ def stem_call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.vtx_stem_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def load_ragged():
+    """Load libvtx_ragged.so and bind every symbol of include/vtx_ragged.h.  Raises if anything is missing: there is no fallback."""
+    global _ragged
+    if _ragged is not None:
+        return _ragged
+    if not os.path.isfile(RAGGED_LIB_PATH):
+        raise VtxError(f'libvtx_ragged.so not found at {RAGGED_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(RAGGED_LIB_PATH)
+    for name, (res, args) in RAGGED_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_ragged.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _ragged = lib
+    return lib
+
+
+def ragged_call(name, *args):
+    lib = load_ragged()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_ragged_last_error_string()
         raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 

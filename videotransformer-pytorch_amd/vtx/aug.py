@@ -31,6 +31,14 @@ resampling is libvtx_views.so's (csrc/views.hip, include/vtx_views.h): frame gat
 (two ops of fourteen at magnitude bin 9 of 31, nearest interpolation, no fill) and the content of the string is ignored.  What
 is restated is torchvision's tensor path as of 0.13 .. 0.20; torchvision is not a dependency and no version is pinned.
 
+Clips that differ in size: every pipeline also takes a list (or tuple) of B clips [Ts_b,Hs_b,Ws_b,3], each its own tensor with its
+own decoded length and frame size -- what a loader yields that collates decoded videos as they are -- and returns the same
+uniform [B,T,S,S,3] ([B*3,T,S,S,3] for ``ClipTest``) in the same number of launches: the resampling is then libvtx_ragged.so's
+(csrc/ragged.hip, include/vtx_ragged.h), which reads each clip's base pointer and geometry on the device.
+
+    batch = [c.cuda(non_blocking=True) for c in decoded]          # 340x256, 256x340, 320x240, ...: no resize on the host
+    out = model(aug(batch, frames=[vtx.aug.sample_frames(len(c), 8, 4) for c in decoded]))
+
 Not built: RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations.
 """
 import math
@@ -87,6 +95,35 @@ def _check_frames(frames, B, Ts):
         raise ValueError(f'frames: {a.shape[0]} rows for {B} clips')
     if a.min() < 0 or a.max() >= Ts:
         raise ValueError(f'frames: indices {int(a.min())} .. {int(a.max())} outside the {Ts} decoded frames')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _check_frames_ragged(frames, lengths):
+    """frames= for a list of clips of ``lengths`` decoded frames: B rows of T host integers, row b indices into its own clip's
+    frames, or one row [T] for every clip -> int32 [B,T]; None (every frame) needs clips of one length."""
+    B = len(lengths)
+    if frames is None:
+        if len(set(lengths)) != 1:
+            raise ValueError(f'frames: clips of {list(lengths)} decoded frames: without frames= every frame is taken and the lengths must agree')
+        return None
+    if isinstance(frames, torch.Tensor):
+        if frames.is_cuda:
+            raise TypeError('frames: host integers expected (a list, an array or a CPU tensor), got a device tensor')
+        frames = frames.numpy()
+    try:
+        a = np.asarray(frames)
+    except ValueError as e:                                      # rows of different lengths
+        raise TypeError(f'frames: integers [T] or [{B},T] expected: {e}') from e
+    if a.dtype.kind not in 'iu' or a.ndim not in (1, 2) or a.size == 0:
+        raise TypeError(f'frames: integers [T] or [{B},T] expected, got {a.dtype} {a.shape}')
+    if a.ndim == 1:
+        a = np.broadcast_to(a, (B, a.shape[0]))
+    if a.shape[0] != B:
+        raise ValueError(f'frames: {a.shape[0]} rows for {B} clips')
+    bad = ((a < 0) | (a >= np.asarray(lengths).reshape(B, 1))).any(axis=1)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError(f'frames: indices {int(a[b].min())} .. {int(a[b].max())} of clip {b} outside its {lengths[b]} decoded frames')
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
@@ -207,11 +244,17 @@ def randaug_theta(op, mag, H, W):
 
 
 def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, generator=None, auto_augment=None, out_hw=None):
-    """The draws of RandomResizedCrop + RandomHorizontalFlip + ColorJitter for B clips of ``src_hw`` = (height, width) frames:
-    a list of B ``ClipDraw``.  Host code; all randomness comes from ``generator`` (None = torch's default CPU generator).
+    """The draws of RandomResizedCrop + RandomHorizontalFlip + ColorJitter for B clips of ``src_hw`` = (height, width) frames, or
+    of B clips of their own sizes, ``src_hw`` = B pairs (height, width) -- the draws are then those of B successive one-clip calls
+    on the same generator: a list of B ``ClipDraw``.  Host code; all randomness comes from ``generator`` (None = torch's default CPU generator).
     A truthy ``auto_augment`` draws RandAugment() for ``out_hw`` frames in place of the ColorJitter (``ops`` and ``factors`` stay
     empty), clip by clip: crop, flip, RandAugment."""
-    height, width = int(src_hw[0]), int(src_hw[1])
+    if np.ndim(src_hw) == 2:
+        sizes = [(int(h), int(w)) for h, w in src_hw]
+        if len(sizes) != int(B):
+            raise ValueError(f'sample_params: {len(sizes)} frame sizes for {B} clips')
+    else:
+        sizes = [(int(src_hw[0]), int(src_hw[1]))] * int(B)
     scale = tuple(scale or (0.08, 1.0))
     ratio = tuple(ratio or (3. / 4., 4. / 3.))
     ranges = _jitter_ranges(color_jitter)
@@ -221,7 +264,7 @@ def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4
             raise ValueError('sample_params: auto_augment needs out_hw, the frame size behind the crop')
         ranges, mags = None, _randaug_magnitudes(out_hw, 9, 31)
     draws = []
-    for _ in range(int(B)):
+    for height, width in sizes:
         top, left, h, w = _crop_box(height, width, scale, ratio, generator)
         flip = bool(hflip > 0. and float(torch.rand(1, generator=generator)) < hflip)
         jops, jfac = [], []
@@ -237,9 +280,11 @@ def sample_params(B, src_hw, scale=None, ratio=None, hflip=0.5, color_jitter=0.4
 
 
 def _check_draws(draws, B, Hs, Ws, num_ops=2):
+    """Hs, Ws: the frame size of every clip, or B sizes each (a list of clips)."""
     if len(draws) != B:
         raise ValueError(f'params: {len(draws)} records for {B} clips')
-    for d in draws:
+    sizes = zip(Hs, Ws) if isinstance(Hs, (list, tuple)) else [(Hs, Ws)] * B
+    for d, (Hs, Ws) in zip(draws, sizes):
         if not (0 <= d.top and 0 < d.height and d.top + d.height <= Hs and 0 <= d.left and 0 < d.width and d.left + d.width <= Ws):
             raise ValueError(f'params: crop box (top {d.top}, left {d.left}, {d.height}x{d.width}) outside the {Hs}x{Ws} frame')
         if len(d.ops) != len(d.factors) or len(d.ops) > 3 or len(set(d.ops)) != len(d.ops) or any(o not in (0, 1, 2) for o in d.ops):
@@ -255,7 +300,8 @@ def _check_draws(draws, B, Hs, Ws, num_ops=2):
 
 def _tables(specs, mode, antialias):
     """specs: per clip (src_len, crop_start, crop_len, out_len, flip, lo, n) -> first [B,n], count [B,n], weights [B,n,taps]
-    (rows lo .. lo+n of each clip's table)."""
+    (rows lo .. lo+n of each clip's table; where n differs between the clips, the largest, and the shorter tables end in rows of
+    count 0)."""
     taps = max(ops.resample_max_taps(s[2], s[3], mode, antialias) for s in specs)
     built = {}                                              # clips that share a spec (ClipEval: all of them) share the table
     for s in specs:
@@ -263,6 +309,9 @@ def _tables(specs, mode, antialias):
             built[s[:5]] = ops.resample_table(s[0], s[1], s[2], s[3], mode, antialias, s[4], taps)
     tabs = [built[s[:5]] for s in specs]
     cut = [tuple(a[s[5]:s[5] + s[6]] for a in t) for t, s in zip(tabs, specs)]
+    n = max(s[6] for s in specs)
+    if any(s[6] != n for s in specs):
+        cut = [tuple(np.concatenate([a, np.zeros((n - len(a),) + a.shape[1:], dtype=a.dtype)]) for a in c) for c in cut]
     return tuple(np.stack([c[i] for c in cut]) for i in range(3))
 
 
@@ -313,7 +362,9 @@ def _randaug_plan(draws, H, W):
 def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None, lefts=None):
     """Tables (and colour / RandAugment records) to the device in one copy, then the kernels.  With ``frames`` (int32 [B,T]) or
     ``lefts`` (int32 [B,V]: the x tables then cover the whole resized row and out_hw[1] is the width of a view) the resampling is
-    clip_views_u8's, and its [B,V,T,H,W,3] is returned as [B*V,T,H,W,3]."""
+    clip_views_u8's, and its [B,V,T,H,W,3] is returned as [B*V,T,H,W,3].  ``clips`` a list: clips_views_u8's, always; the
+    pointer table and geometry travel at the front of the same copy (the x table of clip b holds xspecs[b][6] columns)."""
+    ragged = isinstance(clips, (list, tuple))
     xf, xc, xw = _tables(xspecs, mode, antialias)
     yf, yc, yw = _tables(yspecs, mode, antialias)
     parts = [xf, xc, xw.view(np.int32), yf, yc, yw.view(np.int32)]
@@ -331,21 +382,29 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None
     plan = _randaug_plan(draws, out_hw[0], out_hw[1]) if draws is not None and any(d.randaug for d in draws) else []
     for _, recs in plan:
         parts += [r.view(np.int32) for r in recs]
-    gather = frames is not None or lefts is not None
+    gather = ragged or frames is not None or lefts is not None
     if gather:
         if lefts is None:
             lefts = np.zeros((len(xspecs), 1), dtype=np.int32)
         parts += [lefts] + ([frames] if frames is not None else [])
-    dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.device)
+    if ragged:                                               # every check of the list happens here, before anything is enqueued
+        clips = ops.clips_table(clips, [s[6] for s in xspecs], 'vtx.aug')
+        parts.insert(0, clips.host)                          # first: the 8-byte pointers are aligned there
+    dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.kept[0].device if ragged else clips.device)
     views, at = [], 0
     for p in parts:
         views.append(dev[at:at + p.size].view(p.shape))
         at += p.size
+    if ragged:
+        parts, table = parts[1:], views.pop(0)
     f32 = lambda t: t.view(torch.float32)
     xtab, ytab = (views[0], views[1], f32(views[2])), (views[3], views[4], f32(views[5]))
     if gather:
         at = len(parts) - (1 if frames is None else 2)
-        out = ops.clip_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab)
+        if ragged:
+            out = ops.clips_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab, table=table)
+        else:
+            out = ops.clip_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab)
         out = out.view((-1,) + tuple(out.shape[2:]))
     else:
         out = ops.clip_resample_u8(clips, out_hw, xtab, ytab)
@@ -375,11 +434,20 @@ def _check_clips(clips):
     return clips.shape[0], clips.shape[2], clips.shape[3]
 
 
+def _check_clip_list(clips, frames):
+    """A list of clips [Ts_b,Hs_b,Ws_b,3] and its frames= -> (B, [Hs_b], [Ws_b], int32 frames [B,T] or None).  Host checks of types,
+    shapes and indices; where the tensors live is checked with everything else before the upload (ops.clips_table)."""
+    shapes = ops.clip_list_shapes(clips, 'vtx.aug')
+    frames = _check_frames_ragged(frames, [s[0] for s in shapes])
+    return len(shapes), [s[1] for s in shapes], [s[2] for s in shapes], frames
+
+
 class ClipAugment:
     """``transforms_train`` (data_transform.py:495-531) without its ToTensor + Normalize tail, per clip on the device.  Takes
     that function's arguments and defaults; ``scale=(0.5, 1.0), color_jitter=None`` is the ``mim`` branch of
     data_trainer.py:61-63; a truthy ``auto_augment`` (the -auto_augment flag, data_trainer.py:82) puts RandAugment() in the place
-    of the ColorJitter, whatever the string says.  uint8 CUDA [B,T,Hs,Ws,3] -> uint8 CUDA [B,T,img_size,img_size,3]."""
+    of the ColorJitter, whatever the string says.  uint8 CUDA [B,T,Hs,Ws,3], or a list of B uint8 CUDA clips [Ts_b,Hs_b,Ws_b,3] of
+    their own sizes, -> uint8 CUDA [B,T,img_size,img_size,3]."""
 
     def __init__(self, img_size=224, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, interpolation='bicubic', antialias=False,
                  auto_augment=None):
@@ -392,7 +460,19 @@ class ClipAugment:
 
     def __call__(self, clips_u8, generator=None, params=None, frames=None):
         """``frames``: host integers [B,T] (or [T] for every clip alike), the decoded frames to take (``sample_frames``); the result
-        is that of the call on ``clips_u8[b, frames[b]]`` under the same draws, without the gathered copy."""
+        is that of the call on ``clips_u8[b, frames[b]]`` under the same draws, without the gathered copy.  A list of clips: row b
+        of ``frames`` indexes its own clip's frames, and clip b's result is that of the call on ``clips_u8[b][None]`` with
+        ``params[b]`` and ``frames[b]``; without ``frames`` the clips must agree in length."""
+        if isinstance(clips_u8, (list, tuple)):
+            B, Hs, Ws, frames = _check_clip_list(clips_u8, frames)
+            if params is None:
+                params = sample_params(B, list(zip(Hs, Ws)), self.scale, self.ratio, self.hflip, self.color_jitter, generator,
+                                       auto_augment=self.auto_augment, out_hw=self.out_hw)
+            _check_draws(params, B, Hs, Ws)
+            H, W = self.out_hw
+            xs = [(w, d.left, d.width, W, d.flip, 0, W) for d, w in zip(params, Ws)]
+            ys = [(h, d.top, d.height, H, False, 0, H) for d, h in zip(params, Hs)]
+            return _run(clips_u8, xs, ys, self.out_hw, self.interpolation, self.antialias, params, frames=frames)
         B, Hs, Ws = _check_clips(clips_u8)
         if frames is not None:
             frames = _check_frames(frames, B, clips_u8.shape[1])
@@ -424,7 +504,19 @@ class ClipEval:
         return (new_long, new_short) if Ws <= Hs else (new_short, new_long)
 
     def __call__(self, clips_u8, frames=None):
-        """``frames``: as ClipAugment's."""
+        """``frames``: as ClipAugment's.  A list of clips: each is resized and cropped by its own size."""
+        S = self.img_size
+        if isinstance(clips_u8, (list, tuple)):
+            B, Hs, Ws, frames = _check_clip_list(clips_u8, frames)
+            xs, ys = [], []
+            for b in range(B):
+                Hr, Wr = self.resized_hw(Hs[b], Ws[b])
+                if Hr < S or Wr < S:
+                    raise ValueError(f'ClipEval: the resized frame {Hr}x{Wr} of clip {b} ({Hs[b]}x{Ws[b]}) is smaller than the {S}x{S} crop '
+                                     '(padding is not built)')
+                xs.append((Ws[b], 0, Ws[b], Wr, False, int(round((Wr - S) / 2.0)), S))
+                ys.append((Hs[b], 0, Hs[b], Hr, False, int(round((Hr - S) / 2.0)), S))
+            return _run(clips_u8, xs, ys, (S, S), self.interpolation, self.antialias, frames=frames)
         B, Hs, Ws = _check_clips(clips_u8)
         if frames is not None:
             frames = _check_frames(frames, B, clips_u8.shape[1])
@@ -473,8 +565,29 @@ class ClipTest:
             raise ValueError('Requested crop size {} is bigger than input size {}'.format(S, (Hr, Wr)))
         return (Hr - S) // 2, (0, Wr - S, (Wr - S) // 2)
 
+    def specs(self, sizes):
+        """For clips of ``sizes`` = [(Hs_b, Ws_b)]: -> (x specs, y specs, lefts int32 [B,3]) of ``_tables`` / ``_run``.  The x table of
+        clip b has the Wr_b columns of its own resized row; ``_tables`` pads them to the widest with count 0."""
+        S = self.img_size
+        xs, ys, lefts = [], [], []
+        for b, (Hs, Ws) in enumerate(sizes):
+            Hr, Wr = self.resized_hw(Hs, Ws)
+            try:
+                top, left = self.offsets(Hs, Ws)
+            except ValueError as e:
+                raise ValueError(f'{e} (clip {b}, {Hs}x{Ws})') from None
+            xs.append((Ws, 0, Ws, Wr, False, 0, Wr))
+            ys.append((Hs, 0, Hs, Hr, False, top, S))
+            lefts.append(left)
+        return xs, ys, np.array(lefts, dtype=np.int32)
+
     def __call__(self, clips_u8, frames=None):
-        """``frames``: as ClipAugment's; None takes every frame."""
+        """``frames``: as ClipAugment's; None takes every frame.  A list of clips: each is resized and cropped by its own size, view
+        v of clip b in row b*3 + v as ever."""
+        if isinstance(clips_u8, (list, tuple)):
+            B, Hs, Ws, frames = _check_clip_list(clips_u8, frames)
+            xs, ys, lefts = self.specs(list(zip(Hs, Ws)))
+            return _run(clips_u8, xs, ys, (self.img_size, self.img_size), self.interpolation, self.antialias, frames=frames, lefts=lefts)
         B, Hs, Ws = _check_clips(clips_u8)
         if frames is not None:
             frames = _check_frames(frames, B, clips_u8.shape[1])

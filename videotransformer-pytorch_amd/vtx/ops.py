@@ -935,6 +935,151 @@ def clip_views_u8(src, frames, left, width, xtab, ytab, out=None):
     return out
 
 
+# ------------------------------------------------- views of clips that differ in source size (csrc/ragged.hip -> libvtx_ragged.so)
+def clip_list_shapes(clips, what):
+    """A ragged batch: a non-empty list or tuple of uint8 [Ts_b,Hs_b,Ws_b,3] tensors -> [(Ts_b, Hs_b, Ws_b)].  Types and shapes
+    only (host); where the tensors live is ``clips_table``'s check."""
+    if not isinstance(clips, (list, tuple)):
+        raise TypeError(f'{what}: a list or tuple of uint8 [T,H,W,3] clips expected, got {type(clips).__name__}')
+    if len(clips) == 0:
+        raise ValueError(f'{what}: an empty list of clips')
+    for b, c in enumerate(clips):
+        if not isinstance(c, torch.Tensor):
+            raise TypeError(f'{what}: clip {b} is a {type(c).__name__}, not a tensor')
+        if c.dtype != torch.uint8 or c.ndim != 4 or c.shape[-1] != 3 or c.numel() == 0:
+            raise TypeError(f'{what}: clip {b} must be a non-empty uint8 [T,H,W,3], got {c.dtype} {tuple(c.shape)}')
+    return [tuple(c.shape[:3]) for c in clips]
+
+
+class ClipTable:
+    """A list of clips that passed every host check, and the descriptor vtx_clips_views_u8 reads on the device.  ``kept``: the
+    clips made contiguous (referenced here until the launch is enqueued); ``shapes``: [(Ts_b, Hs_b, Ws_b)]; ``widths``: the columns
+    of each clip's resized row; ``host``: int32 array [6 * B] -- the B base pointers as little-endian int32 pairs, then B records
+    (Ts_b, Hs_b, Ws_b, widths[b]).  The pointers come FIRST: whoever packs ``host`` into a larger upload puts it at the front,
+    where the 8-byte loads of the pointers are aligned.  Only ``clips_table`` makes one."""
+    __slots__ = ('kept', 'shapes', 'widths', 'host')
+
+
+def clips_table(clips, widths, what='clips_views_u8'):
+    """list or tuple of uint8 CUDA clips [Ts_b,Hs_b,Ws_b,3] on the current device, B row widths -> ClipTable.  Host only: nothing
+    is enqueued but the copies of entries that are not contiguous."""
+    import numpy as np
+    t = ClipTable()
+    t.shapes = clip_list_shapes(clips, what)
+    need_cuda(*clips)
+    t.widths = [int(w) for w in widths]
+    if len(t.widths) != len(clips):
+        raise ValueError(f'{what}: {len(t.widths)} row widths for {len(clips)} clips')
+    t.kept = [c.contiguous() for c in clips]
+    ptrs = np.array([c.data_ptr() for c in t.kept], dtype=np.uint64)
+    geom = np.array([s + (w,) for s, w in zip(t.shapes, t.widths)], dtype=np.int32)
+    t.host = np.concatenate([ptrs.view(np.int32), geom.reshape(-1)])
+    return t
+
+
+def _ragged_index(t, B, hi, what, device):
+    """frames / left of clips_views_u8: an int32 [B,n] device tensor is taken as it is (the kernel clamps what it reads with the
+    clip's own numbers); host integers are checked row by row against 0 <= v <= hi[b] -> int32 array [B,n], not yet uploaded."""
+    import numpy as np
+    if isinstance(t, torch.Tensor) and t.is_cuda:
+        need_cuda(t)
+        if t.dtype != torch.int32 or t.ndim != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
+            raise TypeError(f'clips_views_u8: {what} must be int32 [{B},n] contiguous, got {t.dtype} {tuple(t.shape)}')
+        return t
+    a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    if a.dtype.kind not in 'iu' or a.ndim != 2 or a.shape[0] != B or a.shape[1] < 1:
+        raise TypeError(f'clips_views_u8: {what} must be integers [{B},n], got {a.dtype} {a.shape}')
+    bad = ((a < 0) | (a > np.asarray(hi).reshape(B, 1))).any(axis=1)
+    if bad.any():
+        b = int(np.argmax(bad))
+        raise ValueError(f'clips_views_u8: {what} of clip {b} must lie in 0 .. {hi[b]}, got {int(a[b].min())} .. {int(a[b].max())}')
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None, table=None):
+    """clip_views_u8 for clips that differ in decoded length and frame size, in one launch: ``clips`` a list or tuple of B uint8
+    CUDA tensors [Ts_b,Hs_b,Ws_b,3] on the current device -> uint8 [B,V,T,H,width,3].  frames: [B,T] indices, row b into the Ts_b
+    frames of its own clip, or None for every frame (all Ts_b must then be equal); left: [B,V], V <= 8, first columns in clip b's
+    resized row of widths[b] columns (both: int32 device tensors, or host integers, which are validated and uploaded).  xtab =
+    (first [B,Wr_max] int32, count [B,Wr_max] int32, weights [B,Wr_max,K] float32) device tensors, row b valid for its first
+    widths[b] columns (``widths``: B integers in width .. Wr_max; None = Wr_max for every clip); ytab likewise for the H output
+    rows.  Clip b's views are byte for byte clip_views_u8 on clips[b][None] with row b of the tables.
+
+    Entries that are not contiguous are copied; the copies live until the launch is enqueued.  Everything is checked on the host
+    before anything is enqueued, and the pointer table is built only from tensors that passed.  It is uploaded, with the
+    geometry and whatever of frames / left came as host values, in one copy.  A caller with records of its own to upload
+    (vtx.aug: tables, colour records and descriptor in one copy) passes the ``ClipTable`` of ``clips_table`` as ``clips`` and
+    the int32 [6 * B] device copy of its ``host`` array as ``table``; the list is then not checked again."""
+    import numpy as np
+    name = 'clips_views_u8'
+    if isinstance(clips, ClipTable):
+        ct = clips
+        if widths is not None:
+            raise TypeError(f'{name}: a ClipTable carries its row widths')
+    else:
+        if table is not None:
+            raise TypeError(f'{name}: table= goes with the ClipTable it is the device copy of')
+        shapes = clip_list_shapes(clips, name)                   # types and shapes before the tables' batch size is read
+        need_cuda(*clips)
+        ct = None
+    B, W = len(ct.kept if ct else clips), int(width)
+    for tab in (xtab, ytab):
+        f, c, w = tab
+        need_cuda(f, c, w)
+        n = f.shape[1] if f.ndim == 2 else -1
+        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
+                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n) or n < 1 or w.shape[2] < 1
+                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
+            raise TypeError(f'{name}: a table is (int32 [{B},n], int32 [{B},n], float32 [{B},n,taps]), contiguous')
+    Wr_max, H = xtab[0].shape[1], ytab[0].shape[1]
+    if ct is None:
+        ct = clips_table(clips, [Wr_max] * B if widths is None else widths, name)
+    shapes, widths, dev = ct.shapes, ct.widths, ct.kept[0].device
+    for b, w in enumerate(widths):
+        if not 0 < W <= w <= Wr_max:
+            raise ValueError(f'{name}: views of {W} columns do not fit the resized row of {w} of clip {b} (the tables hold {Wr_max})')
+    left = _ragged_index(left, B, [w - W for w in widths], 'left (left + width <= the row of the clip)', dev)
+    V = left.shape[1]
+    if V > _lib.VIEWS_MAX:
+        raise ValueError(f'{name}: {V} views, at most {_lib.VIEWS_MAX}')
+    if frames is None:
+        T = shapes[0][0]
+        if any(s[0] != T for s in shapes):
+            raise ValueError(f'{name}: without frame indices every frame is taken and the clips must agree in length, got {[s[0] for s in shapes]}')
+    else:
+        frames = _ragged_index(frames, B, [s[0] - 1 for s in shapes], 'frame indices (into the frames of the clip)', dev)
+        T = frames.shape[1]
+    if B * T > 65535:
+        raise ValueError(f'{name}: {B} clips x {T} frames exceed the grid (65535)')
+    if out is None:
+        out = torch.empty(B, V, T, H, W, 3, dtype=torch.uint8, device=dev)
+    else:
+        need_cuda(out)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (B, V, T, H, W, 3) or not out.is_contiguous():
+            raise TypeError(f'{name}: out must be a contiguous uint8 {(B, V, T, H, W, 3)} tensor, got {out.dtype} {tuple(out.shape)}')
+    if table is None:
+        parts = [ct.host] + [a.reshape(-1) for a in (left, frames) if isinstance(a, np.ndarray)]
+        up = upload_i32(np.concatenate(parts), dev)
+        table, at = up[:6 * B], 6 * B
+        if isinstance(left, np.ndarray):
+            left, at = up[at:at + left.size].view(left.shape), at + left.size
+        if isinstance(frames, np.ndarray):
+            frames = up[at:at + frames.size].view(frames.shape)
+    else:
+        need_cuda(table)
+        if (table.dtype != torch.int32 or table.ndim != 1 or table.numel() != 6 * B or not table.is_contiguous()
+                or table.data_ptr() % 8):
+            raise TypeError(f'{name}: table must be the int32 [{6 * B}] device copy of the ClipTable\'s host array, 8-byte aligned')
+        if isinstance(left, np.ndarray) or isinstance(frames, np.ndarray):
+            raise TypeError(f'{name}: with table= frames and left are device tensors (uploaded with it)')
+    src_bytes = sum(T * s[1] * s[2] * 3 for s in shapes)
+    with _timed('clips_views', nbytes=src_bytes + out.numel(), key=f'{B}x{T} ragged->{V}x{H}x{W}'):
+        _lib.ragged_call('vtx_clips_views_u8', B, T, H, V, W, Wr_max, ptr(table), table.data_ptr() + 8 * B, ptr(out), ptr(frames),
+                         ptr(left), ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]), xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]),
+                         ptr(ytab[2]), ytab[2].shape[2], stream())
+    return out                                                   # (ct.kept lived until here: the launch is enqueued)
+
+
 # ------------------------------------------------- clip-batch mixing, accuracy (csrc/head.hip)
 def mixup_batch_(x, lam):
     """In place: x[b] = x[b]*lam + x[B-1-b]*(1-lam) on a contiguous fp32 [B, ...] batch (reference mixup.py:112-113)."""
