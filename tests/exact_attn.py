@@ -14,8 +14,10 @@ neighbouring sequence, the wrong frame, a stale row of the previous item, an unm
 scores 0 with some query and adds a winner, which moves P from 2^-k to 1 / (2^k + 1).
 
 Layouts: 'contig' (sequence s = rows [s L, (s+1) L)), 'space' (VTX_ATTN_SPACE: clip b, frame t; the cls row is shared by
-the T frames of a clip, so its code, Q, K and V are drawn once per (clip, head)), 'cross' (separate q [B, Lq, C] and
-k, v [B, Lk, C]).  The float64 reference works on the winner lists, never on a dense L x L matrix.
+the T frames of a clip, so its code, Q, K and V are drawn once per (clip, head)), 'time_cls' (VTX_ATTN_TIME_CLS: clip b,
+patch position p; the cls row is shared by the P sequences of a clip), 'space_nocls' (VTX_ATTN_SPACE_NOCLS: clip b, frame
+t, token rows only), 'cross' (separate q [B, Lq, C] and k, v [B, Lk, C]).  layout_rows restates the row addressing of the
+three strided layouts.  The float64 reference works on the winner lists, never on a dense L x L matrix.
 """
 import math
 
@@ -51,9 +53,8 @@ def edge_keys(nk):
     return sorted(e)
 
 
-def _groups(nk, rng, required, first):
-    """Partition range(nk) into groups of 1, 2 or 4; every required key in a group of >= 2 (when nk >= 2); key 0 first in
-    its group when `first`."""
+def _draw_groups(nk, rng, required, first):
+    """One draw of _groups; None where a required singleton finds no larger group with a key it may take."""
     perm = list(rng.permutation(nk))
     if first:
         perm.remove(0)
@@ -77,12 +78,23 @@ def _groups(nk, rng, required, first):
                         h[h.index(x)], g[0] = g[0], x
                         break
                 else:
-                    raise AssertionError('no group to move a required key into')
+                    return None
     if first:
         g0 = next(g for g in groups if 0 in g)
         g0.remove(0)
         g0.insert(0, 0)
     return groups
+
+
+def _groups(nk, rng, required, first):
+    """Partition range(nk) into groups of 1, 2 or 4; every required key in a group of >= 2 (when nk >= 2); key 0 first in
+    its group when `first`.  A draw that cannot place a required key (a few keys, most of them required: at nk = 3 only
+    [0, 2], [1] serves) is drawn again; a draw that can is returned as it always was, from the same random numbers."""
+    for _ in range(64):
+        groups = _draw_groups(nk, rng, required, first)
+        if groups is not None:
+            return groups
+    raise AssertionError('no group to move a required key into')
 
 
 def route_item(nq, nk, R, rng, required=(), first_code=None):
@@ -337,9 +349,13 @@ def assert_edges(it, ref, required=None):
 
 # ------------------------------------------------------------------------------------------------ cases by layout
 class Case:
-    """A routed case in a physical layout.  Tensors (float64 CPU):
-    contig / space: qkv [rows, 3D], dout [out_rows, D]; expected out [out_rows, D], lse [S, H, L], dqkv [rows, 3D] (space:
-    cls rows NaN), dqkv_cls [S, 3D] (space) and the bound tensors dqkv_abs / dqkv_n (same shape);
+    """A routed case in a physical layout: layout in 'contig', 'space', 'time_cls', 'space_nocls' (self-attention) or
+    'cross'.  Self-attention cases carry their own B, T, P (0 for contig), cls_group -- the number of sequences that share one
+    cls row: T for space, P for time_cls, 0 otherwise -- and cls_rows, the cls row of every clip in qkv / dqkv.
+    Tensors (float64 CPU):
+    self-attention: qkv [rows, 3D] (space_nocls: cls rows NaN), dout [out_rows, D]; expected out [out_rows, D], lse
+    [S, H, L], dqkv [rows, 3D] (cls rows: NaN where cls_group, for they go to dqkv_cls [S, 3D]; zeros for space_nocls) and
+    the bound tensors dqkv_abs / dqkv_n (same shape);
     cross: q [B, Lq, C], k, v [B, Lk, C], dout; expected out, lse [B, heads, Lq], dq, dk, dv and their *_abs / *_n."""
 
 
@@ -355,6 +371,7 @@ def contig_case(S, L, H, kind='exact', bwd=True, seed=0, hd=64):
         assert_edges(it, r)
     c = Case()
     c.layout, c.S, c.L, c.H, c.hd, c.kind, c.bwd, c.items, c.ref = 'contig', S, L, H, hd, kind, bwd, it, r
+    c.B, c.T, c.P, c.cls_group = 0, 0, 0, 0
     D = H * hd
     c.qkv = np.concatenate([_sh(it.Q, S, H, L, hd), _sh(it.K, S, H, L, hd), _sh(it.V, S, H, L, hd)], 2).reshape(S * L, 3 * D)
     c.dout = _sh(it.dO, S, H, L, hd).reshape(S * L, D)
@@ -368,36 +385,59 @@ def contig_case(S, L, H, kind='exact', bwd=True, seed=0, hd=64):
     return c
 
 
-def space_rows(B, T, P):
-    """in_row / out_row of vtx_attn (attn_common.h) as [S, L] int arrays."""
-    S, L = B * T, P + 1
+def layout_rows(mode, B, T, P):
+    """in_row / out_row of vtx_attn (attn_common.h) as [S, L] int arrays, for the layouts that read qkv in the natural token
+    order [B, 1 + P T, 3D]: 'space' (s = (b, t), L = 1 + P), 'time_cls' (s = (b, p), L = 1 + T), 'space_nocls' (s = (b, t),
+    L = P)."""
+    S, L = {'space': (B * T, P + 1), 'time_cls': (B * P, T + 1), 'space_nocls': (B * T, P)}[mode]
     s = np.arange(S)[:, None]
     i = np.arange(L)[None, :]
+    rpc = 1 + P * T
+    if mode == 'time_cls':
+        b = s // P
+        return np.where(i == 0, b * rpc, s * T + b + i), np.where(i == 0, B * P * T + s, s * T + i - 1)
     b, t = s // T, s % T
-    rin = np.where(i == 0, b * (1 + P * T), b * (1 + P * T) + 1 + (i - 1) * T + t)
+    if mode == 'space_nocls':
+        return b * rpc + 1 + i * T + t, b * P * T + i * T + t
+    rin = np.where(i == 0, b * rpc, b * rpc + 1 + (i - 1) * T + t)
     rout = np.where(i == 0, B * P * T + s, b * P * T + (i - 1) * T + t)
     return rin, rout
 
 
-def space_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
-    S, L, D = B * T, P + 1, H * hd
-    R = routing_dims(int(math.ceil(L / 1.3)) + 2)
-    sh = shared_rows(B * H, hd, R, kind, bwd, seed + 1)
-    # item n = s * H + h = (b T + t) H + h uses the shared rows of (b, h)
-    idx = (np.arange(S)[:, None] // T * H + np.arange(H)[None, :]).reshape(-1)
-    it = build_items(S * H, L, L, hd, kind, bwd, seed, R=R, shared={k: v[idx] for k, v in sh.items()})
+def space_rows(B, T, P):
+    return layout_rows('space', B, T, P)
+
+
+def _layout_case(layout, B, T, P, H, kind, bwd, seed, hd):
+    """A case of one of layout_rows' layouts.  Where the sequences of a clip share its cls row ('space': the T frames,
+    'time_cls': the P patch positions) the row's code, Q, K and V are drawn once per (clip, head); 'space_nocls' has no shared
+    row: its items are contig_case's, the cls rows of qkv stay NaN (no kernel may read them) and the cls rows of the
+    expected dqkv are zeros."""
+    rin, rout = layout_rows(layout, B, T, P)
+    S, L = rin.shape
+    D = H * hd
+    cls_group = {'space': T, 'time_cls': P, 'space_nocls': 0}[layout]
+    if cls_group:
+        R = routing_dims(int(math.ceil(L / 1.3)) + 2)
+        sh = shared_rows(B * H, hd, R, kind, bwd, seed + 1)
+        # item n = s * H + h uses the shared rows of (b, h), b = s // cls_group
+        idx = (np.arange(S)[:, None] // cls_group * H + np.arange(H)[None, :]).reshape(-1)
+        it = build_items(S * H, L, L, hd, kind, bwd, seed, R=R, shared={k: v[idx] for k, v in sh.items()})
+    else:
+        it = build_items(S * H, L, L, hd, kind, bwd, seed)
     r = reference(it)
     if bwd:
         assert_edges(it, r)
     c = Case()
     c.layout, c.S, c.L, c.H, c.hd, c.B, c.T, c.P, c.kind, c.bwd, c.items, c.ref = \
-        'space', S, L, H, hd, B, T, P, kind, bwd, it, r
-    rin, rout = space_rows(B, T, P)
-    rows, orows = B * (1 + P * T), B * P * T + S
+        layout, S, L, H, hd, B, T, P, kind, bwd, it, r
+    c.cls_group = cls_group
+    rows, orows = B * (1 + P * T), B * P * T + (S if cls_group else 0)
+    c.cls_rows = np.arange(B) * (1 + P * T)
     c.qkv = np.full((rows, 3 * D), np.nan)
     for j, a in enumerate((it.Q, it.K, it.V)):
         c.qkv[rin.reshape(-1), j * D:(j + 1) * D] = _sh(a, S, H, L, hd).reshape(S * L, D)
-    assert not np.isnan(c.qkv).any()
+    assert np.isnan(c.qkv).any(1).sum() == (0 if cls_group else B)
     c.dout = np.zeros((orows, D))
     c.dout[rout.reshape(-1)] = _sh(it.dO, S, H, L, hd).reshape(S * L, D)
     c.out = np.zeros((orows, D))
@@ -405,13 +445,31 @@ def space_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
     c.lse = r['lse'].numpy().reshape(S, H, L)
     c.nwin = it.nwin.reshape(S, H, L)
     if bwd:
+        i0 = 1 if cls_group else 0
         for key in ('', '_abs', '_n'):
             full = np.concatenate([_sh(r[n + key].numpy(), S, H, L, hd) for n in ('dq', 'dk', 'dv')], 2)   # [S, L, 3D]
-            d = np.full((rows, 3 * D), np.nan)
-            d[rin[:, 1:].reshape(-1)] = full[:, 1:].reshape(-1, 3 * D)
+            d = np.full((rows, 3 * D), np.nan if cls_group else 0.0)
+            d[rin[:, i0:].reshape(-1)] = full[:, i0:].reshape(-1, 3 * D)
             c.__dict__['dqkv' + key] = d
-            c.__dict__['dqkv_cls' + key] = full[:, 0].copy()
+            if cls_group:
+                c.__dict__['dqkv_cls' + key] = full[:, 0].copy()
     return c
+
+
+def space_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
+    """VTX_ATTN_SPACE."""
+    return _layout_case('space', B, T, P, H, kind, bwd, seed, hd)
+
+
+def time_cls_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
+    """VTX_ATTN_TIME_CLS: sequence s = (b, p) of L = 1 + T rows whose row 0 is the cls row that the P sequences of clip b
+    share."""
+    return _layout_case('time_cls', B, T, P, H, kind, bwd, seed, hd)
+
+
+def space_nocls_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
+    """VTX_ATTN_SPACE_NOCLS: sequence s = (b, t) of the L = P token rows of frame t."""
+    return _layout_case('space_nocls', B, T, P, H, kind, bwd, seed, hd)
 
 
 def cross_case(B, Lq, Lk, heads, hd, kind='exact', bwd=True, seed=0):

@@ -1,6 +1,7 @@
 """CPU checks of the routed-score attention cases (tests/exact_attn.py): the premise of every case table that
-test_gpu_exact_attention.py uses, and that the exact comparison rejects the attention faults a float64 tolerance check
-lets through.  Faults are emulated in float64 (a dense softmax over the key set the faulty kernel would see) and stored
+test_gpu_exact_attention.py and test_gpu_exact_attn_layouts.py use, exact_attn.layout_rows against the row addressing that
+include/vtx.h states, and that the exact comparison rejects the attention faults a float64 tolerance check lets through.
+Faults are emulated in float64 (a dense softmax over the key set the faulty kernel would see) and stored
 as the kernels store them (float64 -> float32 -> RNE bf16)."""
 import math
 
@@ -10,6 +11,7 @@ import torch
 
 import exact as X
 import exact_attn as A
+import test_gpu_exact_attn_layouts as G
 from helpers import relerr, report
 
 OUT_BAR, GRAD_BAR = 1e-2, 2e-2       # the relerr bars test_gpu_kernels.py holds bf16 attention outputs / gradients to
@@ -33,12 +35,77 @@ def test_routing_premises():
         A.cross_case(2, 300, 37, 2, hd)
         A.cross_case(1, 2500, 393, 2, hd)
         A.expect('round', A.cross_case(2, 300, 37, 2, hd, 'round', False).out, torch.bfloat16, 'round')
+    # test_gpu_cls_order.py and every case of test_gpu_exact_attn_layouts.py (time_cls at L = 3 among them: three keys, two
+    # of them required, one partition that serves), and space at P = 2
+    for T, P in ((8, 7), (16, 5)):
+        A.time_cls_case(3, T, P, 5)
+    A.space_case(2, 3, 2, 2)
+    assert {k[:4] for k in G.CASES} >= {('time_cls', 3, 2, 7), ('space_nocls', 3, 4, 1), ('space_nocls', 2, 3, 196)}
+    for key in sorted(G.CASES):
+        c = G.build(key)
+        assert (c.layout, c.B, c.T, c.P, c.H, c.kind, c.bwd) == key
+        assert c.cls_group == {'space': c.T, 'time_cls': c.P, 'space_nocls': 0}[c.layout]
+        A.expect(str(key), c.out, torch.bfloat16, c.kind)
 
 
 def test_routing_premise_bench_scale():
-    """The bench-scale cases of the streamed kernels (840 and 1152 items)."""
+    """The bench-scale cases of the streamed kernels (840 and 1152 items) and of the fused backward on space_nocls (576)."""
     A.contig_case(70, 197, 12)
     A.space_case(6, 8, 196, 12)
+    assert G.BENCH_CASES
+    for key in sorted(G.BENCH_CASES):
+        G.build(key)
+
+
+LAYOUT_SHAPES = ((2, 3, 5), (3, 4, 2), (2, 1, 7))
+
+
+@pytest.mark.parametrize('mode', ['space', 'time_cls', 'space_nocls'])
+def test_layout_rows_cover_every_row_once(mode):
+    for B, T, P in LAYOUT_SHAPES:
+        rin, rout = A.layout_rows(mode, B, T, P)
+        rpc = 1 + P * T
+        share = {'space': T, 'time_cls': P, 'space_nocls': 0}[mode]
+        S, L = {'space': (B * T, P + 1), 'time_cls': (B * P, T + 1), 'space_nocls': (B * T, P)}[mode]
+        assert rin.shape == rout.shape == (S, L)
+        want = np.ones(B * rpc, np.int64)
+        want[np.arange(B) * rpc] = share            # the cls row: once per sequence that shares it; never for space_nocls
+        assert np.array_equal(np.bincount(rin.reshape(-1), minlength=B * rpc), want), (mode, B, T, P)
+        out_rows = B * P * T + (S if share else 0)
+        assert np.array_equal(np.bincount(rout.reshape(-1), minlength=out_rows), np.ones(out_rows, np.int64)), (mode, B, T, P)
+        if share:                                   # the sequences that share a cls row are those of one clip, in order
+            assert np.array_equal(rin[:, 0], np.repeat(np.arange(B) * rpc, share))
+            assert np.array_equal(rout[:, 0], B * P * T + np.arange(S))
+
+
+def test_layout_rows_are_the_rows_of_the_header():
+    """include/vtx.h, written out with loops: qkv is [B, 1 + P T, 3D] with tokens in (p t) order; out holds the token rows
+    clip-major in (p t) order, then (space, time_cls) one cls row per sequence."""
+    for B, T, P in LAYOUT_SHAPES:
+        rpc, N = 1 + P * T, P * T
+        for mode in ('space', 'time_cls', 'space_nocls'):
+            rin, rout = A.layout_rows(mode, B, T, P)
+            for b in range(B):
+                clip_in, clip_out = b * rpc, b * N
+                if mode == 'time_cls':
+                    for p in range(P):
+                        s = b * P + p
+                        assert rin[s, 0] == clip_in and rout[s, 0] == B * N + s
+                        for i in range(1, T + 1):           # row 1 + p T + (i - 1) of clip b: frame i - 1 of patch p
+                            assert rin[s, i] == clip_in + 1 + p * T + (i - 1)
+                            assert rout[s, i] == clip_out + p * T + (i - 1)
+                    continue
+                for t in range(T):
+                    s = b * T + t
+                    if mode == 'space':
+                        assert rin[s, 0] == clip_in and rout[s, 0] == B * N + s
+                        for i in range(1, P + 1):           # token 1 + (i - 1) T + t: patch i - 1 of frame t
+                            assert rin[s, i] == clip_in + 1 + (i - 1) * T + t
+                            assert rout[s, i] == clip_out + (i - 1) * T + t
+                    else:
+                        for i in range(P):                  # row 1 + i T + t: patch i of frame t
+                            assert rin[s, i] == clip_in + 1 + i * T + t
+                            assert rout[s, i] == clip_out + i * T + t
 
 
 def test_premise_rejects_broken_routing():
@@ -75,6 +142,68 @@ def _verdict(name, got_bf16, want_bf16, exact, bar):
 
 def _trunc_bf16(v):
     return (torch.as_tensor(v).float().view(torch.int32) & ~0xFFFF).view(torch.float32).to(torch.bfloat16)
+
+
+def _gathered_out(qkv, hd, rq, rkv, pad=0):
+    """[S, L, hd] float64 outputs of a one-head kernel that gathers the query of (s, i) from row rq[s, i] of qkv [rows, 3 hd]
+    and its key / value from row rkv[s, i], with `pad` unmasked zero rows after the keys."""
+    z = np.zeros((pad, hd))
+    return np.stack([_dense_out(qkv[q, :hd], np.vstack([qkv[k, hd:2 * hd], z]), np.vstack([qkv[k, 2 * hd:], z]))
+                     for q, k in zip(rq, rkv)])
+
+
+def _layout_addressing_faults():
+    """Addressing faults of VTX_ATTN_TIME_CLS and VTX_ATTN_SPACE_NOCLS, one head (so a row of qkv is q | k | v of one item).
+    The outputs land where they belong; the operands come from the rows the faulty kernel would compute."""
+    # ---- time_cls: B = 2 clips of P = 3 sequences, L = 1 + 8
+    c = A.time_cls_case(2, 8, 3, 1)
+    hd, rpc = c.hd, 1 + c.P * c.T
+    rin, _ = A.layout_rows('time_cls', c.B, c.T, c.P)
+    b = np.arange(c.S)[:, None] // c.P
+    want, exact = X.rne_bf16(c.ref['O']), c.ref['O']
+    clean = lambda got, ref: not X.mismatch(X.rne_bf16(torch.from_numpy(got)), ref).any()          # noqa: E731
+    assert clean(_gathered_out(c.qkv, hd, rin, rin), want)            # the emulation itself, without a fault
+    bad = rin.copy()
+    bad[:, 1:] -= b                                                   # s T + i instead of s T + b + i
+    got = _gathered_out(c.qkv, hd, bad, bad)
+    assert clean(got[:c.P], want[:c.P])                               # clip 0 has no offset to lose
+    _verdict('time_cls: token rows without the clip offset (clips b >= 1)', X.rne_bf16(torch.from_numpy(got)), want, exact,
+             OUT_BAR)
+    bad = rin.copy()
+    bad[:, 0] = np.maximum(b[:, 0] - 1, 0) * rpc                      # the cls key / value of clip b - 1
+    _verdict('time_cls: cls key taken from clip b - 1', X.rne_bf16(torch.from_numpy(_gathered_out(c.qkv, hd, rin, bad))),
+             want, exact, OUT_BAR)
+    # the per-sequence cls gradient of (b, p) stored in the row of (b, p + 1): what vtx_cls_qkv_reduce folds is unchanged
+    W = 3 * hd
+    good = c.dqkv_cls.reshape(c.B, c.P, W)
+    moved = np.roll(good, 1, axis=1)
+    assert np.array_equal(moved.sum(1), good.sum(1)), 'the reduced cls row sees the fault'
+    _verdict('time_cls: dqkv_cls row of sequence s written to row s + 1 (reduced row unchanged)',
+             X.rne_bf16(torch.from_numpy(moved.reshape(c.S, W))), X.rne_bf16(torch.from_numpy(c.dqkv_cls)),
+             torch.from_numpy(c.dqkv_cls), GRAD_BAR)
+    # ---- space_nocls: B = 2 clips of T = 3 frames, P = 16.  The cls rows of the case are NaN; a model's hold data, so here
+    # they hold a copy of the clip's last token row (routed like every other row)
+    c = A.space_nocls_case(2, 3, 16, 1)
+    hd, rpc = c.hd, 1 + c.P * c.T
+    rin, _ = A.layout_rows('space_nocls', c.B, c.T, c.P)
+    qkv = c.qkv.copy()
+    qkv[c.cls_rows] = qkv[c.cls_rows + rpc - 1]
+    want, exact = X.rne_bf16(c.ref['O']), c.ref['O']
+    assert clean(_gathered_out(qkv, hd, rin, rin), want)
+    got = _gathered_out(qkv, hd, rin - 1, rin - 1)                    # i T + t: the cls row is token 0 of frame 0
+    _verdict('space_nocls: rows without the + 1 that skips the cls row', X.rne_bf16(torch.from_numpy(got)), want, exact,
+             OUT_BAR)
+    s = np.arange(c.S)[:, None]
+    i = np.arange(c.L)[None, :]
+    bad = s // c.T * rpc + 1 + i * (c.T + 1) + s % c.T                 # stride T + 1
+    first = slice(0, c.T)                                             # clip 0: its overrun stays inside the buffer (clip 1)
+    assert bad[first].max() < c.qkv.shape[0]
+    got = _gathered_out(qkv, hd, bad[first], bad[first])
+    _verdict('space_nocls: rows read with stride T + 1', X.rne_bf16(torch.from_numpy(got)), want[first], exact[first],
+             OUT_BAR)
+    got = _gathered_out(qkv, hd, rin, rin, pad=32 - c.P)
+    _verdict('space_nocls: the 32 - P zero pad rows of the single tile unmasked', X.rne_bf16(torch.from_numpy(got)), want,
+             exact, OUT_BAR)
 
 
 def test_check_exact_rejects_attention_faults():
@@ -115,6 +244,7 @@ def test_check_exact_rejects_attention_faults():
     bad = _item_out(c, stride)
     _verdict('space mode: frame stride off by one', X.rne_bf16(torch.from_numpy(bad)), X.rne_bf16(c.ref['O']),
              c.ref['O'], OUT_BAR)
+    _layout_addressing_faults()
     # backward faults on L = 197: the last key tile dropped from dk / dv; a dS mask one row early drops the last real key
     c = A.contig_case(3, 197, 2, seed=5)
     it, r = c.items, c.ref

@@ -14,10 +14,10 @@ runs without the cls token (VTX_ATTN_SPACE_NOCLS, vtx.functions.AttnFn kind 'spa
   4. recompute against stored activations, bit for bit, and the direct-gradient path against autograd's accumulation;
   5. exact arithmetic (tests/exact_attn.py: routed inputs whose results have one correct bf16 value each) for the packed
      TIME_CLS kernels at L = 9 and 17, with one head and with several heads per workgroup: out, lse, dqkv and dqkv_cls are
-     compared for equality, so a cls row gathered from or scattered to the wrong row shows as such, not as rounding.
+     compared for equality, so a cls row gathered from or scattered to the wrong row shows as such, not as rounding.  The
+     other kernel families of the two layouts are held to the same standard in tests/test_gpu_exact_attn_layouts.py.
 """
 import json
-import math
 import os
 
 import numpy as np
@@ -299,74 +299,16 @@ def test_direct_gradients_equal_autograd(prec):
 
 
 # ------------------------------------------------------------------------------------------------ 5. exact arithmetic
-def time_cls_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
-    """exact_attn.space_case for VTX_ATTN_TIME_CLS: sequence s = (b, p) of L = 1 + T rows whose row 0 is the cls row that the P
-    sequences of clip b share per head; qkv / dout / out laid out by the layout's in_row / out_row (attn_common.h).  The Case
-    is handed to the runners of tests/test_gpu_exact_attention.py as a 'space' case with the roles of T and P exchanged
-    (c.T = sequences per clip, c.P = tokens per sequence): they then size dqkv_cls by S, tell cls rows from token rows by the
-    NaN rows of c.dqkv and fold the per-sequence cls rows with vtx_cls_qkv_reduce over c.T = P rows -- see _time_cls_desc."""
-    import exact_attn as A
-    S, L, Dm = B * P, T + 1, H * hd
-    R = A.routing_dims(int(math.ceil(L / 1.3)) + 2)
-    sh = A.shared_rows(B * H, hd, R, kind, bwd, seed + 1)
-    idx = (np.arange(S)[:, None] // P * H + np.arange(H)[None, :]).reshape(-1)      # item (b P + p) H + h: the rows of (b, h)
-    it = A.build_items(S * H, L, L, hd, kind, bwd, seed, R=R, shared={k: v[idx] for k, v in sh.items()})
-    r = A.reference(it)
-    if bwd:
-        A.assert_edges(it, r)
-    c = A.Case()
-    c.layout, c.S, c.L, c.H, c.hd, c.B, c.T, c.P, c.kind, c.bwd, c.items, c.ref = 'space', S, L, H, hd, B, P, T, kind, bwd, it, r
-    sq, i = np.arange(S)[:, None], np.arange(L)[None, :]
-    b = sq // P
-    rin = np.where(i == 0, b * (1 + P * T), sq * T + b + i)
-    rout = np.where(i == 0, B * P * T + sq, sq * T + i - 1)
-    rows, orows = B * (1 + P * T), B * P * T + S
-    assert sorted(set(rin.reshape(-1))) == list(range(rows)) and sorted(rout.reshape(-1)) == list(range(orows))
-    c.qkv = np.full((rows, 3 * Dm), np.nan)
-    for j, a in enumerate((it.Q, it.K, it.V)):
-        c.qkv[rin.reshape(-1), j * Dm:(j + 1) * Dm] = A._sh(a, S, H, L, hd).reshape(S * L, Dm)
-    assert not np.isnan(c.qkv).any()
-    c.dout = np.zeros((orows, Dm))
-    c.dout[rout.reshape(-1)] = A._sh(it.dO, S, H, L, hd).reshape(S * L, Dm)
-    c.out = np.zeros((orows, Dm))
-    c.out[rout.reshape(-1)] = A._sh(r['O'].numpy(), S, H, L, hd).reshape(S * L, Dm)
-    c.lse = r['lse'].numpy().reshape(S, H, L)
-    c.nwin = it.nwin.reshape(S, H, L)
-    if bwd:
-        for key in ('', '_abs', '_n'):
-            full = np.concatenate([A._sh(r[n + key].numpy(), S, H, L, hd) for n in ('dq', 'dk', 'dv')], 2)   # [S, L, 3D]
-            d = np.full((rows, 3 * Dm), np.nan)
-            d[rin[:, 1:].reshape(-1)] = full[:, 1:].reshape(-1, 3 * Dm)
-            c.__dict__['dqkv' + key] = d
-            c.__dict__['dqkv_cls' + key] = full[:, 0].copy()
-    return c
-
-
-@pytest.fixture
-def time_cls_runner(monkeypatch):
-    """The forward / backward runners of tests/test_gpu_exact_attention.py with the descriptor of a time_cls_case: mode
-    VTX_ATTN_TIME_CLS, T and P back in their own fields."""
-    import test_gpu_exact_attention as E
-    from vtx import _lib
-    plain = E.attn_desc
-
-    def desc(c, *a, **k):
-        d = plain(c, *a, **k)
-        d.mode, d.T, d.P = _lib.ATTN_TIME_CLS, c.P, c.T
-        return d
-    monkeypatch.setattr(E, 'attn_desc', desc)
-    return E
-
-
 @pytest.mark.parametrize('hw', ['0', '3', '16'])
 @pytest.mark.parametrize('T,P', [(8, 7), (16, 5)], ids=['L9', 'L17'])
-def test_time_cls_packed_kernels_exact(T, P, hw, vtx_opts, time_cls_runner):
+def test_time_cls_packed_kernels_exact(T, P, hw, vtx_opts):
     """attn_fwd_small_kernel<HW, true>, attn_bwd_small_kernel<HW, true>.  B * P = 21 / 15 sequences: not a multiple of the 3
     sequences a tile holds at L = 9, and tiles that straddle two clips (two different cls rows in one tile); H = 5 does not
-    divide into groups of 3 or 16."""
-    E = time_cls_runner
+    divide into groups of 3 or 16.  The case is exact_attn.time_cls_case, run by the layout-aware runners of
+    tests/test_gpu_exact_attention.py."""
+    import test_gpu_exact_attention as E
     vtx_opts('attn_hw_fwd', hw)
     vtx_opts('attn_hw_bwd', hw)
-    c = time_cls_case(3, T, P, 5)
+    c = E.time_cls(3, T, P, 5)
     qkv, out, lse = E.run_fwd(c, BF16)
     E.run_bwd(c, BF16, qkv, out, lse, True)

@@ -40,6 +40,16 @@ def space(B, T, P, H, kind='exact', bwd=True, seed=0):
 
 
 @functools.lru_cache(maxsize=None)
+def time_cls(B, T, P, H, kind='exact', bwd=True, seed=0):
+    return A.time_cls_case(B, T, P, H, kind, bwd, seed)
+
+
+@functools.lru_cache(maxsize=None)
+def space_nocls(B, T, P, H, kind='exact', bwd=True, seed=0):
+    return A.space_nocls_case(B, T, P, H, kind, bwd, seed)
+
+
+@functools.lru_cache(maxsize=None)
 def cross(B, Lq, Lk, heads, hd, kind='exact', bwd=True, seed=0):
     return A.cross_case(B, Lq, Lk, heads, hd, kind, bwd, seed)
 
@@ -71,10 +81,11 @@ def _dt(dtype):
 
 
 def _mfma_path(c, dtype, valu):
-    """Whether vtx_attn_* takes the bf16 MFMA kernels (attn.hip: attn_route, SMALL / MFMA)."""
+    """Whether vtx_attn_* takes the bf16 MFMA kernels (attn.hip: attn_route, SMALL / MFMA): contig and time_cls 1..256 tokens
+    (packed up to 32), space_nocls 1..256 (one tile up to 32), space 33..256."""
     if dtype != BF16 or valu:
         return False
-    return c.L <= 256 and (c.layout == 'contig' or c.L > 32)
+    return c.L <= 256 and (c.layout != 'space' or c.L > 32)
 
 
 def _check_bounded(name, got, c, key, dtype, guards=None):
@@ -106,16 +117,19 @@ def _check_mask(name, ok, what):
 
 
 # ------------------------------------------------------------------------------------------------ self-attention
+QKV_PAD = {'contig': 0, 'space': 0, 'time_cls': PAD, 'space_nocls': PAD}      # NaN columns after every row of qkv
+
+
 def attn_desc(c, dtype, qkv, out, lse, probs=None):
     L = _lib()
     d = L.AttnDesc()
     d.dtype = _dt(dtype)
-    d.mode = L.ATTN_SPACE if c.layout == 'space' else L.ATTN_CONTIG
+    d.mode = {'contig': L.ATTN_CONTIG, 'space': L.ATTN_SPACE, 'time_cls': L.ATTN_TIME_CLS,
+              'space_nocls': L.ATTN_SPACE_NOCLS}[c.layout]
     d.S, d.L, d.H, d.hd = c.S, c.L, c.H, c.hd
-    if c.layout == 'space':
-        d.B, d.T, d.P = c.B, c.T, c.P
+    d.B, d.T, d.P = c.B, c.T, c.P
+    d.qkv, d.ld_qkv = qkv.data_ptr(), qkv.stride(0)
     D = c.H * c.hd
-    d.qkv, d.ld_qkv = qkv.data_ptr(), 3 * D
     d.out, d.ld_out = out.data_ptr(), D + PAD
     d.lse = lse.data_ptr()
     d.probs = None if probs is None else probs.data_ptr()
@@ -123,10 +137,18 @@ def attn_desc(c, dtype, qkv, out, lse, probs=None):
     return d
 
 
+def _shape(c):
+    btp = '' if c.layout == 'contig' else f' B={c.B} T={c.T} P={c.P}'
+    return f'{c.layout}{btp} S={c.S} L={c.L} H={c.H}'
+
+
 def run_fwd(c, dtype, probs=False):
-    """Forward with guarded outputs; checks out, lse (and probs).  Returns (qkv, out, lse) device tensors."""
+    """Forward with guarded outputs; checks out, lse (and probs).  Returns (qkv, out, lse) device tensors.  In the
+    time_cls and space_nocls layouts qkv has PAD columns of NaN after every row (ld_qkv = 3D + PAD): a kernel that takes
+    ld_qkv for 3D reads them."""
     D, n = c.H * c.hd, c.S * c.H * c.L
-    qkv = torch.from_numpy(c.qkv).to(dtype).to(DEV).contiguous()
+    qkv = torch.full((c.qkv.shape[0], 3 * D + QKV_PAD[c.layout]), float('nan'), dtype=dtype, device=DEV)
+    qkv[:, :3 * D] = torch.from_numpy(c.qkv).to(dtype).to(DEV)
     rows = c.out.shape[0]
     out = X.guarded((rows + 2, D), dtype, DEV, PAD)
     lse = X.sentinel_fill(torch.empty(n + PAD, device=DEV))
@@ -134,12 +156,14 @@ def run_fwd(c, dtype, probs=False):
     d = attn_desc(c, dtype, qkv, out, lse, pr)
     _lib().call('vtx_attn_fwd', C.byref(d), _stream())
     torch.cuda.synchronize()
-    name = f'attn fwd {c.layout} S={c.S} L={c.L} H={c.H} {c.kind} {dtype}'
+    name = f'attn fwd {_shape(c)} {c.kind} {dtype}'
     X.check_exact(name, out[:rows, :D], A.expect(name, c.out, dtype, c.kind),
                   {'ld_out pad': out[:, D:], 'rows after the last sequence': out[rows:, :D]})
     _check_mask(f'{name} lse', A.lse_ok(lse[:n].cpu(), c.nwin.reshape(-1)), '0 for one winner, 4 ulps of k ln2')
     X.check_exact(f'{name} lse tail', lse[n:], lse[n:].cpu(), {'lse tail': lse[n:]})
     if probs:
+        # probs is [S, H, L, L] whatever the layout: the block of item n = s H + h is indexed by the positions i, j in
+        # the sequence, not by the rows they sit on
         want = np.zeros((c.S * c.H, c.L, c.L))
         it = c.items
         i_idx = np.arange(c.L)[None, :, None].repeat(it.I, 0).repeat(4, 2)
@@ -153,8 +177,10 @@ def run_fwd(c, dtype, probs=False):
 
 
 def run_bwd(c, dtype, qkv, out, lse, exact):
-    """Backward from the forward's own out / lse; checks dqkv (and, in space mode, dqkv_cls, the untouched cls rows and
-    cls_qkv_reduce).  exact: RNE equality (MFMA) or the interval check (VALU).  Returns the device outputs."""
+    """Backward from the forward's own out / lse; checks dqkv and, where c.cls_group sequences share a cls row (space,
+    time_cls), dqkv_cls (one row per sequence), the untouched cls rows and cls_qkv_reduce over c.cls_group rows.  space_nocls
+    passes no dqkv_cls, and the cls rows of dqkv must hold +0 over exactly 3D columns.  exact: RNE equality (MFMA) or the
+    interval check (VALU).  Returns the device outputs."""
     L_ = _lib()
     D = c.H * c.hd
     W = 3 * D
@@ -168,34 +194,49 @@ def run_bwd(c, dtype, qkv, out, lse, exact):
     delta = torch.empty(c.S * c.H * c.L, device=DEV)
     b.delta = delta.data_ptr()
     dcls = None
-    if c.layout == 'space':
+    if c.cls_group:
         dcls = X.guarded((c.S + 2, W), dtype, DEV, PAD)
         b.dqkv_cls = dcls.data_ptr()
+    else:
+        b.dqkv_cls = None
     L_.call('vtx_attn_bwd', C.byref(b), _stream())
     torch.cuda.synchronize()
-    name = f'attn bwd {c.layout} S={c.S} L={c.L} H={c.H} {dtype}'
+    name = f'attn bwd {_shape(c)} {dtype}'
     guards = {'ld_dqkv pad': dqkv[:, W:], 'rows after the last sequence': dqkv[rows:, :W]}
-    if c.layout == 'space':
+    if c.cls_group:
         tok = torch.from_numpy(~np.isnan(c.dqkv[:, 0]))
         cls_rows = torch.nonzero(~tok).reshape(-1)
+        assert cls_rows.tolist() == c.cls_rows.tolist()
         guards['clip cls rows'] = dqkv[cls_rows.to(DEV), :W]
         got_tok = dqkv[:rows, :W][tok.to(DEV)]
         sub = {k: getattr(c, 'dqkv' + k)[tok.numpy()] for k in ('', '_abs', '_n')}
     else:
         got_tok, sub = dqkv[:rows, :W], {k: getattr(c, 'dqkv' + k) for k in ('', '_abs', '_n')}
+    if c.layout == 'space_nocls':
+        # the cls rows of dqkv: +0 bit for bit over exactly 3D columns (check_exact lets -0 pass for 0), their pad columns
+        # still the sentinel
+        cls_rows = torch.from_numpy(c.cls_rows).to(DEV)
+        zrows = dqkv[cls_rows]
+        nz = int((zrows[:, :W].contiguous().view(torch.int16 if dtype == BF16 else torch.int32) != 0).sum())
+        touched = X.sentinel_touched(zrows[:, W:])
+        ok = nz == 0 and touched == 0
+        X.report(f'{"ok  " if ok else "FAIL"} exact {name} cls rows of dqkv: {zrows[:, :W].numel()} elements (+0), '
+                 f'{nz} not +0, {touched} pad elements overwritten')
+        assert ok, f'{name}: cls rows of dqkv: {nz} elements are not +0, {touched} pad elements overwritten'
     _check_self_grad(name, got_tok, sub, dtype, exact, guards)
-    if c.layout == 'space':
+    if c.cls_group:
         csub = {k: getattr(c, 'dqkv_cls' + k) for k in ('', '_abs', '_n')}
         _check_self_grad(f'{name} per-frame cls rows', dcls[:c.S, :W], csub, dtype, exact,
                          {'ld_dqkv pad': dcls[:, W:], 'rows after the last frame': dcls[c.S:, :W]})
-        # cls_qkv_reduce: fp32 sum over t of the stored per-frame rows, in frame order, stored once (vtx.h)
+        # cls_qkv_reduce: fp32 sum of the stored rows of the cls_group sequences that share the cls row, in sequence order,
+        # stored once (vtx.h)
         rpc = 1 + c.P * c.T
-        L_.call('vtx_cls_qkv_reduce', _dt(dtype), c.B, c.T, W, dcls.data_ptr(), W + PAD, dqkv.data_ptr(), W + PAD, rpc,
+        L_.call('vtx_cls_qkv_reduce', _dt(dtype), c.B, c.cls_group, W, dcls.data_ptr(), W + PAD, dqkv.data_ptr(), W + PAD, rpc,
                 _stream())
         torch.cuda.synchronize()
-        frames = dcls[:c.S, :W].cpu().float().reshape(c.B, c.T, W)
+        frames = dcls[:c.S, :W].cpu().float().reshape(c.B, c.cls_group, W)
         acc = torch.zeros(c.B, W)
-        for t in range(c.T):
+        for t in range(c.cls_group):
             acc = acc + frames[:, t]
         X.check_exact(f'{name} cls_qkv_reduce', dqkv[cls_rows.to(DEV), :W], acc.to(dtype),
                       {'ld_dqkv pad': dqkv[:, W:]})
