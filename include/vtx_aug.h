@@ -62,8 +62,11 @@ int vtx_clip_resample_u8(int B, int T, int Hs, int Ws, int H, int W, const unsig
  * {r, r, r, 1 - r, 1 - r, 1 - r}, entry i and 3 + i belong to op i of the record (torchvision forms 1.0 - r in float64
  * and rounds it to float32 on its own: so does the caller).  Each op is  trunc(clamp(r * img + (1 - r) * other, 0, 255))
  * in float32 (two products, one add); other = 0 | the frame's mean of grey | the pixel's grey, grey = trunc(0.2989 r + 0.587 g + 0.114 b).
- * The mean is the integer sum of the frame's greys divided once in float32 (= torch.mean while the sum stays below
- * 2^24, i.e. up to 65 793 pixels per frame).  Hue is not built (the reference passes three jitter values).
+ * The mean is the exact integer sum of the frame's greys, converted to float32 and divided once by the pixel count.
+ * Bit-identical to torchvision's arithmetic up to 65 793 pixels per frame (the sum stays below 2^24, so torch.mean of
+ * the float32 greys is that value whatever its summation order); on larger frames (448 x 448 = 200 704 pixels)
+ * torch.mean's own float32 sum is no longer exact and depends on its order, and the call returns the exactly summed,
+ * once-rounded mean instead.  Hue is not built (the reference passes three jitter values).
  * workspace: vtx_clip_jitter_workspace(B, T) bytes, 4-byte aligned, zeroed by the call. */
 size_t vtx_clip_jitter_workspace(int B, int T);
 int vtx_clip_jitter_u8(int B, int T, int H, int W, unsigned char* clip, const int32_t* ops, const float* factors,

@@ -77,14 +77,22 @@ def _grey(img):
     return (0.2989 * r + 0.587 * g + 0.114 * b).to(img.dtype).unsqueeze(dim=-3)
 
 
-def jitter_ref(frames_u8, jit_ops, factors):
-    """uint8 [T,H,W,3]; ops in order (0 brightness, 1 contrast, 2 saturation), one factor each -> uint8 [T,H,W,3]."""
+def jitter_ref(frames_u8, jit_ops, factors, exact_mean=False):
+    """uint8 [T,H,W,3]; ops in order (0 brightness, 1 contrast, 2 saturation), one factor each -> uint8 [T,H,W,3].
+    exact_mean: the contrast mean is float32(the int64 sum of the greys) / float32(H W) instead of torch.mean of the float32 greys.
+    The two agree while the sum stays below 2^24 (every frame of up to 65 793 pixels); beyond, torch.mean's value depends on its
+    summation order (thread count, vector width) and the exact sum is what the device computes."""
     img = frames_u8.permute(0, 3, 1, 2).contiguous()
     for op, f in zip(jit_ops, factors):
         if op == 0:
             img = _blend(img, torch.zeros_like(img), f)
         elif op == 1:
-            mean = torch.mean(_grey(img).to(torch.float32), dim=(-3, -2, -1), keepdim=True)
+            grey = _grey(img)
+            if exact_mean:
+                total = grey.to(torch.int64).sum(dim=(-3, -2, -1), keepdim=True)
+                mean = total.to(torch.float32) / torch.tensor(float(grey[0].numel()), dtype=torch.float32)
+            else:
+                mean = torch.mean(grey.to(torch.float32), dim=(-3, -2, -1), keepdim=True)
             img = _blend(img, mean, f)
         elif op == 2:
             img = _blend(img, _grey(img), f)
