@@ -1,4 +1,4 @@
-"""Build libvtx.so, libvtx_aug.so, libvtx_randaug.so, libvtx_views.so, libvtx_mix.so, libvtx_stem.so and libvtx_ragged.so (gfx950) with hipcc -- no torch headers, no cmake.
+"""Build libvtx.so, libvtx_aug.so, libvtx_randaug.so, libvtx_views.so, libvtx_mix.so, libvtx_stem.so, libvtx_ragged.so and libvtx_dropout.so (gfx950) with hipcc -- no torch headers, no cmake.
 
     python videotransformer-pytorch_amd/csrc/build.py [--force]
 
@@ -9,7 +9,8 @@ videotransformer-pytorch_amd/libvtx_randaug.so, csrc/views.hip (test-time views,
 videotransformer-pytorch_amd/libvtx_views.so and csrc/mix.hip (Mixup / CutMix on uint8 clips, include/vtx_mix.h)
 videotransformer-pytorch_amd/libvtx_mix.so, csrc/stem.hip (MaskFeat from uint8 clips: the Conv3d stem gather and the HOG of
 selected frames, include/vtx_stem.h) videotransformer-pytorch_amd/libvtx_stem.so, csrc/ragged.hip (views of clips that differ in
-source size, include/vtx_ragged.h) videotransformer-pytorch_amd/libvtx_ragged.so.  hipcc cross-compiles without a GPU.
+source size, include/vtx_ragged.h) videotransformer-pytorch_amd/libvtx_ragged.so, csrc/dropout.hip (dropout without a stored
+mask, include/vtx_dropout.h) videotransformer-pytorch_amd/libvtx_dropout.so.  hipcc cross-compiles without a GPU.
 """
 import os
 import subprocess
@@ -25,6 +26,7 @@ VIEWS_OUT = os.path.join(PKG, 'libvtx_views.so')
 MIX_OUT = os.path.join(PKG, 'libvtx_mix.so')
 STEM_OUT = os.path.join(PKG, 'libvtx_stem.so')
 RAGGED_OUT = os.path.join(PKG, 'libvtx_ragged.so')
+DROPOUT_OUT = os.path.join(PKG, 'libvtx_dropout.so')
 OBJ = os.path.join(HERE, '_obj')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_mfma.hip', 'attn_long.hip', 'attn_f32.hip', 'elementwise.hip', 'hog.hip', 'optim.hip', 'head.hip', 'mvit.hip', 'wprod.hip', 'xattn_mfma.hip']
@@ -39,6 +41,7 @@ VIEWS_SOURCES = ['views.hip']      # the fourth: frame selection + resize + Thre
 MIX_SOURCES = ['mix.hip']          # the fifth: CutMix on bytes, Mixup inside the patch gather
 STEM_SOURCES = ['stem.hip']        # the sixth: the MViT stem gather from bytes, HOG of selected frames (hog_kernel.h, shared with hog.hip)
 RAGGED_SOURCES = ['ragged.hip']    # the seventh: views.hip's kernel with per-clip base pointer and geometry
+DROPOUT_SOURCES = ['dropout.hip']  # the eighth: mask, DropPath scale and residual in one launch, the mask regenerated in the backward
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result', '-Wno-unused-value', '-Wno-inline-asm',
          '-Wno-cuda-compat']
 EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contraction
@@ -47,7 +50,8 @@ EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contr
          'views.hip': ['-ffp-contract=off'],       # the weighted sums of aug.hip's resampler, byte for byte
          'mix.hip': ['-ffp-contract=off'],         # normalise then blend: five roundings per operand pair
          'stem.hip': ['-ffp-contract=off'],        # hog_kernel.h as hog.hip compiles it; normalise: three roundings per tap
-         'ragged.hip': ['-ffp-contract=off']}      # views.hip's weighted sums, byte for byte
+         'ragged.hip': ['-ffp-contract=off'],      # views.hip's weighted sums, byte for byte
+         'dropout.hip': ['-ffp-contract=off']}     # mask, scale, row scale, residual: four float32 operations, one rounding on the store
 
 
 def _deps():
@@ -59,6 +63,7 @@ def _deps():
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_mix.h'))
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_stem.h'))
     hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_ragged.h'))
+    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_dropout.h'))
     hdrs.append(os.path.abspath(__file__))                       # the flags live here
     return max(os.path.getmtime(h) for h in hdrs)
 
@@ -128,7 +133,7 @@ def _link(out, res, extra, verbose):
 
 
 def _build_locked(force, verbose):
-    every = SOURCES + AUG_SOURCES + RANDAUG_SOURCES + VIEWS_SOURCES + MIX_SOURCES + STEM_SOURCES + RAGGED_SOURCES
+    every = SOURCES + AUG_SOURCES + RANDAUG_SOURCES + VIEWS_SOURCES + MIX_SOURCES + STEM_SOURCES + RAGGED_SOURCES + DROPOUT_SOURCES
     with ThreadPoolExecutor(max_workers=min(8, len(every))) as ex:
         res = list(ex.map(lambda s: _compile(s, force), every))
     n, m = len(SOURCES), len(SOURCES) + len(AUG_SOURCES)
@@ -136,6 +141,7 @@ def _build_locked(force, verbose):
     j = k + len(VIEWS_SOURCES)
     i = j + len(MIX_SOURCES)
     h = i + len(STEM_SOURCES)
+    g = h + len(RAGGED_SOURCES)
     _link(OUT, res[:n], [], verbose)
     # -Bsymbolic: the library's own definitions of the helpers common.h declares, whatever else the process has loaded
     _link(AUG_OUT, res[n:m], ['-Wl,-Bsymbolic'], verbose)
@@ -143,7 +149,8 @@ def _build_locked(force, verbose):
     _link(VIEWS_OUT, res[k:j], ['-Wl,-Bsymbolic'], verbose)
     _link(MIX_OUT, res[j:i], ['-Wl,-Bsymbolic'], verbose)
     _link(STEM_OUT, res[i:h], ['-Wl,-Bsymbolic'], verbose)
-    _link(RAGGED_OUT, res[h:], ['-Wl,-Bsymbolic'], verbose)
+    _link(RAGGED_OUT, res[h:g], ['-Wl,-Bsymbolic'], verbose)
+    _link(DROPOUT_OUT, res[g:], ['-Wl,-Bsymbolic'], verbose)
     return OUT
 
 

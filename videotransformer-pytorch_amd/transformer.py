@@ -7,8 +7,10 @@ each module's forward is one ``torch.autograd.Function`` from ``vtx.functions``
 issuing a short chain of HIP kernels.  There is no PyTorch/CPU fallback -- CPU
 tensors raise (the CPU reference lives in oracle/, used by the tests only).
 
-Not carried over (raise ``NotImplementedError`` when exercised): non-zero
-dropout probabilities (the reference models always pass 0), norm / activation
+Dropout: ``proj_drop`` and the FFN's ``dropout_p`` run as HIP launches whose mask is
+regenerated in the backward pass (include/vtx_dropout.h, vtx_dropout_rows; one seed per
+sub-block forward from the default CPU generator).  Not carried over (raise
+``NotImplementedError`` when exercised): ``attn_drop`` > 0, norm / activation
 classes other than nn.LayerNorm / nn.GELU and FFN num_layers != 2.  Both
 operator orders of divided attention run: time-then-space (the models' own) and
 space-then-time, where the temporal op attends over the cls token and the
@@ -55,8 +57,22 @@ def _build_norm(norm_layer, embed_dims):
 
 def _no_dropout(p, what):
     if p:
-        raise NotImplementedError(f'vtx: {what} > 0 is not supported by the HIP path '
-                                  '(the reference models always use 0)')
+        raise NotImplementedError(f'vtx: {what} > 0 is not supported by the HIP path: the mask would sit inside the attention '
+                                  'kernels (proj_drop and dropout_p are supported; the reference models always use 0)')
+
+
+def _draw_seed():
+    """The seed of one Function call's dropout masks (include/vtx_dropout.h, vtx_dropout_rows): one draw from the default CPU generator,
+    the generator DropPath draws from, so torch.manual_seed reproduces the masks and torch.utils.checkpoint re-draws them."""
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))
+
+
+def _drop_spec(module, p):
+    """(p, seed) for a sub-block whose dropout is active, else None: nothing is drawn with p == 0 or in eval."""
+    if not p or not module.training:
+        return None
+    vtx.ops.dropout_params(p)                        # (range check before anything is drawn)
+    return float(p), _draw_seed()
 
 
 class DropPath(nn.Module):
@@ -221,11 +237,14 @@ class Attention(nn.Module):
 
     def forward(self, x):
         _no_dropout(self.attn_drop.p if self.training else 0, 'attn_drop')
-        _no_dropout(self.proj_drop.p if self.training else 0, 'proj_drop')
         x = _to_compute(x)
         qkv = F_.LinearFn.apply(x, self.qkv.weight, self.qkv.bias)
         ctx, probs = F_.AttnCoreFn.apply(qkv, self.num_heads, True)
-        return F_.LinearFn.apply(ctx, self.proj.weight, self.proj.bias), probs
+        y = F_.LinearFn.apply(ctx, self.proj.weight, self.proj.bias)
+        drop = _drop_spec(self, self.proj_drop.p)
+        if drop is not None:
+            y = F_.DropoutFn.apply(y, drop[0], drop[1], 0)
+        return y, probs
 
 
 class _DividedBase(nn.Module):
@@ -243,7 +262,6 @@ class _DividedBase(nn.Module):
 
     def _guard(self):
         if self.training:
-            _no_dropout(self.proj_drop.p, 'proj_drop')
             _no_dropout(self.attn.attn_drop.p, 'attn_drop')
 
 
@@ -276,9 +294,10 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
         p = (n1 - 1) // t
         if self.use_cls_token:                       # space-then-time order: sequences (b, p) of the cls row + T tokens
             s = None if return_attention else _drop_scale(self.layer_drop, b * p, 3, x.device)
+            drop = None if return_attention else _drop_spec(self, self.proj_drop.p)
             res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                                   self.attn.proj.weight, self.attn.proj.bias, 'time_cls', t, self.num_heads, s,
-                                  bool(return_attention), self.norm.eps, xs, exact)
+                                  bool(return_attention), self.norm.eps, xs, exact, drop)
             return res if return_attention else _with_stream(res, exact)
         if return_attention:
             _no_exact('the attention map of a temporal block')
@@ -286,10 +305,11 @@ class DividedTemporalAttentionWithPreNorm(_DividedBase):
             return F_.AttnFn.apply(tok, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                                    self.attn.proj.weight, self.attn.proj.bias, 'self', 0, self.num_heads, None, True, self.norm.eps)
         s = _drop_scale(self.layer_drop, b * p, 3, x.device)
+        drop = _drop_spec(self, self.proj_drop.p)
         return _with_stream(F_.TimeAttnFn.apply(
             x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias, self.attn.proj.weight,
             self.attn.proj.bias, self.temporal_fc.weight, self.temporal_fc.bias, t, self.num_heads, s, self.norm.eps,
-            _keep_scale(self.layer_drop) if s is not None else None, xs, exact), exact)
+            _keep_scale(self.layer_drop) if s is not None else None, xs, exact, drop), exact)
 
 
 class DividedSpatialAttentionWithPreNorm(_DividedBase):
@@ -314,9 +334,10 @@ class DividedSpatialAttentionWithPreNorm(_DividedBase):
         if (x.shape[1] - 1) % t:
             raise ValueError(f'{x.shape[1] - 1} tokens per clip are not a multiple of num_frames={t}')
         s = None if return_attention else _drop_scale(self.layer_drop, b * t, 3, x.device)
+        drop = None if return_attention else _drop_spec(self, self.proj_drop.p)
         res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                               self.attn.proj.weight, self.attn.proj.bias, 'space' if self.use_cls_token else 'space_nocls', t,
-                              self.num_heads, s, bool(return_attention), self.norm.eps, xs, exact)
+                              self.num_heads, s, bool(return_attention), self.norm.eps, xs, exact, drop)
         return res if return_attention else _with_stream(res, exact)
 
 
@@ -336,14 +357,14 @@ class MultiheadAttentionWithPreNorm(nn.Module):
     def forward(self, query, key=None, value=None, residual=None, attn_mask=None, key_padding_mask=None,
                 return_attention=False, **kwargs):
         if self.training:
-            _no_dropout(self.proj_drop.p, 'proj_drop')
             _no_dropout(self.attn.attn_drop.p, 'attn_drop')
         x, xs, exact = _stream_of(query)
         x = _to_compute(x)
         s = None if return_attention else _drop_scale(self.layer_drop, x.shape[0], 3, x.device)
+        drop = None if return_attention else _drop_spec(self, self.proj_drop.p)
         res = F_.AttnFn.apply(x, self.norm.weight, self.norm.bias, self.attn.qkv.weight, self.attn.qkv.bias,
                               self.attn.proj.weight, self.attn.proj.bias, 'self', 0, self.num_heads, s,
-                              bool(return_attention), self.norm.eps, xs, exact)
+                              bool(return_attention), self.norm.eps, xs, exact, drop)
         return res if return_attention else _with_stream(res, exact)
 
 
@@ -372,14 +393,13 @@ class FFNWithPreNorm(nn.Module):
         self.layer_drop = _build_layer_drop(layer_drop) if layer_drop else nn.Identity()
 
     def forward(self, x):
-        if self.training:
-            _no_dropout(self.dropout_p, 'dropout_p')
         x, xs, exact = _stream_of(x)
         x = _to_compute(x)
         s = _drop_scale(self.layer_drop, x.shape[0], x.ndim, x.device)
+        drop = _drop_spec(self, self.dropout_p)      # (p, seed) of the two nn.Dropout above, or None
         fc1, fc2 = self.layers[0][0], self.layers[1]
         return _with_stream(F_.FFNFn.apply(x, self.norm.weight, self.norm.bias, fc1.weight, fc1.bias, fc2.weight, fc2.bias, s,
-                                           self.norm.eps, xs, exact), exact)
+                                           self.norm.eps, xs, exact, drop), exact)
 
 
 class BasicTransformerBlock(nn.Module):

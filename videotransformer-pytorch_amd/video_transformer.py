@@ -1,5 +1,6 @@
 """Drop-in replacement for the reference ``video_transformer.py`` models
 (TimeSformer, ViViT, MaskFeat head) running on libvtx.so HIP kernels (gfx950).
+``dropout_p`` > 0 (drop_after_pos / drop_after_time) runs as vtx_dropout_rows launches in training.
 
 Same constructor arguments, methods, attributes and ``state_dict`` keys as the
 reference.  The token preparation is fused: one patch
@@ -15,7 +16,8 @@ import torch.nn as nn
 import vtx
 from vtx import functions as F_
 from vtx import ops
-from transformer import PatchEmbed, TransformerContainer, get_sine_cosine_pos_emb, stream_value, _stream_of, _with_stream
+from transformer import (PatchEmbed, TransformerContainer, get_sine_cosine_pos_emb, stream_value, _stream_of, _with_stream,
+                         _draw_seed, _no_exact)
 from weight_init import (trunc_normal_, init_from_vit_pretrain_, init_from_mae_pretrain_,
                          init_from_kinetics_pretrain_)
 from mvit import (PatchEmbeding, create_conv_patch_embed, create_multiscale_vision_transformers)  # noqa: F401
@@ -32,8 +34,7 @@ def _embed(param_or_tensor, device):
 class _VideoTransformerBase(nn.Module):
     def _setup_embeddings(self, num_patches, num_frames, embed_dims, use_learnable_pos_emb, dropout_p,
                           with_time):
-        if dropout_p:
-            raise NotImplementedError('vtx: dropout_p > 0 is not supported by the HIP path')
+        ops.dropout_params(dropout_p)                # (the range check nn.Dropout would make)
         if use_learnable_pos_emb:
             self.pos_embed = nn.Parameter(torch.zeros(1, num_patches, embed_dims))
         else:
@@ -56,9 +57,30 @@ class _VideoTransformerBase(nn.Module):
         pos = _embed(self.pos_embed, dev) if pos_embed is None or pos_embed is self.pos_embed else pos_embed
         dtype = vtx.compute_dtype()
         exact = F_.exact_stream() and dtype == torch.bfloat16
+        p = self.drop_after_pos.p if self.training else 0
+        self._embed_drop = None
+        if p:
+            return self._tokens_dropout(x, layout, time_embed, pos, dtype, p)
         out = F_.TokensFn.apply(x, proj.weight, proj.bias, self.cls_token, pos,
                                 None if time_embed is None else _embed(time_embed, dev), dtype, layout, exact)
         return _with_stream(out, exact)              # (exact: the stream starts in float32 -- TokensFn gives the first pair)
+
+    def _tokens_dropout(self, x, layout, time_embed, pos, dtype, p):
+        """dropout_p > 0 in training: the token kernel un-fused on this branch only.  TokensFn without the time embedding, then
+        drop_after_pos over every row, the cls rows included (site 0; reference video_transformer.py:212 / :474), then
+        drop_after_time behind the time embedding (site 1; :238 / :500).  One seed for the embedding forward; the fact_encoder's
+        drop_after_time (:523) sits behind the spatial encoder and takes it from ``_embed_drop``.  The reference reads the cls
+        row of drop_after_pos's output of the clip's FIRST frame (`x[:b, 0]` of the (b t) axis); here the stream has one cls row
+        per clip, masked once per site."""
+        _no_exact('embedding dropout')
+        proj = self.patch_embed.projection
+        seed = _draw_seed()
+        self._embed_drop = (float(p), seed)
+        tok = F_.TokensFn.apply(x, proj.weight, proj.bias, self.cls_token, pos, None, dtype, layout, False)
+        tok = F_.DropoutFn.apply(tok, float(p), seed, 0)
+        if time_embed is not None:
+            tok = F_.TimeDropFn.apply(tok, _embed(time_embed, x.device), float(p), seed, 1)
+        return tok
 
     def _readout(self, x):
         # under vtx.set_stream('fp32') x is a Stream: the last sub-block's contribution and the float32 stream it read; the add is
@@ -283,8 +305,12 @@ class ViViT(_VideoTransformerBase):
         literal: the cls rows are the first b rows of the flattened (b t) axis."""
         x = stream_value(x)                          # (the exact residual stream: the spatial encoder's stream as one tensor)
         D = x.shape[2]
+        drop = getattr(self, '_embed_drop', None)    # (p, seed) of this forward's prepare_tokens, or None
         if D % 8 == 0 and D <= 1024 and x.dtype == vtx.compute_dtype():
-            return F_.FactGlueFn.apply(x, _embed(self.time_embed, x.device), b)
+            h = F_.FactGlueFn.apply(x, _embed(self.time_embed, x.device), b)
+            return h if drop is None else F_.DropoutFn.apply(h, drop[0], drop[1], 1)     # drop_after_time (reference :523)
+        if drop is not None:
+            raise NotImplementedError('vtx: embedding dropout needs an embedding width that vtx_fact_glue_fwd takes')
         # widths vtx_fact_glue_fwd does not take (16-byte vectors of a row, one row per workgroup pass): the same expressions
         # as device-side ATen ops between the two encoders (round 3's form; not on any BASELINE configuration)
         x32 = F_.CastFn.apply(x, torch.float32)

@@ -237,6 +237,15 @@ RAGGED_SIGNATURES = {
     'vtx_clips_views_u8': (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
 }
 
+# libvtx_dropout.so (include/vtx_dropout.h, csrc/dropout.hip): dropout without a stored mask, the eighth library.  Must list every symbol the header declares.
+DROPOUT_LIB_PATH = os.environ.get('VTX_DROPOUT_LIB', os.path.join(_PKG, 'libvtx_dropout.so'))
+DROPOUT_SIGNATURES = {
+    'vtx_dropout_version': (ci, []),
+    'vtx_dropout_last_error_string': (C.c_char_p, []),
+    'vtx_dropout_rows': (ci, [ci, ci, ci, vp, cl, RowMap, vp, cl, RowMap, vp, cl, RowMap, vp, ci, vp, ci, ci, ci, ci,
+                              C.c_ulonglong, cf, C.c_ulonglong, C.c_uint, C.c_ulonglong, vp]),
+}
+
 _lib = None
 _aug = None
 _randaug = None
@@ -244,6 +253,7 @@ _views = None
 _mix = None
 _stem = None
 _ragged = None
+_dropout = None
 
 
 class VtxError(RuntimeError):
@@ -418,6 +428,34 @@ def ragged_call(name, *args):
     rc = getattr(lib, name)(*args)
     if rc != 0:
         msg = lib.vtx_ragged_last_error_string()
+        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+
+
+def load_dropout():
+    """Load libvtx_dropout.so and bind every symbol of include/vtx_dropout.h.  Raises if anything is missing: there is no fallback."""
+    global _dropout
+    if _dropout is not None:
+        return _dropout
+    if not os.path.isfile(DROPOUT_LIB_PATH):
+        raise VtxError(f'libvtx_dropout.so not found at {DROPOUT_LIB_PATH}: build it with '
+                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
+    lib = C.CDLL(DROPOUT_LIB_PATH)
+    for name, (res, args) in DROPOUT_SIGNATURES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VtxError(f'libvtx_dropout.so does not export {name}') from e
+        fn.restype = res
+        fn.argtypes = args
+    _dropout = lib
+    return lib
+
+
+def dropout_call(name, *args):
+    lib = load_dropout()
+    rc = getattr(lib, name)(*args)
+    if rc != 0:
+        msg = lib.vtx_dropout_last_error_string()
         raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 

@@ -411,7 +411,7 @@ class TimeAttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, tfc_w, tfc_b, T, heads, scale_vec, eps=1e-5,
-                keep_scale=None, xs=None, exact=False):
+                keep_scale=None, xs=None, exact=False, proj_drop=None):
         # exact: x is the previous sub-block's contribution d, xs the float32 stream it was computed from (None: the stream
         # starts at d); returns (this block's contribution, the float32 stream xs + d)
         x = _chk(x)
@@ -423,6 +423,8 @@ class TimeAttnFn(torch.autograd.Function):
         dtp = x.dtype
         need_t = any(ctx.needs_input_grad)
         merged = _merge_tfc and (scale_vec is None or keep_scale is not None) and proj_b is not None and tfc_b is not None
+        # proj_drop = (p, seed): a mask sits between the two Linear layers (transformer.py:265), the product weight is not valid
+        merged = merged and proj_drop is None
         xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, tm)
         if exact:
             _cls_pass_acc(x, xs, x32)
@@ -444,12 +446,17 @@ class TimeAttnFn(torch.autograd.Function):
         else:
             wp, wpT = weights(proj_w, dtp, need_t)
             a = _empty((M, D), x)
-            ops.gemm_nt(o, wp, a, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(T, 1, 1, 0))
+            if proj_drop is None:
+                ops.gemm_nt(o, wp, a, M, D, D, bias=proj_b, row_scale=scale_vec, rs=(T, 1, 1, 0))
+            else:                                    # a = drop(o Wp^T + b) * s
+                ops.gemm_nt(o, wp, a, M, D, D, bias=proj_b)
+                ops.dropout_rows(a, a, M, D, proj_drop[0], proj_drop[1], 0, s=scale_vec, rs=(T, 1, 1, 0))
             wt, wtT = weights(tfc_w, dtp, need_t)
             ops.gemm_nt(a, wt, out, M, D, D, cmap=tm, bias=tfc_b, R=res, rmap=tm)
             wts = (wqT, wpT, wtT)
         _cls_pass_out(x, out, exact)
         ctx.cfg = (T, heads, scale_vec is not None, merged, keep_scale)
+        ctx.proj_drop = proj_drop
         ctx.params = (ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, tfc_w, tfc_b)
         return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse, a), scale_vec, wts)
 
@@ -500,7 +507,11 @@ class TimeAttnFn(torch.autograd.Function):
             # temporal_fc
             d_tfc_w, d_tfc_b = _weight_grads((p_tfc_w, p_tfc_b), dout, a, M, D, D, amap=tm)
             da = _empty((M, D), x)
-            ops.gemm_nt(dout, wtT, da, M, D, D, amap=tm, row_scale=sv, rs=(T, 1, 1, 0))
+            if ctx.proj_drop is None:
+                ops.gemm_nt(dout, wtT, da, M, D, D, amap=tm, row_scale=sv, rs=(T, 1, 1, 0))
+            else:                                    # the forward's launch on the gradient: the mask is regenerated
+                ops.gemm_nt(dout, wtT, da, M, D, D, amap=tm)
+                ops.dropout_rows(da, da, M, D, ctx.proj_drop[0], ctx.proj_drop[1], 0, s=sv, rs=(T, 1, 1, 0))
             # proj
             d_proj_w, d_proj_b = _weight_grads((p_proj_w, p_proj_b), da, o, M, D, D)
             ops.gemm_nt(da, wpT, do, M, D, D)
@@ -510,7 +521,7 @@ class TimeAttnFn(torch.autograd.Function):
         d_qkv_w, d_qkv_b, dxn = _qkv_bwd((p_qkv_w, p_qkv_b), dqkv, xn, wqT, M, D)
         # LayerNorm + residual; the cls rows pass through
         dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, tm, ln_w, mean, rstd, (p_ln_w, p_ln_b), skip=_cls_rows(dout.shape))
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, d_tfc_w, d_tfc_b, None, None, None, None, None, None, None)
+        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, d_tfc_w, d_tfc_b, None, None, None, None, None, None, None, None)
 
 
 # ---------------------------------------------------------------------------------
@@ -574,7 +585,7 @@ class AttnFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, ln_w, ln_b, qkv_w, qkv_b, proj_w, proj_b, kind, T, heads, scale_vec, want_probs, eps=1e-5, xs=None,
-                exact=False):
+                exact=False, proj_drop=None):
         x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
         lay = _attn_layout(kind, x.shape, T)
         D = x.shape[-1]
@@ -595,13 +606,25 @@ class AttnFn(torch.autograd.Function):
         wp, wpT = weights(proj_w, x.dtype, need_t)
         out = torch.empty_like(x)
         a_cls = _empty((lay.ncls, D), x) if lay.ncls else None
-        ops.gemm_nt(o, wp, out, Mo, D, D, cmap=lay.omap, bias=proj_b, row_scale=scale_vec, rs=lay.rs, R=res, rmap=lay.omap,
-                    split_row=lay.tok if lay.ncls else 0, Csplit=a_cls)
+        if proj_drop is None:
+            ops.gemm_nt(o, wp, out, Mo, D, D, cmap=lay.omap, bias=proj_b, row_scale=scale_vec, rs=lay.rs, R=res, rmap=lay.omap,
+                        split_row=lay.tok if lay.ncls else 0, Csplit=a_cls)
+        else:
+            # proj_drop = (p, seed) (transformer.py:176 behind attn.proj): the GEMM writes acc + bias through the same maps, one
+            # launch then applies mask, DropPath scale and residual.  Element index = row of o: the token rows, then the split
+            # cls rows (in a_cls, m continuing at tok), which take the scale of their own sequence as the GEMM's split rows do
+            ops.gemm_nt(o, wp, out, Mo, D, D, cmap=lay.omap, bias=proj_b, split_row=lay.tok if lay.ncls else 0, Csplit=a_cls)
+            ops.dropout_rows(out, out, lay.tok, D, proj_drop[0], proj_drop[1], 0, xmap=lay.omap, ymap=lay.omap, post=res,
+                             pmap=lay.omap, s=scale_vec, rs=lay.rs)
+            if lay.ncls:
+                ops.dropout_rows(a_cls, a_cls, lay.ncls, D, proj_drop[0], proj_drop[1], 0, e0=lay.tok * D, s=scale_vec,
+                                 rs=(1, 1, 1, 0))
         if lay.cls == CLS_MEAN:
             ops.cls_mean_fwd(a_cls, res, out, lay.B, lay.groups, D, x.shape[1])
         elif lay.cls == CLS_PASS:
             _cls_pass_out(x, out, exact)
         ctx.cfg = (kind, T, heads, scale_vec is not None)
+        ctx.proj_drop = proj_drop
         ctx.params = ((ln_w, ln_b), (qkv_w, qkv_b), (proj_w, proj_b)) if lay.direct else (None, None, None)
         return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, qkv, o, lse), scale_vec, (wqT, wpT))
 
@@ -624,6 +647,12 @@ class AttnFn(torch.autograd.Function):
             da = _empty((Mo, D), x)
             prep = ops.time_cls_grad_prep if lay.mode == ATTN_TIME_CLS else ops.space_grad_prep
             prep(dout, sv if has_scale else None, da, lay.B, lay.T, lay.P, D)
+            if ctx.proj_drop is not None:            # the mask in o's row order, on the scaled rows (the factors commute)
+                ops.dropout_rows(da, da, Mo, D, ctx.proj_drop[0], ctx.proj_drop[1], 0)
+        elif ctx.proj_drop is not None:              # with a mask da is always built: mask and DropPath scale in one launch
+            da = _empty((Mo, D), x)
+            ops.dropout_rows(dout, da, Mo, D, ctx.proj_drop[0], ctx.proj_drop[1], 0, xmap=lay.omap, s=sv if has_scale else None,
+                             rs=lay.rs)
         elif has_scale:
             da = _empty((Mo, D), x)
             ops.row_scale_copy(dout, da, Mo, D, smap=lay.omap, s=sv, rs=lay.rs)
@@ -640,7 +669,7 @@ class AttnFn(torch.autograd.Function):
         d_qkv_w, d_qkv_b, dxn = _qkv_bwd(p_qkv, dqkv, xn, wqT, lay.rows, D, qmap=lay.qmap)
         dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, lay.xmap, ln_w, mean, rstd, p_ln,
                                           skip=_cls_rows(x.shape) if lay.cls == CLS_PASS else None)
-        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None, None)
+        return (dx, d_ln_w, d_ln_b, d_qkv_w, d_qkv_b, d_proj_w, d_proj_b, None, None, None, None, None, None, None, None, None)
 
 
 _compact = True
@@ -697,12 +726,14 @@ class FFNFn(torch.autograd.Function):
     """FFNWithPreNorm.forward with num_layers == 2 (reference transformer.py:516-523)."""
 
     @staticmethod
-    def forward(ctx, x, ln_w, ln_b, w1, b1, w2, b2, scale_vec, eps=1e-5, xs=None, exact=False):
+    def forward(ctx, x, ln_w, ln_b, w1, b1, w2, b2, scale_vec, eps=1e-5, xs=None, exact=False, drop=None):
         x = _chk(x)                                  # exact: the contribution d of the previous sub-block (see TimeAttnFn)
         D = x.shape[-1]
         M = x.numel() // D
         rows_per = M // x.shape[0]
         Hd = w1.shape[0]
+        if drop is not None:                         # dropout_p > 0 in training: its own path, without the DropPath compaction
+            return FFNFn._forward_drop(ctx, x, ln_w, ln_b, w1, b1, w2, b2, scale_vec, eps, xs, exact, drop)
         plan = _compaction_plan(scale_vec, x.shape[0], rows_per, x.device)
         if plan is not None:
             return FFNFn._forward_compact(ctx, x, ln_w, ln_b, w1, b1, w2, b2, eps, plan, rows_per, xs, exact)
@@ -719,6 +750,32 @@ class FFNFn(torch.autograd.Function):
         out = torch.empty_like(x)
         ops.gemm_nt(g, w2c, out, M, D, Hd, bias=b2, row_scale=scale_vec, rs=(rows_per, 1, 1, 0), R=res)
         ctx.cfg = (rows_per, scale_vec is not None, Hd)
+        ctx.params = (ln_w, ln_b, w1, b1, w2, b2)
+        return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, h, g), scale_vec, (w1T, w2T))
+
+    @staticmethod
+    def _forward_drop(ctx, x, ln_w, ln_b, w1, b1, w2, b2, scale_vec, eps, xs, exact, drop):
+        """drop = (p, seed): the two nn.Dropout of the reference's FFN (transformer.py:498-507).  Site 0 behind the GELU, in place
+        on g -- the dropped g is what fc2 and the fc2 weight gradient read; h = gelu' stays.  Site 1 behind fc2: the GEMM runs
+        without residual and row scale, one launch applies mask, DropPath scale and residual."""
+        p, seed = drop
+        D = x.shape[-1]
+        M = x.numel() // D
+        rows_per = M // x.shape[0]
+        Hd = w1.shape[0]
+        need_t = any(ctx.needs_input_grad)
+        xn, mean, rstd, x32, res = _prenorm_fwd(x, xs, exact, ln_w, ln_b, eps, M, IDENT)
+        w1c, w1T = weights(w1, x.dtype, need_t)
+        h = _empty((M, Hd), x)
+        g = _empty((M, Hd), x)
+        ops.gemm_nt(xn, w1c, g, M, Hd, D, bias=b1, act=2, C2=h)
+        ops.dropout_rows(g, g, M, Hd, p, seed, 0)
+        w2c, w2T = weights(w2, x.dtype, need_t)
+        out = torch.empty_like(x)
+        ops.gemm_nt(g, w2c, out, M, D, Hd, bias=b2)
+        ops.dropout_rows(out, out, M, D, p, seed, 1, post=res, s=scale_vec, rs=(rows_per, 1, 1, 0))
+        ctx.cfg = (rows_per, scale_vec is not None, Hd)
+        ctx.drop = drop
         ctx.params = (ln_w, ln_b, w1, b1, w2, b2)
         return _prenorm_save(ctx, out, x, x32, (ln_w, mean, rstd, xn, h, g), scale_vec, (w1T, w2T))
 
@@ -792,7 +849,7 @@ class FFNFn(torch.autograd.Function):
             d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2 = zeros
         _copy_rows_res(dout, dx, g32, dx32, nd * rows_per, D, dmap)
         _hand_on(dx, dx32)
-        return (dx, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, None, None, None, None)
+        return (dx, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, None, None, None, None, None)
 
     @staticmethod
     def backward(ctx, dout, _dstream=None):
@@ -805,7 +862,11 @@ class FFNFn(torch.autograd.Function):
         D = x.shape[-1]
         M = x.numel() // D
         x_stream, x = x, dout                          # (the saved stream may be float32: buffers take dout's dtype)
-        if has_scale:
+        drop = getattr(ctx, 'drop', None)
+        if drop is not None:                           # dz = drop_1(dout) * s, out of place: dout is never modified
+            dz = _empty((M, D), x)
+            ops.dropout_rows(dout, dz, M, D, drop[0], drop[1], 1, s=sv if has_scale else None, rs=(rows_per, 1, 1, 0))
+        elif has_scale:
             dz = _empty((M, D), x)
             ops.row_scale_copy(dout, dz, M, D, s=sv, rs=(rows_per, 1, 1, 0))
         else:
@@ -813,11 +874,13 @@ class FFNFn(torch.autograd.Function):
         d_w2, d_b2 = _weight_grads((p_w2, p_b2), dz, g, M, D, Hd)
         dh = _empty((M, Hd), x)
         ops.gemm_nt(dz, w2T, dh, M, Hd, D, dgelu_in=h, dgelu_kind=1)
+        if drop is not None:                           # site 0's mask behind the dgelu epilogue: the two factors commute
+            ops.dropout_rows(dh, dh, M, Hd, drop[0], drop[1], 0)
         d_w1, d_b1 = _weight_grads((p_w1, p_b1), dh, xn, M, Hd, D)
         dxn = _empty((M, D), x)
         ops.gemm_nt(dh, w1T, dxn, M, D, Hd)
         dx, d_ln_w, d_ln_b = _prenorm_bwd(dout, dxn, x_stream, IDENT, ln_w, mean, rstd, (p_ln_w, p_ln_b))
-        return (dx, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, None, None, None, None)
+        return (dx, d_ln_w, d_ln_b, d_w1, d_b1, d_w2, d_b2, None, None, None, None, None)
 
 
 class TokensFn(torch.autograd.Function):
@@ -1155,6 +1218,67 @@ class AttnCoreFn(torch.autograd.Function):
         dqkv = torch.empty_like(qkv)
         ops.attn_bwd(qkv, o, lse, do, dqkv, ATTN_CONTIG, Bn, L, heads, hd, hd ** -0.5)
         return dqkv, None, None
+
+
+class DropoutFn(torch.autograd.Function):
+    """nn.Dropout on a contiguous [.., D] tensor without a stored mask: the mask is a function of (seed, site, element index, p)
+    (include/vtx_dropout.h, vtx_dropout_rows) and the backward is the same launch on dy."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, site):
+        x = _chk(x)
+        D = x.shape[-1]
+        y = torch.empty_like(x)
+        ops.dropout_rows(x, y, x.numel() // D, D, p, seed, site)
+        ctx.cfg = (p, seed, site)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, site = ctx.cfg
+        dy = _chk(dy)
+        D = dy.shape[-1]
+        dx = torch.empty_like(dy)
+        ops.dropout_rows(dy, dx, dy.numel() // D, D, p, seed, site)
+        return dx, None, None, None
+
+
+class TimeDropFn(torch.autograd.Function):
+    """drop_after_time of prepare_tokens on the 'pt' stream x [B, 1 + P*T, D] (reference video_transformer.py:212-238 /
+    :474-500): y = drop(x + time_embed[t]) on the token rows (logical row m = b P T + p T + t, so the table's period is T) and
+    y = drop(x) on the cls rows, whose element indices continue behind the tokens'.  d_time_embed is the sum of the masked
+    gradient over (b, p), formed as TokensFn.backward forms it."""
+
+    @staticmethod
+    def forward(ctx, x, time_embed, p, seed, site):
+        x = _chk(x)
+        B, N1, D = x.shape
+        N = N1 - 1
+        T = time_embed.shape[-2]
+        if N % T:
+            raise ValueError(f'clip has {N} tokens, no multiple of the {T} frames time_embed holds')
+        y = torch.empty_like(x)
+        tm, cm = ops.tokmap(N), ops.clsmap(N)
+        ops.dropout_rows(x, y, B * N, D, p, seed, site, xmap=tm, ymap=tm, pre=time_embed.detach().reshape(T, D), pre_period=T)
+        ops.dropout_rows(x, y, B, D, p, seed, site, e0=B * N * D, xmap=cm, ymap=cm)
+        ctx.cfg = (p, seed, site, T, time_embed.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, site, T, e_shape = ctx.cfg
+        dy = _chk(dy)
+        B, N1, D = dy.shape
+        N = N1 - 1
+        dx = torch.empty_like(dy)
+        tm, cm = ops.tokmap(N), ops.clsmap(N)
+        ops.dropout_rows(dy, dx, B * N, D, p, seed, site, xmap=tm, ymap=tm)
+        ops.dropout_rows(dy, dx, B, D, p, seed, site, e0=B * N * D, xmap=cm, ymap=cm)
+        d_time = None
+        if ctx.needs_input_grad[1]:
+            dE = ops.reduce_rows(dx, N, B, D, D, 1, 1 + N, 1)                    # dE[n] = sum over clips of dx[b, 1 + n]
+            d_time = ops.reduce_rows(dE, T, N // T, D, D, 0, T, 1).reshape(e_shape)
+        return dx, d_time, None, None, None
 
 
 class RowScaleFn(torch.autograd.Function):

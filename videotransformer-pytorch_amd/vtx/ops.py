@@ -397,6 +397,39 @@ def row_scale_copy(src, dst, rows, D, lds=None, smap=IDENT, ldd=None, dmap=IDENT
          D if ldd is None else ldd, dmap, ptr(s), int(rs[0]), int(rs[1]), int(rs[2]), int(rs[3]), stream())
 
 
+# ---- dropout without a stored mask (libvtx_dropout.so: include/vtx_dropout.h, vtx_dropout_rows) ----
+# csrc/dropout.hip caps its grid at DROPOUT_GRID_CAP workgroups of DROPOUT_BLOCK threads, 8 elements each: a launch of more
+# than DROPOUT_TRIP elements strides (the tests cross the cap by these numbers).
+DROPOUT_GRID_CAP, DROPOUT_BLOCK = 4096, 256
+DROPOUT_TRIP = DROPOUT_GRID_CAP * DROPOUT_BLOCK * 8
+
+
+def dropout_params(p):
+    """(thr, scale) of a dropout probability: an element is dropped iff its 32-bit Philox word < thr = floor(p * 2^32) (Python
+    integers), a kept one is multiplied by scale = float32(1) / float32(1 - p) -- transformer._keep_scale's arithmetic; 0 for p == 1."""
+    import fractions
+    import numpy as np
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f'dropout probability has to be between 0 and 1, but got {p}')
+    thr = int(fractions.Fraction(p) * (1 << 32))          # floor of the exact product: p is a binary fraction
+    scale = 0.0 if p == 1.0 else float(np.float32(1.0) / np.float32(1 - p))
+    return thr, scale
+
+
+def dropout_rows(x, y, rows, D, p, seed, site, e0=0, ldx=None, xmap=IDENT, ldy=None, ymap=IDENT, post=None, ldp=None, pmap=IDENT,
+                 pre=None, pre_period=0, s=None, rs=(1, 0, 1, 0)):
+    """y[ymap(m)] = post[pmap(m)] + s(m) * dropout(x[xmap(m)] + pre[m % pre_period]); the mask of element (m, c) is a function
+    of (seed, site, e0 + m * D + c, p) alone.  y may be x (same maps)."""
+    need_cuda(x, y, post, pre, s)
+    thr, scale = dropout_params(p)
+    if post is not None and post.dtype != x.dtype:
+        raise TypeError('dropout_rows: the residual must have the dtype of x')
+    _lib.dropout_call('vtx_dropout_rows', dt(x), int(rows), int(D), ptr(x), D if ldx is None else ldx, xmap, ptr(y), D if ldy is None else ldy,
+         ymap, ptr(post), D if ldp is None else ldp, pmap, ptr(_f32(pre)), int(pre_period), ptr(_f32(s)), int(rs[0]), int(rs[1]),
+         int(rs[2]), int(rs[3]), thr, scale, int(seed), int(site), int(e0), stream())
+
+
 def dropped_rows_fix(s, M, D, group_rows, x=None, xmap=IDENT, bias=None, out=None, omap=IDENT, zero=None, ldx=None, ldo=None):
     """Rows of the groups with s == 0: out[omap(m)] = x[xmap(m)] + bias; zero[m] = 0 (either part optional)."""
     ref = out if out is not None else zero
