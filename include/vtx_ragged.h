@@ -44,7 +44,7 @@ const char* vtx_ragged_last_error_string(void);
  * [B,Wr_max] and x_weights [B,Wr_max,x_taps], row b valid for x < Wr_b (what lies behind is never read); y_first / y_count
  * [B,H] and y_weights [B,H,y_taps].  x_taps / y_taps: the widest window of any clip.
  *
- * Arithmetic: vtx_clip_views_u8's, statement for statement (x pass, then y pass, taps in ascending order, float32 without
+ * Arithmetic: vtx_clip_views_u8's, the same device code (x pass, then y pass, taps in ascending order, float32 without
  * contraction, clamp to [0, 255], round half-to-even): clip b's views are byte for byte that call on clip b alone with its
  * rows of the tables.  With V = 1, left = 0 and Wr_b = W it is vtx_clip_resample_u8 on the gathered frames.
  *

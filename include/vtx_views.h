@@ -39,7 +39,7 @@ const char* vtx_views_last_error_string(void);
  * no view is not computed.  Tables as vtx_clip_resample_u8's (vtx_resample_build_table of libvtx_aug.so), per clip:
  * x_first / x_count [B,Wr] int32 and x_weights [B,Wr,x_taps] float32 for ALL Wr columns of the resized frame; y_first /
  * y_count [B,H] and y_weights [B,H,y_taps] for the H output rows (the caller cuts the resized frame's table to the crop
- * window).  Arithmetic: vtx_clip_resample_u8's, operation for operation (x pass, then y pass, float32 without
+ * window).  Arithmetic: vtx_clip_resample_u8's, the same device code (x pass, then y pass, float32 without
  * contraction), so each view equals that call on the gathered frames, sliced.  Only the first count taps of an output are
  * read; frame indices, lefts and tap windows are clamped into range on the device whatever the arrays say (validate them
  * on the host).  No alignment requirement. */

@@ -4,6 +4,8 @@ Two independent expectations for the resampler:
   * ``torch_resized_crop``: what torchvision's resized_crop (+ hflip) computes on a tensor -- crop, torch.nn.functional.interpolate
     (align_corners=False) of the float image, clamp, round, uint8 -- in plain torch;
   * ``table_eval``: a float64 evaluation  Wy . img . Wx^T  of the tables the library builds (vtx_resample_build_table).
+A third, ``resample_f32``, restates the kernels' own float32 operation order and their clamp of the tap windows: the exact
+bytes for any table, ``edge_table``'s bent ones included.
 And ``jitter_ref``: torchvision's ColorJitter arithmetic (brightness / contrast / saturation blends) on a uint8 [T,H,W,3] clip.
 """
 import numpy as np
@@ -51,6 +53,63 @@ def near_tie(v64):
     """Where rint(clip(v64)) is decided by less than TIE."""
     v = np.clip(v64, 0.0, 255.0)
     return np.abs(np.abs(v - np.floor(v)) - 0.5) < TIE
+
+
+def kernel_windows(table, src_len):
+    """The tap windows as the kernels read them (clamp_taps, csrc/resample_band.h): count into 0 .. taps, first into 0 .. src_len,
+    and a window that still runs past the source edge moved back to end at it -> (first [n], count [n])."""
+    first, count, weights = (np.asarray(a) for a in table)
+    c = np.clip(count.astype(np.int64), 0, weights.shape[1])
+    f = np.clip(first.astype(np.int64), 0, src_len)
+    over = f + c > src_len
+    return np.where(over, np.maximum(src_len - c, 0), f), np.where(over, np.minimum(c, src_len), c)
+
+
+def _pass_f32(img, table, axis):
+    """out[o] = sum_k w[o, k] * img[first[o] + k] along ``axis``: taps in ascending order, every product and every sum rounded
+    to float32 on its own (NumPy float32 arithmetic: no contraction).  Weights behind a count are not read."""
+    img = np.moveaxis(img, axis, 0)
+    f, c = kernel_windows(table, img.shape[0])
+    w = np.asarray(table[2], dtype=np.float32)
+    col = (-1,) + (1,) * (img.ndim - 1)
+    out = np.zeros((len(f),) + img.shape[1:], dtype=np.float32)
+    for k in range(int(c.max())):
+        on = k < c
+        wk = np.where(on, w[:, k], np.float32(0)).astype(np.float32)
+        term = wk.reshape(col) * img[np.minimum(f + k, img.shape[0] - 1)]
+        out = np.where(on.reshape(col), out + term, out)
+    assert out.dtype == np.float32
+    return np.moveaxis(out, 0, axis)
+
+
+def resample_f32(frames_u8, ytab, xtab):
+    """frames uint8 [...,Hs,Ws,3] -> uint8 [...,H,W,3]: the kernels' arithmetic restated operation for operation -- x pass, then
+    y pass, float32, clamp to [0, 255], round half to even -- with their clamp of the tap windows.  Byte for byte."""
+    img = np.asarray(frames_u8).astype(np.float32)
+    out = _pass_f32(_pass_f32(img, xtab, -2), ytab, -3)
+    return np.rint(np.clip(out, np.float32(0), np.float32(255))).astype(np.uint8)
+
+
+def edge_table(src_len, out_len, mode='bicubic', antialias=True, max_taps=None, shift=0):
+    """A table of vtx_resample_build_table (one spare weight column, NaN behind every count) bent at six outputs (out_len >= 13;
+    ``shift`` 0 or 1 moves them by one) so that what the kernels do beyond a well-formed table shows:
+      a window that starts right behind the last source sample, one that starts further behind, a negative first: the clamp acts;
+      a count above the taps of the table (cut to them; that row's weights are all finite);
+      a count of 0: the output row or column is 0 whatever the source holds."""
+    from vtx import ops
+    taps = max_taps or ops.resample_max_taps(src_len, out_len, mode, antialias) + 1
+    f, c, w = ops.resample_table(src_len, 0, src_len, out_len, mode, antialias, max_taps=taps)
+    assert out_len >= 13 and c.min() >= 1 and c.max() < taps
+    for o in range(out_len):
+        w[o, c[o]:] = np.nan
+    f[1 + shift] = src_len
+    f[4 + shift] = -3
+    c[6 + shift] = 0
+    w[8 + shift] = np.float32(1.0 / taps)
+    c[8 + shift] = taps + 4
+    f[out_len - 1 - shift] = src_len + 5
+    assert (f + c > src_len).sum() >= 2 and (f < 0).any() and (c == 0).any() and (c > taps).any()
+    return f, c, w
 
 
 def torch_resize_float(frames_u8, box, out_hw, mode, antialias):

@@ -68,6 +68,34 @@ def test_resample_other_shapes(mode, antialias):
     _check_resample(src, [(1, 2, 10, 297)], [True], (10, 270), mode, antialias)
 
 
+def _stacked(tabs):
+    return tuple(torch.from_numpy(np.stack([t[i] for t in tabs])).to(DEV) for i in range(3))
+
+
+def test_resample_edges_of_the_band_byte_for_byte():
+    """40x300 -> 13x260, bicubic with antialias, tables bent per clip (aug_ref.edge_table): the last band holds 5 rows, the second
+    column tile 4 live lanes (two of them with bent windows), the y windows hold up to 15 taps -- longer than a band --, windows
+    run past the source edge or start in front of it, counts exceed the table's taps, and a row and a column of count 0 come
+    out 0.  Against the float32 restatement of the kernel's operation order (aug_ref.resample_f32): every byte equal."""
+    from vtx import ops
+    B, T, (Hs, Ws), (H, W) = 2, 2, (40, 300), (13, 260)
+    src = R.source_clip(B, T, (Hs, Ws), seed=8)
+    ytabs, xtabs = [R.edge_table(Hs, H, shift=b) for b in range(B)], [R.edge_table(Ws, W, shift=b) for b in range(B)]
+    assert ytabs[0][2].shape[1] == 16 and max(int(R.kernel_windows(t, Hs)[1].max()) for t in ytabs) > 8
+    got = ops.clip_resample_u8(src.to(DEV), (H, W), _stacked(xtabs), _stacked(ytabs))
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    want = np.stack([R.resample_f32(src[b].numpy(), ytabs[b], xtabs[b]) for b in range(B)])
+    assert np.array_equal(got, want), f'{int((got != want).sum())} bytes differ'
+    for b in range(B):
+        assert not got[b, :, 6 + b].any() and not got[b, :, :, 6 + b].any() and got[b, 1, 5].any()
+    # on well-formed tables the restatement is the float64 evaluation up to rounding ties: it is a reference, not a copy
+    plain = [ops.resample_table(n, 0, n, m, 'bicubic', True) for n, m in ((Hs, H), (Ws, W))]
+    v64 = R.table_eval(src[1].numpy(), *plain)
+    diff = np.abs(R.resample_f32(src[1].numpy(), *plain).astype(np.float64) - np.rint(np.clip(v64, 0.0, 255.0)))
+    assert np.all((diff == 0) | (R.near_tie(v64) & (diff <= 1)))
+
+
 def _jit_records(recs):
     jo = np.zeros((len(recs), 4), dtype=np.int32)
     jf = np.zeros((len(recs), 6), dtype=np.float32)

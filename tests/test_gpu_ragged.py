@@ -184,6 +184,35 @@ def test_binding_with_host_and_device_indices_and_out():
         assert torch.equal(got[b, 0], ops.clip_resample_u8(c[None], (24, 24), tuple(a[b:b + 1] for a in xt), tuple(a[b:b + 1] for a in yt))[0])
 
 
+def test_ragged_edges_of_the_band_byte_for_byte():
+    """Two clips of different Ts / Hs / Ws / Wr in one launch -- 3 x 40x300 -> rows of 772 columns, 4 x 19x23 -> rows of 61 -- 13
+    output rows (the last band holds 5), views of 60 columns, bicubic with antialias (clip 0: y windows of up to 15 taps), tables
+    bent per clip (aug_ref.edge_table) and poisoned behind clip 1's 61 columns.  Clip 0: columns 30 .. 59 in two views, the tile
+    256 .. 511 in none, 4 live lanes in the last tile; clip 1: every tile but the first is dead.  Against the float32
+    restatement of the kernel (aug_ref.resample_f32) clip by clip, sliced: every byte equal."""
+    from vtx import ops
+    shapes, widths, H, W = [(3, 40, 300), (4, 19, 23)], [772, 61], 13, 60
+    frames, lefts = [[1, 2], [2, 1]], [[0, 30, 712], [0, 1, 1]]
+    clips = [R.source_clip(1, Ts, (Hs, Ws), seed=SEED + 7 + b)[0] for b, (Ts, Hs, Ws) in enumerate(shapes)]
+    ytabs = [R.edge_table(Hs, H, max_taps=16, shift=b) for b, (_, Hs, _) in enumerate(shapes)]
+    xtabs = [R.edge_table(Ws, widths[b], max_taps=6, shift=b) for b, (_, _, Ws) in enumerate(shapes)]
+    assert int(R.kernel_windows(ytabs[0], 40)[1].max()) > 8
+    xf, xc, xw = np.full((2, 772), 10 ** 6, np.int32), np.full((2, 772), 2, np.int32), np.full((2, 772, 6), np.nan, np.float32)
+    for b, t in enumerate(xtabs):
+        xf[b, :widths[b]], xc[b, :widths[b]], xw[b, :widths[b]] = t
+    xdev = tuple(torch.from_numpy(a).to(DEV) for a in (xf, xc, xw))
+    ydev = tuple(torch.from_numpy(np.stack([t[i] for t in ytabs])).to(DEV) for i in range(3))
+    got = ops.clips_views_u8([c.to(DEV) for c in clips], frames, lefts, W, xdev, ydev, widths=widths)
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    assert got.shape == (2, 3, 2, H, W, 3)
+    for b, c in enumerate(clips):
+        whole = R.resample_f32(c[frames[b]].numpy(), ytabs[b], xtabs[b])
+        want = np.stack([whole[:, :, l:l + W] for l in lefts[b]])
+        assert np.array_equal(got[b], want), f'clip {b}: {int((got[b] != want).sum())} bytes differ'
+        assert not got[b, :, :, 6 + b].any() and not got[b, 0, :, :, 6 + b].any() and got[b, 2, 0, 5].any()
+
+
 def test_bad_lists_raise_before_any_launch_and_a_valid_call_still_works():
     from vtx import aug, ops
     clips = list(_clips())

@@ -93,6 +93,29 @@ def test_views_equal_the_resampler_on_the_gathered_frames(name, mode, antialias)
     assert torch.equal(again.cpu(), got)
 
 
+def test_views_edges_of_the_band_byte_for_byte():
+    """40x300 -> 13 rows x 772 columns (bicubic, antialias: y windows of up to 15 taps), views of 60 columns from 0, 30 and 712,
+    tables bent per clip (aug_ref.edge_table): columns 30 .. 59 lie in two views, the column tile 256 .. 511 in none, the last
+    tile has 4 live lanes, the last band 5 rows; windows past the source edge, counts above the taps and of 0.  Against the
+    float32 restatement of the kernel (aug_ref.resample_f32) on the gathered frames, sliced: every byte equal."""
+    from vtx import ops
+    B, Ts, (Hs, Ws), (H, Wr), W = 2, 3, (40, 300), (13, 772), 60
+    frames, lefts = [[1, 0], [0, 2]], [[0, 30, 712]] * B
+    src = R.source_clip(B, Ts, (Hs, Ws), seed=SEED)
+    ytabs, xtabs = [R.edge_table(Hs, H, shift=b) for b in range(B)], [R.edge_table(Ws, Wr, shift=b) for b in range(B)]
+    assert max(int(R.kernel_windows(t, Hs)[1].max()) for t in ytabs) > 8
+    dev = lambda tabs: tuple(torch.from_numpy(np.stack([t[i] for t in tabs])).to(DEV) for i in range(3))
+    got = ops.clip_views_u8(src.to(DEV), frames, lefts, W, dev(xtabs), dev(ytabs))
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    whole = [R.resample_f32(src[b, frames[b]].numpy(), ytabs[b], xtabs[b]) for b in range(B)]
+    want = np.stack([np.stack([whole[b][:, :, l:l + W] for l in lefts[b]]) for b in range(B)])
+    assert got.shape == (B, 3, 2, H, W, 3) and np.array_equal(got, want), f'{int((got != want).sum())} bytes differ'
+    assert np.array_equal(got[:, 0, :, :, 30:], got[:, 1, :, :, :30])                      # the columns that two views hold
+    for b in range(B):
+        assert not got[b, :, :, 6 + b].any() and not got[b, 0, :, :, 6 + b].any() and got[b, 2, 0, 5].any()
+
+
 @pytest.mark.parametrize('mode,antialias', R.MODES)
 def test_one_view_of_every_frame_is_the_plain_call(mode, antialias):
     """V = 1, frames=None, the window = the whole row: vtx_clip_resample_u8 itself."""

@@ -203,7 +203,8 @@ def views_main(a):
              f'{torch.cuda.get_device_name(0)}',
              f'{a.rounds} rounds of {a.iters} calls per path, the two paths in alternating rounds of one run, after {a.warmup} warm-up calls each, HIP events; '
              f'{k} source sets in rotation (together larger than the 256 MiB Infinity Cache)',
-             'bytes = what each path has to move, whole source frames counted (the rows outside the crop window are never read by either)',
+             'bytes = what each path has to move, whole source frames counted (the rows outside the crop window are never read by either); '
+             'spread = (max - min) / median over the rounds',
              '']
     shapes = [tuple(a.src)] + ([(240, 320)] if tuple(a.src) == (256, 340) else [])
     for Hs, Ws in shapes:
@@ -248,8 +249,8 @@ def views_main(a):
                      f'columns in a view, {3 * S} stored; source set {srcs[0].numel() / 2**20:.0f} MiB; same bytes from both paths: {same}')
 
         def row(name, us, nbytes, what):
-            med, lo = statistics.median(us), min(us)
-            lines.append(f'{name:<34} median {med:8.1f} us  min {lo:8.1f} us  {nbytes / 1e6:7.1f} MB ({what})  {nbytes / med / 1e6:5.2f} TB/s '
+            med, lo, hi = statistics.median(us), min(us), max(us)
+            lines.append(f'{name:<34} median {med:8.1f} us  min {lo:8.1f}  max {hi:8.1f}  spread {100 * (hi - lo) / med:4.1f} %  {nbytes / 1e6:7.1f} MB ({what})  {nbytes / med / 1e6:5.2f} TB/s '
                          f'= {nbytes / (med * 1e-6) / HBM:5.3f} of 8 TB/s')
             return med
         m_new = row('vtx_clip_views_u8', new, new_bytes, 'selected frames read, three views written')
@@ -671,12 +672,12 @@ def main():
     jit_bytes = frames * S * S * 3 * 3
     lines = [f'clip augmentation, {B} clips x {T} frames, {Hs}x{Ws} -> {S}x{S}, bicubic, antialias off; {torch.cuda.get_device_name(0)}',
              f'{a.rounds} rounds of {a.iters} launches after {a.warmup} warm-up launches, HIP events; {a.sets} source sets of '
-             f'{srcs[0].numel() / 2**20:.0f} MiB in rotation',
+             f'{srcs[0].numel() / 2**20:.0f} MiB in rotation; spread = (max - min) / median over the rounds',
              '']
 
     def row(name, us, nbytes, note=''):
-        med, lo = statistics.median(us), min(us)
-        lines.append(f'{name:<22} median {med:8.1f} us  min {lo:8.1f} us  {nbytes / 1e6:7.1f} MB  {nbytes / med / 1e6:6.2f} TB/s '
+        med, lo, hi = statistics.median(us), min(us), max(us)
+        lines.append(f'{name:<22} median {med:8.1f} us  min {lo:8.1f}  max {hi:8.1f}  spread {100 * (hi - lo) / med:4.1f} %  {nbytes / 1e6:7.1f} MB  {nbytes / med / 1e6:6.2f} TB/s '
                      f'= {nbytes / (med * 1e-6) / HBM:5.3f} of 8 TB/s{note}')
         return med
     m1 = row('vtx_clip_resample_u8', res, res_bytes, f'  (whole source frames; the crop boxes alone: {(crop + frames * S * S * 3) / 1e6:.1f} MB)')

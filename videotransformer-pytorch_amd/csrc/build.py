@@ -1,16 +1,12 @@
-"""Build libvtx.so, libvtx_aug.so, libvtx_randaug.so, libvtx_views.so, libvtx_mix.so, libvtx_stem.so, libvtx_ragged.so and libvtx_dropout.so (gfx950) with hipcc -- no torch headers, no cmake.
+"""Build libvtx.so and the side libraries libvtx_<name>.so of SIDE (gfx950) with hipcc -- no torch headers, no cmake.
 
     python videotransformer-pytorch_amd/csrc/build.py [--force]
 
-Each .hip file is compiled to an object (skipped when up to date) and linked into
-videotransformer-pytorch_amd/libvtx.so; csrc/aug.hip (clip augmentation, include/vtx_aug.h) becomes
-videotransformer-pytorch_amd/libvtx_aug.so and csrc/randaug.hip (RandAugment, include/vtx_randaug.h)
-videotransformer-pytorch_amd/libvtx_randaug.so, csrc/views.hip (test-time views, include/vtx_views.h)
-videotransformer-pytorch_amd/libvtx_views.so and csrc/mix.hip (Mixup / CutMix on uint8 clips, include/vtx_mix.h)
-videotransformer-pytorch_amd/libvtx_mix.so, csrc/stem.hip (MaskFeat from uint8 clips: the Conv3d stem gather and the HOG of
-selected frames, include/vtx_stem.h) videotransformer-pytorch_amd/libvtx_stem.so, csrc/ragged.hip (views of clips that differ in
-source size, include/vtx_ragged.h) videotransformer-pytorch_amd/libvtx_ragged.so, csrc/dropout.hip (dropout without a stored
-mask, include/vtx_dropout.h) videotransformer-pytorch_amd/libvtx_dropout.so.  hipcc cross-compiles without a GPU.
+Each .hip file is compiled to an object (skipped when up to date).  LIBRARIES lists what is linked from which objects:
+SOURCES become videotransformer-pytorch_amd/libvtx.so (include/vtx.h), and every side library is one source file,
+csrc/<name>.hip, with its header include/vtx_<name>.h (the file headers say what each holds).  Nothing of a side library
+is linked into libvtx.so or into another side library; what they share is header text (side_lib.h, resample_band.h,
+hog_kernel.h).  hipcc cross-compiles without a GPU.
 """
 import os
 import subprocess
@@ -20,13 +16,6 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.dirname(HERE)
 OUT = os.path.join(PKG, 'libvtx.so')
-AUG_OUT = os.path.join(PKG, 'libvtx_aug.so')
-RANDAUG_OUT = os.path.join(PKG, 'libvtx_randaug.so')
-VIEWS_OUT = os.path.join(PKG, 'libvtx_views.so')
-MIX_OUT = os.path.join(PKG, 'libvtx_mix.so')
-STEM_OUT = os.path.join(PKG, 'libvtx_stem.so')
-RAGGED_OUT = os.path.join(PKG, 'libvtx_ragged.so')
-DROPOUT_OUT = os.path.join(PKG, 'libvtx_dropout.so')
 OBJ = os.path.join(HERE, '_obj')
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_mfma.hip', 'attn_long.hip', 'attn_f32.hip', 'elementwise.hip', 'hog.hip', 'optim.hip', 'head.hip', 'mvit.hip', 'wprod.hip', 'xattn_mfma.hip']
@@ -35,13 +24,15 @@ SOURCES = ['api.hip', 'ln.hip', 'gemm_nt.hip', 'gemm_tn.hip', 'attn.hip', 'attn_
 # two it replaces (MI355X_MICROARCH.md): step 128.24 -> 127.84 ms over three interleaved A/B rounds.  NOT adopted: without the packing
 # the compiler fuses other multiply-add pairs, every bf16 result moves inside its rounding noise, and the noisiest statistic of the
 # suite -- the 24-layer default-stream maximum -- landed on the wrong side of its bar.  `build.py --variant noslp -fno-slp-vectorize`.)
-AUG_SOURCES = ['aug.hip']          # the second library: nothing of it is linked into libvtx.so
-RANDAUG_SOURCES = ['randaug.hip']  # the third: libvtx_aug.so keeps its seven symbols
-VIEWS_SOURCES = ['views.hip']      # the fourth: frame selection + resize + ThreeCrop in one launch
-MIX_SOURCES = ['mix.hip']          # the fifth: CutMix on bytes, Mixup inside the patch gather
-STEM_SOURCES = ['stem.hip']        # the sixth: the MViT stem gather from bytes, HOG of selected frames (hog_kernel.h, shared with hog.hip)
-RAGGED_SOURCES = ['ragged.hip']    # the seventh: views.hip's kernel with per-clip base pointer and geometry
-DROPOUT_SOURCES = ['dropout.hip']  # the eighth: mask, DropPath scale and residual in one launch, the mask regenerated in the backward
+
+# the side libraries, in the order they arrived: libvtx_<name>.so from <name>.hip alone
+SIDE = ['aug',        # clip augmentation: crop-resize + flip, colour jitter
+        'randaug',    # RandAugment
+        'views',      # test-time views: frame selection + resize + ThreeCrop in one launch
+        'mix',        # CutMix on bytes, Mixup inside the patch gather
+        'stem',       # the MViT stem gather from bytes, HOG of selected frames (hog_kernel.h, shared with hog.hip)
+        'ragged',     # views of clips that differ in source size
+        'dropout']    # mask, DropPath scale and residual in one launch, the mask regenerated in the backward
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result', '-Wno-unused-value', '-Wno-inline-asm',
          '-Wno-cuda-compat']
 EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contraction
@@ -52,18 +43,14 @@ EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contr
          'stem.hip': ['-ffp-contract=off'],        # hog_kernel.h as hog.hip compiles it; normalise: three roundings per tap
          'ragged.hip': ['-ffp-contract=off'],      # views.hip's weighted sums, byte for byte
          'dropout.hip': ['-ffp-contract=off']}     # mask, scale, row scale, residual: four float32 operations, one rounding on the store
+# (output, sources, link flags).  -Bsymbolic: a side library's own definitions of the helpers common.h declares, whatever else
+# the process has loaded
+LIBRARIES = [(OUT, SOURCES, [])] + [(os.path.join(PKG, f'libvtx_{n}.so'), [n + '.hip'], ['-Wl,-Bsymbolic']) for n in SIDE]
 
 
 def _deps():
-    hdrs = [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith('.h')]
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_aug.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_randaug.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_views.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_mix.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_stem.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_ragged.h'))
-    hdrs.append(os.path.join(PKG, '..', 'include', 'vtx_dropout.h'))
+    inc = os.path.join(PKG, '..', 'include')
+    hdrs = [os.path.join(d, f) for d in (HERE, inc) for f in os.listdir(d) if f.endswith('.h')]
     hdrs.append(os.path.abspath(__file__))                       # the flags live here
     return max(os.path.getmtime(h) for h in hdrs)
 
@@ -133,24 +120,11 @@ def _link(out, res, extra, verbose):
 
 
 def _build_locked(force, verbose):
-    every = SOURCES + AUG_SOURCES + RANDAUG_SOURCES + VIEWS_SOURCES + MIX_SOURCES + STEM_SOURCES + RAGGED_SOURCES + DROPOUT_SOURCES
+    every = [src for _, sources, _ in LIBRARIES for src in sources]
     with ThreadPoolExecutor(max_workers=min(8, len(every))) as ex:
-        res = list(ex.map(lambda s: _compile(s, force), every))
-    n, m = len(SOURCES), len(SOURCES) + len(AUG_SOURCES)
-    k = m + len(RANDAUG_SOURCES)
-    j = k + len(VIEWS_SOURCES)
-    i = j + len(MIX_SOURCES)
-    h = i + len(STEM_SOURCES)
-    g = h + len(RAGGED_SOURCES)
-    _link(OUT, res[:n], [], verbose)
-    # -Bsymbolic: the library's own definitions of the helpers common.h declares, whatever else the process has loaded
-    _link(AUG_OUT, res[n:m], ['-Wl,-Bsymbolic'], verbose)
-    _link(RANDAUG_OUT, res[m:k], ['-Wl,-Bsymbolic'], verbose)
-    _link(VIEWS_OUT, res[k:j], ['-Wl,-Bsymbolic'], verbose)
-    _link(MIX_OUT, res[j:i], ['-Wl,-Bsymbolic'], verbose)
-    _link(STEM_OUT, res[i:h], ['-Wl,-Bsymbolic'], verbose)
-    _link(RAGGED_OUT, res[h:g], ['-Wl,-Bsymbolic'], verbose)
-    _link(DROPOUT_OUT, res[g:], ['-Wl,-Bsymbolic'], verbose)
+        res = dict(zip(every, ex.map(lambda s: _compile(s, force), every)))
+    for out, sources, flags in LIBRARIES:
+        _link(out, [res[src] for src in sources], flags, verbose)
     return OUT
 
 

@@ -5,31 +5,14 @@
 // operand; the kernel streams every byte once.
 //
 // A library of its own, libvtx_dropout.so (include/vtx_dropout.h): the other seven keep their export lists and versions.
-// The error plumbing common.h declares is defined here for this library (the link is -Bsymbolic).
-#include <stdarg.h>
-#include "common.h"
+// Error plumbing, version and last-error exports: VTX_SIDE_LIB(dropout) (side_lib.h).
+#include "side_lib.h"
 #include "philox.h"
 #include "../../include/vtx_dropout.h"
 
+VTX_SIDE_LIB(dropout)
+
 namespace vtx {
-
-static thread_local char g_dropout_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_dropout_err, sizeof(g_dropout_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return VTX_ELAUNCH;
-  }
-  return VTX_OK;
-}
 
 // Grid-stride with a capped grid: at most DROPOUT_GRID_CAP workgroups of 256 threads, i.e. launches of more than
 // DROPOUT_GRID_CAP * 256 * 8 = 8 388 608 elements take a second trip (vtx/ops.py mirrors the two numbers for the tests).
@@ -88,9 +71,6 @@ __global__ __launch_bounds__(DROPOUT_BLOCK) void dropout_rows_kernel(
 }  // namespace vtx
 
 using namespace vtx;
-
-extern "C" int vtx_dropout_version(void) { return 100; }  // 0.1.0
-extern "C" const char* vtx_dropout_last_error_string(void) { return g_dropout_err; }
 
 extern "C" int vtx_dropout_rows(int dtype, int rows, int D, const void* x, long ldx, vtx_rowmap xmap, void* y, long ldy,
                                 vtx_rowmap ymap, const void* post, long ldp, vtx_rowmap pmap, const float* pre, int pre_period,

@@ -18,32 +18,15 @@
 // byte is read once and normalised once: 1 byte read and 2 written (bf16) per sample, as vtx_patch_rows_u8.  The route it
 // replaces (normalise to a float clip, mix it in place, gather) moves 4 + 8 + 6 = 19 bytes per sample with the byte read.
 //
-// A library of its own, libvtx_mix.so (include/vtx_mix.h): the other four keep their export lists and versions.  The
-// error plumbing common.h declares is defined here for this library (the link is -Bsymbolic).
-#include <stdarg.h>
+// A library of its own, libvtx_mix.so (include/vtx_mix.h): the other four keep their export lists and versions.  Error
+// plumbing, version and last-error exports, and grid_for: side_lib.h.
 #include <string.h>
-#include "common.h"
+#include "side_lib.h"
 #include "../../include/vtx_mix.h"
 
+VTX_SIDE_LIB(mix)
+
 namespace vtx {
-
-static thread_local char g_mix_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_mix_err, sizeof(g_mix_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return VTX_ELAUNCH;
-  }
-  return VTX_OK;
-}
 
 // ---- CutMix: swap the box rows of clip b and clip B-1-b, b < B/2 -------------------------------------------------------
 // A box row of one frame is (xh - xl) * 3 contiguous bytes; nothing about it is aligned (W*3, xl*3 and the clip pointer are
@@ -168,17 +151,9 @@ __global__ __launch_bounds__(256) void patch_rows_mix_u8_kernel(int B, int Tn, i
   }
 }
 
-static inline int grid_for(long work, int cap) {
-  const long g = (work + 255) / 256;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-
 }  // namespace vtx
 
 using namespace vtx;
-
-extern "C" int vtx_mix_version(void) { return 100; }  // 0.1.0
-extern "C" const char* vtx_mix_last_error_string(void) { return g_mix_err; }
 
 extern "C" int vtx_cutmix_batch_u8(int B, int T, int H, int W, unsigned char* clip, int yl, int yh, int xl, int xh, void* stream) {
   VTX_REQUIRE(clip, VTX_EINVAL, "cutmix_batch_u8: null pointer");

@@ -21,32 +21,15 @@
 // solarize: 16 bytes per thread), else one pixel per thread with byte accesses.
 //
 // A library of its own, libvtx_randaug.so (include/vtx_randaug.h): libvtx_aug.so keeps its seven symbols and its version.
-// The error plumbing common.h declares is defined here for this library (the link is -Bsymbolic).
+// Error plumbing, version and last-error exports: VTX_SIDE_LIB(randaug) (side_lib.h).
 #include <math.h>
-#include <stdarg.h>
 #include <string.h>
-#include "common.h"
+#include "side_lib.h"
 #include "../../include/vtx_randaug.h"
 
+VTX_SIDE_LIB(randaug)
+
 namespace vtx {
-
-static thread_local char g_randaug_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_randaug_err, sizeof(g_randaug_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return VTX_ELAUNCH;
-  }
-  return VTX_OK;
-}
 
 // ---- pixel groups ---------------------------------------------------------------------------------------------------
 // A thread owns PP consecutive pixels of a frame (linear index i .. i + PP - 1): 12 bytes as three words, or 3 bytes.
@@ -415,9 +398,6 @@ using namespace vtx;
   VTX_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0, VTX_EINVAL, name ": B=%d T=%d H=%d W=%d must all be positive", B, T, H, W);   \
   VTX_REQUIRE((long)H * W <= (1L << 28), VTX_EINVAL, name ": %dx%d frames exceed 2^28 pixels", H, W);                         \
   VTX_REQUIRE((long)B * T <= 65535, VTX_EINVAL, name ": %ld frames exceed the grid (65535)", (long)B * T)
-
-extern "C" int vtx_randaug_version(void) { return 100; }  // 0.1.0
-extern "C" const char* vtx_randaug_last_error_string(void) { return g_randaug_err; }
 
 extern "C" int vtx_clip_warp_nearest_u8(int B, int T, int H, int W, const unsigned char* src, unsigned char* dst, const float* theta,
                                         const int32_t* sel, void* stream) {

@@ -16,32 +16,16 @@
 // = 22.5 MB per clip and reads 2.4 MB of clip bytes, each about 4.6 times (from L2); the float route reads 9.6 MB per clip
 // that a normalising pass had to write first.  Store-bound either way.
 //
-// A library of its own, libvtx_stem.so (include/vtx_stem.h): the other five keep their export lists and versions.  The
-// error plumbing common.h declares is defined here for this library (the link is -Bsymbolic).  -ffp-contract=off as hog.hip.
-#include <stdarg.h>
+// A library of its own, libvtx_stem.so (include/vtx_stem.h): the other five keep their export lists and versions.  Error
+// plumbing, version and last-error exports, and grid_for: side_lib.h.  -ffp-contract=off as hog.hip.
 #include <string.h>
+#include "side_lib.h"
 #include "hog_kernel.h"
 #include "../../include/vtx_stem.h"
 
+VTX_SIDE_LIB(stem)
+
 namespace vtx {
-
-static thread_local char g_stem_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_stem_err, sizeof(g_stem_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return VTX_ELAUNCH;
-  }
-  return VTX_OK;
-}
 
 // n(v,c) depends on (v, c) alone: each workgroup computes the 3 x 256 values once into LDS (768 entries over 256 threads: six
 // divisions per thread and workgroup, and the launcher sizes the grid so that a workgroup stores some twenty times 4 KiB
@@ -93,17 +77,9 @@ __global__ __launch_bounds__(256) void im2col3d_u8_kernel(int B, int Tc, int H, 
   }
 }
 
-static inline int grid_for(long work, int cap) {
-  const long g = (work + 255) / 256;
-  return (int)(g > cap ? cap : (g < 1 ? 1 : g));
-}
-
 }  // namespace vtx
 
 using namespace vtx;
-
-extern "C" int vtx_stem_version(void) { return 100; }  // 0.1.0
-extern "C" const char* vtx_stem_last_error_string(void) { return g_stem_err; }
 
 extern "C" int vtx_im2col3d_u8(int dtype, int B, int T, int H, int W, const int* k3, const int* s3, const int* p3, int Kp,
                                const unsigned char* clip, const float* host_mean3, const float* host_std3, void* rows, void* stream) {

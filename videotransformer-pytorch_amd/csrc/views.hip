@@ -10,49 +10,29 @@
 // overlap in x (256x341 -> lefts 0, 117, 58: 341 distinct columns for 3 x 224 stored ones): the kernel resamples each
 // column of the union once and stores it to every view whose window holds it.  Columns in no view are not computed.
 //
-// Arithmetic contract: that of clip_resample_u8_kernel (csrc/aug.hip), operation for operation -- x pass first, then the
-// y pass, taps in ascending order, float32 without fma contraction, clamp to [0, 255], round half-to-even -- so a view is
-// byte for byte what vtx_clip_resample_u8 gives on the gathered frames with the same tables, sliced to the window.
+// Arithmetic contract: that of clip_resample_u8_kernel (csrc/aug.hip), because both run resample_band (resample_band.h) --
+// x pass first, then the y pass, taps in ascending order, float32 without fma contraction, clamp to [0, 255], round
+// half-to-even -- so a view is byte for byte what vtx_clip_resample_u8 gives on the gathered frames with the same tables,
+// sliced to the window.
 //
 // Bytes: per selected frame Hs*Ws*3 read (the rows of the crop window) and V*H*W*3 written; the composition it
 // replaces (gathered copy of the source, one resampling pass per view, concatenating copy) reads and writes the selected
 // source frames once more, reads them V times and moves the result three times.
 //
 // A library of its own, libvtx_views.so (include/vtx_views.h): libvtx_aug.so keeps its seven symbols and its version.
-// The error plumbing common.h declares is defined here for this library (the link is -Bsymbolic).
-#include <math.h>
-#include <stdarg.h>
-#include <string.h>
-#include "common.h"
+// Error plumbing, version and last-error exports: VTX_SIDE_LIB(views) (side_lib.h).
+#include "side_lib.h"
+#include "resample_band.h"
 #include "../../include/vtx_views.h"
+
+VTX_SIDE_LIB(views)
 
 namespace vtx {
 
-static thread_local char g_views_err[512] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_views_err, sizeof(g_views_err), fmt, ap);
-  va_end(ap);
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    set_error("%s: launch failed: %s", what, hipGetErrorString(e));
-    return VTX_ELAUNCH;
-  }
-  return VTX_OK;
-}
-
-// One thread per column x of the resized frame (all three channels), one workgroup per (selected frame, band of VW_ROWS
-// output rows, 256 columns).  The band's source rows are walked once in ascending order, as in clip_resample_u8_kernel:
-// x pass of (s, x) in registers, then added, times the y weight, to every output row of the band whose window holds s.
-// Frame index, window lefts and tap windows are clamped here whatever the tables say; the caller validates them.
-constexpr int VW_ROWS = 8;       // output rows per band: 3 * 8 accumulators per thread (aug.hip: RS_ROWS)
-constexpr int VW_MAX_VIEWS = 8;
-
+// One thread per column x of the resized frame (all three channels), one workgroup per (selected frame, band of BAND_ROWS
+// output rows, 256 columns).  A column is resampled once (resample_band) and stored to every view whose window holds it; a
+// column in no view returns before any table load.  Frame index, window lefts and tap windows are clamped here whatever the
+// tables say; the caller validates them.
 __global__ __launch_bounds__(256) void clip_views_u8_kernel(int Ts, int T, int Hs, int Ws, int H, int Wr, int V, int W,
                                                             const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                             const int* __restrict__ frames, const int* __restrict__ left,
@@ -60,15 +40,14 @@ __global__ __launch_bounds__(256) void clip_views_u8_kernel(int Ts, int T, int H
                                                             const float* __restrict__ xw, int xt,
                                                             const int* __restrict__ yf, const int* __restrict__ yc,
                                                             const float* __restrict__ yw, int yt) {
-#pragma clang fp contract(off)
   const int b = blockIdx.z / T, t = blockIdx.z - b * T;
-  const int r0 = blockIdx.y * VW_ROWS;
+  const int r0 = blockIdx.y * BAND_ROWS;
   const int x = blockIdx.x * 256 + threadIdx.x;
   // the views whose window holds this column (the lefts are the same for every thread: scalar registers)
-  int off[VW_MAX_VIEWS];
+  int off[MAX_VIEWS];
   bool any = false;
 #pragma unroll
-  for (int v = 0; v < VW_MAX_VIEWS; ++v) {
+  for (int v = 0; v < MAX_VIEWS; ++v) {
     off[v] = -1;
     if (v < V) {
       int l = left[b * V + v];
@@ -79,72 +58,21 @@ __global__ __launch_bounds__(256) void clip_views_u8_kernel(int Ts, int T, int H
   if (!any) return;                                      // also every x >= Wr: l + W <= Wr
   int ts = frames ? frames[b * T + t] : t;
   ts = ts < 0 ? 0 : (ts > Ts - 1 ? Ts - 1 : ts);
-  // this thread's x taps, clamped into the source row
-  int fx = xf[(long)b * Wr + x], cx = xc[(long)b * Wr + x];
-  cx = cx < 0 ? 0 : (cx > xt ? xt : cx);
-  fx = fx < 0 ? 0 : (fx > Ws ? Ws : fx);
-  if (fx + cx > Ws) { fx = Ws - cx < 0 ? 0 : Ws - cx; cx = cx > Ws ? Ws : cx; }
-  const float* wx = xw + ((long)b * Wr + x) * xt;
-  // the band's y windows
-  int fy[VW_ROWS], cy[VW_ROWS];
-  int lo = Hs, hi = 0;
+  const long col = (long)b * Wr + x;
+  resample_band(src + ((long)b * Ts + ts) * Hs * Ws * 3, Hs, Ws, H, r0, xf[col], xc[col], xw + col * xt, xt,
+                yf + (long)b * H, yc + (long)b * H, yw + (long)b * H * yt, yt, [=](int r, uint8_t q0, uint8_t q1, uint8_t q2) {
 #pragma unroll
-  for (int r = 0; r < VW_ROWS; ++r) {
-    const int ri = r0 + r < H ? r0 + r : H - 1;
-    int f = yf[(long)b * H + ri], c = yc[(long)b * H + ri];
-    c = c < 0 ? 0 : (c > yt ? yt : c);
-    f = f < 0 ? 0 : (f > Hs ? Hs : f);
-    if (f + c > Hs) { f = Hs - c < 0 ? 0 : Hs - c; c = c > Hs ? Hs : c; }
-    if (r0 + r >= H) c = 0;
-    fy[r] = f; cy[r] = c;
-    if (c > 0) { lo = f < lo ? f : lo; hi = f + c > hi ? f + c : hi; }
-  }
-  float acc[VW_ROWS][3];
-#pragma unroll
-  for (int r = 0; r < VW_ROWS; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.0f;
-  const uint8_t* img = src + ((long)b * Ts + ts) * Hs * Ws * 3;
-  for (int s = lo; s < hi; ++s) {
-    const uint8_t* p = img + ((long)s * Ws + fx) * 3;
-    float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
-    for (int k = 0; k < cx; ++k) {
-      const float w = wx[k];
-      v0 = v0 + w * (float)p[3 * k];
-      v1 = v1 + w * (float)p[3 * k + 1];
-      v2 = v2 + w * (float)p[3 * k + 2];
-    }
-#pragma unroll
-    for (int r = 0; r < VW_ROWS; ++r) {
-      const int k = s - fy[r];
-      if (k >= 0 && k < cy[r]) {
-        const float w = yw[((long)b * H + r0 + r) * yt + k];
-        acc[r][0] = acc[r][0] + w * v0;
-        acc[r][1] = acc[r][1] + w * v1;
-        acc[r][2] = acc[r][2] + w * v2;
-      }
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < VW_ROWS; ++r) {
-    if (r0 + r >= H) break;
-    uint8_t q[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      q[c] = (uint8_t)(int)__builtin_rintf(fminf(fmaxf(acc[r][c], 0.0f), 255.0f));      // half-to-even, as torch.round
-#pragma unroll
-    for (int v = 0; v < VW_MAX_VIEWS; ++v) {
-      if (off[v] < 0) continue;
-      uint8_t* o = dst + (((((long)b * V + v) * T + t) * H + r0 + r) * W + off[v]) * 3;
-      o[0] = q[0]; o[1] = q[1]; o[2] = q[2];
-    }
-  }
+                  for (int v = 0; v < MAX_VIEWS; ++v) {
+                    if (off[v] < 0) continue;
+                    uint8_t* o = dst + (((((long)b * V + v) * T + t) * H + r0 + r) * W + off[v]) * 3;
+                    o[0] = q0; o[1] = q1; o[2] = q2;
+                  }
+                });
 }
 
 }  // namespace vtx
 
 using namespace vtx;
-
-extern "C" int vtx_views_version(void) { return 100; }  // 0.1.0
-extern "C" const char* vtx_views_last_error_string(void) { return g_views_err; }
 
 extern "C" int vtx_clip_views_u8(int B, int Ts, int T, int Hs, int Ws, int H, int Wr, int V, int W, const unsigned char* src,
                                  unsigned char* dst, const int32_t* frames, const int32_t* left, const int32_t* x_first,
@@ -153,12 +81,12 @@ extern "C" int vtx_clip_views_u8(int B, int Ts, int T, int Hs, int Ws, int H, in
   VTX_REQUIRE(B > 0 && Ts > 0 && T > 0 && Hs > 0 && Ws > 0 && H > 0 && Wr > 0 && V > 0 && W > 0 && x_taps > 0 && y_taps > 0, VTX_EINVAL,
               "clip_views_u8: B=%d Ts=%d T=%d source %dx%d rows %d resized width %d views %d of width %d taps %d/%d must all be positive",
               B, Ts, T, Hs, Ws, H, Wr, V, W, x_taps, y_taps);
-  VTX_REQUIRE(V <= VW_MAX_VIEWS, VTX_EINVAL, "clip_views_u8: %d views, at most %d are supported", V, VW_MAX_VIEWS);
+  VTX_REQUIRE(V <= MAX_VIEWS, VTX_EINVAL, "clip_views_u8: %d views, at most %d are supported", V, MAX_VIEWS);
   VTX_REQUIRE(W <= Wr, VTX_EINVAL, "clip_views_u8: a view of %d columns does not fit the resized row of %d", W, Wr);
   VTX_REQUIRE(src && dst && left && x_first && x_count && x_weights && y_first && y_count && y_weights, VTX_EINVAL, "clip_views_u8: null pointer");
   VTX_REQUIRE(frames || T == Ts, VTX_EINVAL, "clip_views_u8: without frame indices every frame is taken: T=%d, Ts=%d", T, Ts);
   VTX_REQUIRE(src != dst, VTX_EINVAL, "clip_views_u8: in place is not supported");
-  const long bands = (H + VW_ROWS - 1) / VW_ROWS;
+  const long bands = (H + BAND_ROWS - 1) / BAND_ROWS;
   VTX_REQUIRE((long)B * T <= 65535 && bands <= 65535, VTX_EINVAL, "clip_views_u8: %ld frames / %ld row bands exceed the grid (65535 each)", (long)B * T, bands);
   dim3 grid((unsigned)((Wr + 255) / 256), (unsigned)bands, (unsigned)(B * T));
   hipLaunchKernelGGL(clip_views_u8_kernel, grid, dim3(256), 0, as_stream(stream), Ts, T, Hs, Ws, H, Wr, V, W, src, dst, frames, left,

@@ -7,6 +7,7 @@ symbol is absent, importing the ops raises.
 """
 import ctypes as C
 import os
+from functools import partial
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _PKG = os.path.dirname(_HERE)
@@ -246,238 +247,76 @@ DROPOUT_SIGNATURES = {
                               C.c_ulonglong, cf, C.c_ulonglong, C.c_uint, C.c_ulonglong, vp]),
 }
 
+# key -> (name of the path constant, signatures): every library beside libvtx.so.  The path is read when the library is
+# first loaded.  libvtx_<key>.so exports vtx_<key>_version and vtx_<key>_last_error_string beside its entry points.
+_SIDE = {
+    'aug': ('AUG_LIB_PATH', AUG_SIGNATURES),
+    'randaug': ('RANDAUG_LIB_PATH', RANDAUG_SIGNATURES),
+    'views': ('VIEWS_LIB_PATH', VIEWS_SIGNATURES),
+    'mix': ('MIX_LIB_PATH', MIX_SIGNATURES),
+    'stem': ('STEM_LIB_PATH', STEM_SIGNATURES),
+    'ragged': ('RAGGED_LIB_PATH', RAGGED_SIGNATURES),
+    'dropout': ('DROPOUT_LIB_PATH', DROPOUT_SIGNATURES),
+}
 _lib = None
-_aug = None
-_randaug = None
-_views = None
-_mix = None
-_stem = None
-_ragged = None
-_dropout = None
+_side = {}
 
 
 class VtxError(RuntimeError):
     pass
 
 
-def load_aug():
-    """Load libvtx_aug.so and bind every symbol of include/vtx_aug.h.  Raises if anything is missing: there is no fallback."""
-    global _aug
-    if _aug is not None:
-        return _aug
-    if not os.path.isfile(AUG_LIB_PATH):
-        raise VtxError(f'libvtx_aug.so not found at {AUG_LIB_PATH}: build it with '
+def _bind(path, soname, signatures):
+    """Load one library and bind every listed symbol.  Raises if anything is missing: there is no fallback."""
+    if not os.path.isfile(path):
+        raise VtxError(f'{soname} not found at {path}: build it with '
                        f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(AUG_LIB_PATH)
-    for name, (res, args) in AUG_SIGNATURES.items():
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
-            raise VtxError(f'libvtx_aug.so does not export {name}') from e
+            raise VtxError(f'{soname} does not export {name}') from e
         fn.restype = res
         fn.argtypes = args
-    _aug = lib
     return lib
 
 
-def aug_check(rc, what=''):
-    msg = load_aug().vtx_aug_last_error_string()
+def _load_side(key):
+    """libvtx_<key>.so with every symbol of include/vtx_<key>.h bound (loaded once)."""
+    if key not in _side:
+        path_name, signatures = _SIDE[key]
+        _side[key] = _bind(globals()[path_name], f'libvtx_{key}.so', signatures)
+    return _side[key]
+
+
+def _side_check(key, rc, what=''):
+    msg = getattr(_load_side(key), f'vtx_{key}_last_error_string')()
     raise VtxError(f'{what} failed (code {rc}): {msg.decode() if msg else "?"}')
 
 
-def aug_call(name, *args):
-    rc = getattr(load_aug(), name)(*args)
+def _side_call(key, name, *args):
+    rc = getattr(_load_side(key), name)(*args)
     if rc != 0:
-        aug_check(rc, name)
+        _side_check(key, rc, name)
 
 
-def load_randaug():
-    """Load libvtx_randaug.so and bind every symbol of include/vtx_randaug.h.  Raises if anything is missing: there is no fallback."""
-    global _randaug
-    if _randaug is not None:
-        return _randaug
-    if not os.path.isfile(RANDAUG_LIB_PATH):
-        raise VtxError(f'libvtx_randaug.so not found at {RANDAUG_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(RANDAUG_LIB_PATH)
-    for name, (res, args) in RANDAUG_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_randaug.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _randaug = lib
-    return lib
-
-
-def randaug_call(name, *args):
-    lib = load_randaug()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_randaug_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def load_views():
-    """Load libvtx_views.so and bind every symbol of include/vtx_views.h.  Raises if anything is missing: there is no fallback."""
-    global _views
-    if _views is not None:
-        return _views
-    if not os.path.isfile(VIEWS_LIB_PATH):
-        raise VtxError(f'libvtx_views.so not found at {VIEWS_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(VIEWS_LIB_PATH)
-    for name, (res, args) in VIEWS_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_views.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _views = lib
-    return lib
-
-
-def views_call(name, *args):
-    lib = load_views()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_views_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def load_mix():
-    """Load libvtx_mix.so and bind every symbol of include/vtx_mix.h.  Raises if anything is missing: there is no fallback."""
-    global _mix
-    if _mix is not None:
-        return _mix
-    if not os.path.isfile(MIX_LIB_PATH):
-        raise VtxError(f'libvtx_mix.so not found at {MIX_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(MIX_LIB_PATH)
-    for name, (res, args) in MIX_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_mix.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _mix = lib
-    return lib
-
-
-def mix_call(name, *args):
-    lib = load_mix()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_mix_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def load_stem():
-    """Load libvtx_stem.so and bind every symbol of include/vtx_stem.h.  Raises if anything is missing: there is no fallback."""
-    global _stem
-    if _stem is not None:
-        return _stem
-    if not os.path.isfile(STEM_LIB_PATH):
-        raise VtxError(f'libvtx_stem.so not found at {STEM_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(STEM_LIB_PATH)
-    for name, (res, args) in STEM_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_stem.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _stem = lib
-    return lib
-
-
-def stem_call(name, *args):
-    lib = load_stem()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_stem_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def load_ragged():
-    """Load libvtx_ragged.so and bind every symbol of include/vtx_ragged.h.  Raises if anything is missing: there is no fallback."""
-    global _ragged
-    if _ragged is not None:
-        return _ragged
-    if not os.path.isfile(RAGGED_LIB_PATH):
-        raise VtxError(f'libvtx_ragged.so not found at {RAGGED_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(RAGGED_LIB_PATH)
-    for name, (res, args) in RAGGED_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_ragged.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _ragged = lib
-    return lib
-
-
-def ragged_call(name, *args):
-    lib = load_ragged()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_ragged_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
-
-
-def load_dropout():
-    """Load libvtx_dropout.so and bind every symbol of include/vtx_dropout.h.  Raises if anything is missing: there is no fallback."""
-    global _dropout
-    if _dropout is not None:
-        return _dropout
-    if not os.path.isfile(DROPOUT_LIB_PATH):
-        raise VtxError(f'libvtx_dropout.so not found at {DROPOUT_LIB_PATH}: build it with '
-                       f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(DROPOUT_LIB_PATH)
-    for name, (res, args) in DROPOUT_SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx_dropout.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _dropout = lib
-    return lib
-
-
-def dropout_call(name, *args):
-    lib = load_dropout()
-    rc = getattr(lib, name)(*args)
-    if rc != 0:
-        msg = lib.vtx_dropout_last_error_string()
-        raise VtxError(f'{name} failed (code {rc}): {msg.decode() if msg else "?"}')
+load_aug, aug_call = partial(_load_side, 'aug'), partial(_side_call, 'aug')
+load_randaug, randaug_call = partial(_load_side, 'randaug'), partial(_side_call, 'randaug')
+load_views, views_call = partial(_load_side, 'views'), partial(_side_call, 'views')
+load_mix, mix_call = partial(_load_side, 'mix'), partial(_side_call, 'mix')
+load_stem, stem_call = partial(_load_side, 'stem'), partial(_side_call, 'stem')
+load_ragged, ragged_call = partial(_load_side, 'ragged'), partial(_side_call, 'ragged')
+load_dropout, dropout_call = partial(_load_side, 'dropout'), partial(_side_call, 'dropout')
+aug_check = partial(_side_check, 'aug')
 
 
 def load():
     """Load libvtx.so and bind every declared symbol.  Raises if anything is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.isfile(LIB_PATH):
-        raise VtxError(
-            f'libvtx.so not found at {LIB_PATH}: build it with '
-            f'`python videotransformer-pytorch_amd/csrc/build.py` (there is no CPU/PyTorch fallback)')
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VtxError(f'libvtx.so does not export {name}') from e
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _bind(LIB_PATH, 'libvtx.so', SIGNATURES)
+    return _lib
 
 
 def check(rc, what=''):

@@ -791,6 +791,26 @@ def _check_u8_clip(clip, what):
         raise TypeError(f'{what}: clip must be uint8 [B,T,H,W,3], got {clip.dtype} {tuple(clip.shape)}')
 
 
+def _is_table(tab, B, n=None):
+    """Is ``tab`` a resample table of B clips and n outputs (None: as many as it holds): (first int32 [B,n], count int32 [B,n],
+    weights float32 [B,n,taps]), contiguous device tensors?"""
+    f, c, w = tab
+    need_cuda(f, c, w)
+    if n is None:
+        n = f.shape[1] if f.ndim == 2 else -1
+    return (f.dtype == torch.int32 and c.dtype == torch.int32 and w.dtype == torch.float32 and tuple(f.shape) == (B, n)
+            and tuple(c.shape) == (B, n) and w.ndim == 3 and tuple(w.shape[:2]) == (B, n)
+            and f.is_contiguous() and c.is_contiguous() and w.is_contiguous())
+
+
+def _table_lengths(name, B, xtab, ytab):
+    """The tables of the view kernels, whose output lengths the tables themselves give -> (columns of xtab, rows of ytab)."""
+    for tab in (xtab, ytab):
+        if not _is_table(tab, B) or tab[0].shape[1] < 1 or tab[2].shape[2] < 1:
+            raise TypeError(f'{name}: a table is (int32 [{B},n], int32 [{B},n], float32 [{B},n,taps]), contiguous')
+    return xtab[0].shape[1], ytab[0].shape[1]
+
+
 def clip_resample_u8(src, out_hw, xtab, ytab):
     """src uint8 [B,T,Hs,Ws,3] -> uint8 [B,T,H,W,3].  xtab = (first [B,W] int32, count [B,W] int32, weights [B,W,K] float32)
     device tensors, one resample_table per clip; ytab likewise with H."""
@@ -798,11 +818,8 @@ def clip_resample_u8(src, out_hw, xtab, ytab):
     src = src.contiguous()
     B, T, Hs, Ws, _ = src.shape
     H, W = int(out_hw[0]), int(out_hw[1])
-    for (f, c, w), n in ((xtab, W), (ytab, H)):
-        need_cuda(f, c, w)
-        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
-                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n)
-                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
+    for tab, n in ((xtab, W), (ytab, H)):
+        if not _is_table(tab, B, n):
             raise TypeError(f'clip_resample_u8: a table is (int32 [{B},{n}], int32 [{B},{n}], float32 [{B},{n},taps]), contiguous')
     dst = torch.empty(B, T, H, W, 3, dtype=torch.uint8, device=src.device)
     with _timed('clip_resample', nbytes=src.numel() + dst.numel(), key=f'{B}x{T} {Hs}x{Ws}->{H}x{W}'):
@@ -907,18 +924,27 @@ def clip_equalize_u8_(clip, sel):
 
 
 # ------------------------------------------------- test-time views (csrc/views.hip -> libvtx_views.so)
-def _views_index(t, B, lo, hi, what, device):
-    """frames / left: an int32 [B,n] device tensor is taken as it is (the kernel clamps what it reads; whoever built it validated
-    it); host values -- a CPU integer tensor, an array or nested lists -- are checked against lo <= v <= hi and uploaded."""
+def _index_rows(name, t, B, what):
+    """frames / left of the view kernels, [B,n]: an int32 device tensor is returned as it is (the kernel clamps what it reads;
+    whoever built it validated it); host values -- a CPU integer tensor, an array or nested lists -- come back as an integer
+    array whose range the caller checks."""
     import numpy as np
     if isinstance(t, torch.Tensor) and t.is_cuda:
         need_cuda(t)
         if t.dtype != torch.int32 or t.ndim != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
-            raise TypeError(f'clip_views_u8: {what} must be int32 [{B},n] contiguous, got {t.dtype} {tuple(t.shape)}')
+            raise TypeError(f'{name}: {what} must be int32 [{B},n] contiguous, got {t.dtype} {tuple(t.shape)}')
         return t
     a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
     if a.dtype.kind not in 'iu' or a.ndim != 2 or a.shape[0] != B or a.shape[1] < 1:
-        raise TypeError(f'clip_views_u8: {what} must be integers [{B},n], got {a.dtype} {a.shape}')
+        raise TypeError(f'{name}: {what} must be integers [{B},n], got {a.dtype} {a.shape}')
+    return a
+
+
+def _views_index(t, B, lo, hi, what, device):
+    """frames / left of clip_views_u8: host values are checked against lo <= v <= hi and uploaded."""
+    a = _index_rows('clip_views_u8', t, B, what)
+    if isinstance(a, torch.Tensor):
+        return a
     if a.min() < lo or a.max() > hi:
         raise ValueError(f'clip_views_u8: {what} must lie in {lo} .. {hi}, got {int(a.min())} .. {int(a.max())}')
     return upload_i32(a, device).view(a.shape)
@@ -935,15 +961,7 @@ def clip_views_u8(src, frames, left, width, xtab, ytab, out=None):
     src = src.contiguous()
     B, Ts, Hs, Ws, _ = src.shape
     W = int(width)
-    for tab in (xtab, ytab):
-        f, c, w = tab
-        need_cuda(f, c, w)
-        n = f.shape[1] if f.ndim == 2 else -1
-        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
-                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n) or n < 1 or w.shape[2] < 1
-                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
-            raise TypeError(f'clip_views_u8: a table is (int32 [{B},n], int32 [{B},n], float32 [{B},n,taps]), contiguous')
-    Wr, H = xtab[0].shape[1], ytab[0].shape[1]
+    Wr, H = _table_lengths('clip_views_u8', B, xtab, ytab)
     if not 0 < W <= Wr:
         raise ValueError(f'clip_views_u8: views of {W} columns do not fit the resized row of {Wr}')
     left = _views_index(left, B, 0, Wr - W, f'left (left + width <= {Wr})', src.device)
@@ -1011,17 +1029,12 @@ def clips_table(clips, widths, what='clips_views_u8'):
 
 
 def _ragged_index(t, B, hi, what, device):
-    """frames / left of clips_views_u8: an int32 [B,n] device tensor is taken as it is (the kernel clamps what it reads with the
-    clip's own numbers); host integers are checked row by row against 0 <= v <= hi[b] -> int32 array [B,n], not yet uploaded."""
+    """frames / left of clips_views_u8: host integers are checked row by row against 0 <= v <= hi[b] (the clip's own numbers)
+    -> int32 array [B,n], not yet uploaded."""
     import numpy as np
-    if isinstance(t, torch.Tensor) and t.is_cuda:
-        need_cuda(t)
-        if t.dtype != torch.int32 or t.ndim != 2 or t.shape[0] != B or t.shape[1] < 1 or not t.is_contiguous():
-            raise TypeError(f'clips_views_u8: {what} must be int32 [{B},n] contiguous, got {t.dtype} {tuple(t.shape)}')
-        return t
-    a = t.numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
-    if a.dtype.kind not in 'iu' or a.ndim != 2 or a.shape[0] != B or a.shape[1] < 1:
-        raise TypeError(f'clips_views_u8: {what} must be integers [{B},n], got {a.dtype} {a.shape}')
+    a = _index_rows('clips_views_u8', t, B, what)
+    if isinstance(a, torch.Tensor):
+        return a
     bad = ((a < 0) | (a > np.asarray(hi).reshape(B, 1))).any(axis=1)
     if bad.any():
         b = int(np.argmax(bad))
@@ -1056,15 +1069,7 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
         need_cuda(*clips)
         ct = None
     B, W = len(ct.kept if ct else clips), int(width)
-    for tab in (xtab, ytab):
-        f, c, w = tab
-        need_cuda(f, c, w)
-        n = f.shape[1] if f.ndim == 2 else -1
-        if (f.dtype != torch.int32 or c.dtype != torch.int32 or w.dtype != torch.float32 or tuple(f.shape) != (B, n)
-                or tuple(c.shape) != (B, n) or w.ndim != 3 or tuple(w.shape[:2]) != (B, n) or n < 1 or w.shape[2] < 1
-                or not (f.is_contiguous() and c.is_contiguous() and w.is_contiguous())):
-            raise TypeError(f'{name}: a table is (int32 [{B},n], int32 [{B},n], float32 [{B},n,taps]), contiguous')
-    Wr_max, H = xtab[0].shape[1], ytab[0].shape[1]
+    Wr_max, H = _table_lengths(name, B, xtab, ytab)
     if ct is None:
         ct = clips_table(clips, [Wr_max] * B if widths is None else widths, name)
     shapes, widths, dev = ct.shapes, ct.widths, ct.kept[0].device
