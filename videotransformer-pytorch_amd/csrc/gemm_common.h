@@ -78,6 +78,15 @@ __device__ inline int xcd_remap(int bid, int nwg) {
   return start + idx;
 }
 
+// One LDS-DMA request: every lane fetches 16 bytes, the wave's 1 KiB lands at a wave-uniform LDS base in lane order.
+__device__ inline void dma16(const bf16raw* src, bf16raw* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+// Counted waits of the LDS-DMA kernels: at most N vector-memory requests outstanding; every LDS read returned.
+template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+__device__ inline void lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
 // Store the wave's 2x2 MFMA 32x32 accumulators (C/D layout: col = lane&31,
 // row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)) into its private fp32 staging tile.
 __device__ inline void stage_acc(float* stage, const f32x16 (&acc)[2][2], int lane) {

@@ -122,10 +122,7 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_nt_bf16_kernel(
 // 64 x 16 B = 1 KiB = 8 tile rows at a wave-uniform LDS base in lane order, so the XOR swizzle
 // is applied on the SOURCE side: lane (row, physical chunk pc) fetches logical chunk
 // pc ^ ((row>>1)&7) of its row -- still one full 128-B line per 8 lanes.  Requires K % 64 == 0.
-__device__ inline void dma16(const bf16raw* src, bf16raw* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
+// (the request itself is dma16 of gemm_common.h)
 
 // Result stores of the persistent kernel are nontemporal: a result is never read back by the launch, and as ordinary
 // stores the 0.2 - 0.9 GB of it pushed the A panels out of L2 before the other column tiles of the group had re-read
@@ -243,7 +240,6 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_nt_bf16_dma_kernel(
 //   <4,3,32>:  72 KB, TWO workgroups per CU, so one's prologue / epilogue (measured ~8 us per
 //              tile, ~40 % of a K=768 tile) overlaps the other's main loop.
 // LDS rows are BK elements; 16-B chunk swizzle: BK=64 -> ^((row>>1)&7), BK=32 -> ^((row>>2)&3).
-template <int N> __device__ inline void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int BK> __device__ inline int ring_sw(int row) { return BK == 64 ? ((row >> 1) & 7) : ((row >> 2) & 3); }
 
@@ -393,8 +389,6 @@ constexpr int PP_RING_BYTES = 2 * PP_BUF * 2;   // 131072
 constexpr int PP_STG_LD = 64;                   // staging rows are unpadded: 8 waves x [16][64] fp32 = 32 KB
 constexpr int PP_LDS_BYTES = PP_RING_BYTES + 8 * 16 * PP_STG_LD * 4;   // 163840 = all of the CU's LDS
 constexpr int PP_GRID = 256;                    // persistent: one workgroup per CU
-
-__device__ inline void lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Persistent: workgroup b (XCD b%8, slot b/8) walks the tiles of its XCD's contiguous tile range in
 // steps of gridDim/8.  The C tile is 128 KB, and a non-persistent launch exposes its write-out

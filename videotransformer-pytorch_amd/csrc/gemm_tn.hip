@@ -4,29 +4,28 @@
 // (reference transformer.py:160,162,225,501,505; patch projection :116-126;
 // video_transformer.py:855).  The reduction runs over the token rows M, which
 // are NOT contiguous for either operand, so the MFMA operand fragments are
-// transposed reads of row-major LDS tiles:
-//   bf16: tiles [64 m][128 n] bf16 (row stride 160 elements = 320 B so that the
-//         4 rows x 64 B touched by each half-wave of ds_read_b64_tr_b16 fall in
-//         four disjoint bank quarters); the hardware transpose read
-//         ds_read_b64_tr_b16 delivers 4 consecutive-m values of one column per
-//         lane, two reads build the 8-deep K fragment of v_mfma_f32_32x32x16_bf16.
-//         VTX_TN_SAFE=1 selects plain 2-byte LDS gathers instead (slow, no
-//         dependence on the tr instruction) -- kept as a diagnostic path.
-//   fp32: tiles [16 m][128 n]; v_mfma_f32_32x32x2_f32 takes one element per lane,
-//         read straight along the row (conflict free, no transpose needed).
-// M is split over `splits` workgroup slices (fp32 slabs in the workspace) that a
-// second kernel sums in a fixed order: deterministic, no atomics.
-// Algorithmic FLOPs per launch: 2*M*N1*N2.
+// transposed reads of row-major LDS tiles (ds_read_b64_tr_b16 delivers 4 consecutive-m values of one
+// column per lane, two reads build the 8-deep K fragment of v_mfma_f32_32x32x16_bf16).
+// M is split over slabs (fp32 partials in the workspace) that a second kernel sums in a fixed order:
+// deterministic, no atomics.  Algorithmic FLOPs per launch: 2*M*N1*N2.
+//
+// Seven kernels, chosen by tn_plan (below):
+//   gemm_tn_bf16_kernel<SAFE>  register-staged 128x128 tiles (gemm_nodma / tn_safe)
+//   gemm_tn_f32_kernel         the same for fp32 operands
+//   gemm_tn_bf16_dma_kernel    128x128, LDS-DMA double buffer (dma2: M < 1024)
+//   gemm_tn_bf16_ring_kernel   256x128, three-stage LDS-DMA ring (M >= 1024 where the ping-pong kernel is ineligible)
+//   gemm_tn_bf16_pp_kernel     256x256, two staggered wave groups (the default wherever eligible)
+//   gemm_tn_bf16_w4_kernel     256x256, one wave per SIMD (gemm_tn=w4)
+//   colsum_kernel              column sums alone
+// What they share is written once, as plain functions in front of them: the tile / slab decode (tn_tile), accumulator
+// zeroing (tn_zero), the column-sum accumulate and fold (tn_cs_add, tn_cs_put, tn_cs_fold), the slab store of staged
+// accumulators (tn_store, tn_epi16), the transposed fragment pair (tn_tr_pair, tn_tr_frag), the ragged-tile stager
+// (tn_stage_ragged) and the LDS-DMA feeder of the two 256x256 kernels (TnFeeder<pieces per wave>).
 #include <stdlib.h>
 #include <string>
 #include "gemm_common.h"
 
 namespace vtx {
-
-constexpr int TN_BKM = 64;        // m rows per tile (bf16)
-constexpr int TN_LD = 160;        // padded row length (bf16 elements)
-constexpr int TN_BKM32 = 16;      // m rows per tile (fp32)
-constexpr int TN_LD32 = 128;
 
 struct TnOut {
   float* slab; long slab_stride;  // [splits][N1*N2]
@@ -35,19 +34,151 @@ struct TnOut {
   int cs_fold;                    // ring / ping-pong kernels: [splits][cs_fold][N1], copy t2 = the K tiles kt % tiles2 == t2
 };
 
-__device__ inline void tn_store(const TnOut& o, const float* stage, int split, int r_base, int c_base, int lane) {
+// ---- tile and slab decode ----------------------------------------------------------------------
+// Workgroup -> slab `split` (token rows [m_begin, m_end)) and output tile (t1, t2) with origin (r0, c0).  REMAP: the
+// XCD-aware order (xcd_remap: every XCD takes a contiguous run of the split-major list, so its L2 serves each A / B row to
+// all the tiles that need it; round-robin placement re-fetches every panel once per XCD: 1.85 GB instead of 0.39 GB at
+// 768x3072).  REMAINDER: slabs are whole K tiles and the last one also takes what is left of M;
+// otherwise every slab is m_per_split rows cut at M.
+struct TnTile { int split, t1, t2, r0, c0, m_begin, m_end; };
+template <int TM, int TC, bool REMAINDER, typename Id>      // Id: int (remapped) or unsigned (blockIdx.x: an unsigned division)
+__device__ __forceinline__ TnTile tn_tile_of(Id bid, int M, int m_per_split, int tiles2, int tiles12) {
+  TnTile t;
+  t.split = bid / tiles12;
+  const int tile = bid - t.split * tiles12;
+  t.t1 = tile / tiles2; t.t2 = tile - t.t1 * tiles2;
+  t.r0 = t.t1 * TM; t.c0 = t.t2 * TC;
+  t.m_begin = t.split * m_per_split;
+  if (REMAINDER) t.m_end = (t.split == (int)(gridDim.x / tiles12) - 1) ? M : t.m_begin + m_per_split;
+  else t.m_end = min(M, t.m_begin + m_per_split);
+  return t;
+}
+template <int TM, int TC, bool REMAP, bool REMAINDER>
+__device__ __forceinline__ TnTile tn_tile(int M, int m_per_split, int tiles2, int tiles12) {
+  if (REMAP) return tn_tile_of<TM, TC, REMAINDER>(xcd_remap(blockIdx.x, gridDim.x), M, m_per_split, tiles2, tiles12);
+  return tn_tile_of<TM, TC, REMAINDER>((unsigned)blockIdx.x, M, m_per_split, tiles2, tiles12);
+}
+
+template <int NI, int NJ>
+__device__ __forceinline__ void tn_zero(f32x16 (&acc)[NI][NJ]) {
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// ---- column sums of A (bias gradient) ----------------------------------------------------------
+// the eight bf16 values of a 16-byte word, added into the thread's eight partial sums
+__device__ __forceinline__ void tn_cs_add(float (&cs)[8], const u32x4& v) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    cs[2 * j] += __uint_as_float(v[j] << 16);
+    cs[2 * j + 1] += __uint_as_float(v[j] & 0xffff0000u);
+  }
+}
+// Fold: every thread puts its partial sums of NV columns into red[row lane][TC tile columns]; thread c then adds the
+// RL row lanes of column c in the order 0, 1, 2, ... and stores to column-sum copy `copy` of the slab.
+template <int TC, int NV>
+__device__ __forceinline__ void tn_cs_put(float* red, int row_lane, int col, const float (&cs)[NV]) {
+#pragma unroll
+  for (int j = 0; j < NV; ++j) red[row_lane * TC + col + j] = cs[j];
+}
+template <int RL, int TC>
+__device__ __forceinline__ void tn_cs_fold(const float* red, const TnOut& o, const TnTile& t, int copy, int tid) {
+  __syncthreads();
+  if (tid < TC && t.r0 + tid < o.N1) {
+    float a = 0.f;
+#pragma unroll
+    for (int r = 0; r < RL; ++r) a += red[r * TC + tid];
+    o.cslab[(long)t.split * o.slab_stride + (long)copy * o.N1 + t.r0 + tid] = a;
+  }
+  __syncthreads();
+}
+
+// ---- slab store of staged accumulators ---------------------------------------------------------
+// A staged [8 * PASSES][LD] fp32 block of one wave -> rows r_base + [0, 8 * PASSES) of the slab: lane -> row
+// e * 8 + lane / 8, the 8 staged columns (lane % 8) * 8, which are the slab columns c .. c + 7.
+template <int PASSES, int LD, int UNROLL>
+__device__ __forceinline__ void tn_store(const TnOut& o, const float* stage, int split, int r_base, int c, int lane) {
   float* dst = o.slab + (long)split * o.slab_stride;
-#pragma unroll 1
-  for (int e = 0; e < 8; ++e) {
+#pragma unroll UNROLL
+  for (int e = 0; e < PASSES; ++e) {
     const int rw = e * 8 + (lane >> 3);
-    const int r = r_base + rw, c = c_base + (lane & 7) * 8;
+    const int r = r_base + rw;
     if (r >= o.N1 || c >= o.N2) continue;
-    const float* s = stage + rw * STAGE_LD + (lane & 7) * 8;
+    const float* s = stage + rw * LD + (lane & 7) * 8;
     float* d = dst + (long)r * o.N2 + c;
     *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
     *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(s + 4);
   }
 }
+
+// ---- transposed fragments ----------------------------------------------------------------------
+// MFMA operand: lane l holds column (l&31) of the 32-wide tile for k = 8*(l>>5) + j, j = 0..7.  ds_read_b64_tr_b16: in
+// each 16-lane group, lane r supplies the address of 4 contiguous elements of row (r>>2), columns 4*(r&3)..+3 of a
+// [4][16] block; lane i receives column i.  Two reads, four LDS rows apart, form one operand.
+template <int LD>
+__device__ __forceinline__ bf16x8 tn_tr_pair(const bf16raw* p) {
+  union { bf16x8 v; s16x4 h[2]; } u;
+  u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p));
+  u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(p + 4 * LD));
+  return u.v;
+}
+// The same as inline asm, for the kernels that keep LDS-DMA requests in flight: hipcc puts `s_waitcnt vmcnt(0)` in front of
+// every LDS read it emits itself while requests are outstanding (it cannot prove the read does not alias the DMA destination),
+// which drains the whole lookahead at the top of every load section -- measured: DMA-only 483 us + MFMA-only 486 us = 1047 us
+// for 150528x768x3072 instead of overlapping.  The price: the compiler does not count these reads either, so every load
+// section ends in an explicit lgkmcnt(0) and the fragments are pinned behind it before the MFMAs use them.
+typedef __attribute__((address_space(3))) char tn_lds_char;
+template <int OFF> __device__ inline s16x4 tn_tr_read(unsigned addr) {
+  s16x4 d;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
+  return d;
+}
+template <int OFF, int ROW4>     // byte offset of the first read; bytes of four LDS rows
+__device__ __forceinline__ bf16x8 tn_tr_frag(unsigned addr) {
+  union { bf16x8 v; s16x4 h[2]; } u;
+  u.h[0] = tn_tr_read<OFF>(addr);
+  u.h[1] = tn_tr_read<OFF + ROW4>(addr);
+  return u.v;
+}
+
+// ---- ragged-tile stager ------------------------------------------------------------------------
+// One operand's [ROWS][8 * CHUNKS] bf16 tile through registers, zero fill beyond m_end and beyond the operand's `ncols`
+// columns, 16-byte chunks XOR-ed with (row & 3) << 2 on the source side as the DMA does: thread -> rows
+// tid / CHUNKS + (THREADS / CHUNKS) * it, physical chunk tid % CHUNKS.
+template <int ROWS, int CHUNKS, int THREADS>
+__device__ __forceinline__ void tn_stage_ragged(bf16raw* dst, const bf16raw* __restrict__ src, long ld, const vtx_rowmap& map,
+                                                int mt, int m_end, int col0, int ncols, int tid) {
+  constexpr int RPP = THREADS / CHUNKS;
+#pragma unroll
+  for (int it = 0; it < ROWS / RPP; ++it) {
+    const int row = tid / CHUNKS + RPP * it;
+    const int lc = (tid % CHUNKS) ^ ((row & 3) << 2);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (mt + row < m_end && col0 + lc * 8 < ncols)
+      v = *reinterpret_cast<const uint4*>(src + map_row(map, mt + row) * ld + col0 + lc * 8);
+    *reinterpret_cast<uint4*>(dst + row * (8 * CHUNKS) + (tid % CHUNKS) * 8) = v;
+  }
+}
+
+// ---- the two register-staged kernels ----------------------------------------------------------
+// 128x128 output tile, 4 waves of 64x64, LDS tiles [m][128 n] filled through registers (the next tile's global loads are
+// in flight during the MFMAs):
+//   bf16: tiles [64 m][128 n], row stride 160 elements = 320 B so that the 4 rows x 64 B touched by each half-wave of
+//         ds_read_b64_tr_b16 fall in four disjoint bank quarters.  SAFE (tn_safe=1) selects plain 2-byte LDS gathers
+//         instead (slow, no dependence on the transpose instruction) -- kept as a diagnostic path.
+//   fp32: tiles [16 m][128 n]; v_mfma_f32_32x32x2_f32 takes one element per lane, read straight along the row
+//         (conflict free, no transpose needed).
+// They share the decode, the zeroing, the column sums, the fragment pair and the slab store with the other kernels and
+// keep one loader each: written as one body over an element policy the fp32 kernel measured 3 % slower than its parent
+// (profiles/tn_refactor_bench.txt), so the two bodies stay apart.
+constexpr int TN_BKM = 64;        // m rows per tile (bf16)
+constexpr int TN_LD = 160;        // padded row length (bf16 elements)
+constexpr int TN_BKM32 = 16;      // m rows per tile (fp32)
+constexpr int TN_LD32 = 128;
 
 template <bool SAFE>
 __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
@@ -58,12 +189,8 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
   bf16raw* Bs = As + TN_BKM * TN_LD;                       // [64][160]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
-  const int split = blockIdx.x / tiles12;
-  const int tile = blockIdx.x - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 128, c0 = t2 * 128;               // output tile origin (n1, n2)
-  const int m_begin = split * m_per_split;
-  const int m_end = min(M, m_begin + m_per_split);
+  const TnTile t = tn_tile<128, 128, false, false>(M, m_per_split, tiles2, tiles12);
+  const int split = t.split, t2 = t.t2, r0 = t.r0, c0 = t.c0, m_begin = t.m_begin, m_end = t.m_end;
 
   // loader: 64 rows x 16 chunks(16 B) = 1024 chunks -> 4 per thread per operand
   const int lc = tid & 15, lr = tid >> 4;
@@ -96,17 +223,9 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
   }
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  tn_zero(acc);
 
-  // Transposed fragment addressing.  MFMA operand: lane l holds column (l&31) of
-  // the 32-wide tile for k = 8*(l>>5) + j, j = 0..7.  ds_read_b64_tr_b16: in
-  // each 16-lane group, lane r supplies the address of 4 contiguous elements of
-  // row (r>>2), columns 4*(r&3)..+3 of a [4][16] block; lane i receives column i.
+  // transposed fragment addressing (see tn_tr_pair)
   const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
   const int tr_col = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
   const int sf_row = 8 * (lane >> 5);           // SAFE path: own column, 8 rows
@@ -119,14 +238,7 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
     TN_LSTORE16();
     if (do_cs) {
 #pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const uint32_t w[4] = {ra[it].x, ra[it].y, ra[it].z, ra[it].w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          csum[2 * j] += __uint_as_float(w[j] << 16);
-          csum[2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);
-        }
-      }
+      for (int it = 0; it < 4; ++it) tn_cs_add(csum, u32x4{ra[it].x, ra[it].y, ra[it].z, ra[it].w});
     }
     __syncthreads();
     if (mt + TN_BKM < m_end) TN_GLOAD16(mt + TN_BKM);
@@ -145,12 +257,7 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
         } else {
           const bf16raw* pa = As + (ks * 16 + tr_row) * TN_LD + wm * 64 + i * 32 + tr_col;
           const bf16raw* pb = Bs + (ks * 16 + tr_row) * TN_LD + wn * 64 + i * 32 + tr_col;
-          union { bf16x8 v; s16x4 h[2]; } ua, ub;
-          ua.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa));
-          ua.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa + 4 * TN_LD));
-          ub.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pb));
-          ub.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pb + 4 * TN_LD));
-          af[i] = ua.v; bfr[i] = ub.v;
+          af[i] = tn_tr_pair<TN_LD>(pa); bfr[i] = tn_tr_pair<TN_LD>(pb);
         }
       }
 #pragma unroll
@@ -163,22 +270,98 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
   }
   if (do_cs) {           // reduce the 16 row-lanes of every column chunk through LDS
     float* red = reinterpret_cast<float*>(smem);            // [16][128]
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[lr * 128 + lc * 8 + j] = csum[j];
-    __syncthreads();
-    if (tid < 128 && r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a += red[r * 128 + tid];
-      out.cslab[(long)split * out.slab_stride + r0 + tid] = a;
-    }
-    __syncthreads();
+    tn_cs_put<128>(red, lr, lc * 8, csum);
+    tn_cs_fold<16, 128>(red, out, t, 0, tid);
   }
   float* stage = reinterpret_cast<float*>(smem) + wave * 64 * STAGE_LD;
   stage_acc(stage, acc, lane);
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
-  tn_store(out, stage, split, r0 + wm * 64, c0 + wn * 64, lane);
+  tn_store<8, STAGE_LD, 1>(out, stage, split, r0 + wm * 64, c0 + wn * 64 + (lane & 7) * 8, lane);
+}
+
+__global__ __launch_bounds__(NT_THREADS) void gemm_tn_f32_kernel(
+    int M, int m_per_split, const float* __restrict__ A, long lda, vtx_rowmap amap,
+    const float* __restrict__ B, long ldb, vtx_rowmap bmap, int tiles2, int tiles12, TnOut out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  float* As = reinterpret_cast<float*>(smem);              // [16][128]
+  float* Bs = As + TN_BKM32 * TN_LD32;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1;
+  const TnTile t = tn_tile<128, 128, false, false>(M, m_per_split, tiles2, tiles12);
+  const int split = t.split, t2 = t.t2, r0 = t.r0, c0 = t.c0, m_begin = t.m_begin, m_end = t.m_end;
+
+  // loader: 16 rows x 32 float4 chunks = 512 chunks -> 2 per thread per operand
+  const int lc = tid & 31, lr = tid >> 5;
+  const bool a_col_ok = (r0 + lc * 4) < out.N1;
+  const bool b_col_ok = (c0 + lc * 4) < out.N2;
+  const int a_col = a_col_ok ? r0 + lc * 4 : 0;
+  const int b_col = b_col_ok ? c0 + lc * 4 : 0;
+  float4 ra[2], rb[2];
+  const float4 z4 = make_float4(0, 0, 0, 0);
+#define TN_GLOAD32(mt_)                                                                                        \
+  {                                                                                                            \
+    const int mt__ = (mt_);                                                                                    \
+    _Pragma("unroll") for (int it = 0; it < 2; ++it) {                                                         \
+      const int m = mt__ + lr + 8 * it;                                                                        \
+      const bool ok = m < m_end;                                                                               \
+      const int mc = m < M ? m : M - 1;                                                                        \
+      ra[it] = *reinterpret_cast<const float4*>(A + map_row(amap, mc) * lda + a_col);                          \
+      rb[it] = *reinterpret_cast<const float4*>(B + map_row(bmap, mc) * ldb + b_col);                          \
+      if (!(ok && a_col_ok)) ra[it] = z4;                                                                      \
+      if (!(ok && b_col_ok)) rb[it] = z4;                                                                      \
+    }                                                                                                          \
+  }
+#define TN_LSTORE32()                                                  \
+  {                                                                    \
+    _Pragma("unroll") for (int it = 0; it < 2; ++it) {                 \
+      const int off = (lr + 8 * it) * TN_LD32 + lc * 4;                \
+      *reinterpret_cast<float4*>(As + off) = ra[it];                   \
+      *reinterpret_cast<float4*>(Bs + off) = rb[it];                   \
+    }                                                                  \
+  }
+
+  f32x16 acc[2][2];
+  tn_zero(acc);
+
+  const int kh = lane >> 5, col = lane & 31;
+  const bool do_cs = out.cslab != nullptr && t2 == 0;
+  float csum[4] = {0, 0, 0, 0};
+  TN_GLOAD32(m_begin);
+  for (int mt = m_begin; mt < m_end; mt += TN_BKM32) {
+    TN_LSTORE32();
+    if (do_cs) {
+#pragma unroll
+      for (int it = 0; it < 2; ++it) { csum[0] += ra[it].x; csum[1] += ra[it].y; csum[2] += ra[it].z; csum[3] += ra[it].w; }
+    }
+    __syncthreads();
+    if (mt + TN_BKM32 < m_end) TN_GLOAD32(mt + TN_BKM32);
+#pragma unroll
+    for (int ks = 0; ks < TN_BKM32 / 2; ++ks) {
+      float af[2], bfr[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        af[i] = As[(ks * 2 + kh) * TN_LD32 + wm * 64 + i * 32 + col];
+        bfr[i] = Bs[(ks * 2 + kh) * TN_LD32 + wn * 64 + i * 32 + col];
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bfr[j], acc[i][j], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  if (do_cs) {
+    float* red = reinterpret_cast<float*>(smem);            // [8][128]
+    tn_cs_put<128>(red, lr, lc * 4, csum);
+    tn_cs_fold<8, 128>(red, out, t, 0, tid);
+  }
+  float* stage = reinterpret_cast<float*>(smem) + wave * 64 * STAGE_LD;
+  stage_acc(stage, acc, lane);
+  __builtin_amdgcn_s_waitcnt(0xc07f);
+  __builtin_amdgcn_wave_barrier();
+  tn_store<8, STAGE_LD, 1>(out, stage, split, r0 + wm * 64, c0 + wn * 64 + (lane & 7) * 8, lane);
 }
 
 // ---- bf16 with LDS-DMA staging -----------------------------------------------------------
@@ -187,10 +370,6 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_kernel(
 // touches in one ds_read_b64_tr_b16 fall into the four different 64-B bank quarters.  Full
 // 64-row tiles are staged by DMA into a double buffer; the (at most one) ragged last tile of a
 // split goes through registers with zero fill.
-__device__ inline void tn_dma16(const bf16raw* src, bf16raw* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 constexpr int TN_DLD = 128;   // elements per LDS row in the DMA layout
 
 __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
@@ -202,12 +381,8 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int split = blockIdx.x / tiles12;
-  const int tile = blockIdx.x - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 128, c0 = t2 * 128;
-  const int m_begin = split * m_per_split;
-  const int m_end = min(M, m_begin + m_per_split);
+  const TnTile t = tn_tile<128, 128, false, false>(M, m_per_split, tiles2, tiles12);
+  const int r0 = t.r0, c0 = t.c0, m_begin = t.m_begin, m_end = t.m_end;
 
   // DMA assignment: piece p = wave*4 + j covers tile rows 4p..4p+3; lane -> row 4p + (lane>>4), physical chunk lane&15
   const int prow = lane >> 4;                               // == row & 3
@@ -218,20 +393,15 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
   {                                                                                                   \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                   \
       const int m = (mt_) + (wave * 4 + j) * 4 + prow;                                                \
-      tn_dma16(A + map_row(amap, m) * lda + a_col, As + (buf_) * TN_BKM * TN_DLD + (wave * 4 + j) * 4 * TN_DLD); \
-      tn_dma16(B + map_row(bmap, m) * ldb + b_col, Bs + (buf_) * TN_BKM * TN_DLD + (wave * 4 + j) * 4 * TN_DLD); \
+      dma16(A + map_row(amap, m) * lda + a_col, As + (buf_) * TN_BKM * TN_DLD + (wave * 4 + j) * 4 * TN_DLD); \
+      dma16(B + map_row(bmap, m) * ldb + b_col, Bs + (buf_) * TN_BKM * TN_DLD + (wave * 4 + j) * 4 * TN_DLD); \
     }                                                                                                 \
   }
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  tn_zero(acc);
 
-  // transposed fragment addressing (see gemm_tn_bf16_kernel); row&3 == (lane&15)>>2 for both reads
+  // transposed fragment addressing (see tn_tr_pair); row&3 == (lane&15)>>2 for both reads
   const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
   const int tr_sw = ((lane & 15) >> 2) << 2;
   int a_off[2], b_off[2];
@@ -243,7 +413,7 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
     b_off[i] = tr_row * TN_DLD + (((cb >> 3) ^ tr_sw) << 3) + (cb & 7);
   }
   // column sums of A (bias gradient): thread owns logical chunk cs_chunk of rows (tid>>4) + 16*it
-  const bool do_cs = out.cslab != nullptr && t2 == 0;
+  const bool do_cs = out.cslab != nullptr && t.t2 == 0;
   const int cs_row = tid >> 4;
   const int cs_pc = tid & 15;
   const int cs_chunk = cs_pc ^ ((cs_row & 3) << 2);
@@ -252,21 +422,9 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
   const int n_full = (m_end - m_begin) > 0 ? (m_end - m_begin) / TN_BKM : 0;
   const int rem = (m_end - m_begin) > 0 ? (m_end - m_begin) - n_full * TN_BKM : 0;
   const int n_tiles = n_full + (rem ? 1 : 0);
-  // ragged tile loader (registers, zero fill): thread -> row tid>>4 + 16*it, physical chunk tid&15
   auto stage_ragged = [&](int buf, int mt) {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int row = (tid >> 4) + 16 * it;
-      const int m = mt + row;
-      const int lc = (tid & 15) ^ ((row & 3) << 2);
-      uint4 va = make_uint4(0, 0, 0, 0), vb = make_uint4(0, 0, 0, 0);
-      if (m < m_end) {
-        if (r0 + lc * 8 < out.N1) va = *reinterpret_cast<const uint4*>(A + map_row(amap, m) * lda + r0 + lc * 8);
-        if (c0 + lc * 8 < out.N2) vb = *reinterpret_cast<const uint4*>(B + map_row(bmap, m) * ldb + c0 + lc * 8);
-      }
-      *reinterpret_cast<uint4*>(As + buf * TN_BKM * TN_DLD + row * TN_DLD + (tid & 15) * 8) = va;
-      *reinterpret_cast<uint4*>(Bs + buf * TN_BKM * TN_DLD + row * TN_DLD + (tid & 15) * 8) = vb;
-    }
+    tn_stage_ragged<TN_BKM, 16, NT_THREADS>(As + buf * TN_BKM * TN_DLD, A, lda, amap, mt, m_end, r0, out.N1, tid);
+    tn_stage_ragged<TN_BKM, 16, NT_THREADS>(Bs + buf * TN_BKM * TN_DLD, B, ldb, bmap, mt, m_end, c0, out.N2, tid);
   };
   if (n_tiles > 0) {
     if (n_full > 0) { TN_STAGE_DMA(0, m_begin); } else { stage_ragged(0, m_begin); }
@@ -284,12 +442,7 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
 #pragma unroll
       for (int it = 0; it < 4; ++it) {
         const uint4 v = *reinterpret_cast<const uint4*>(Ab + (cs_row + 16 * it) * TN_DLD + cs_pc * 8);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          csum[2 * j] += __uint_as_float(w[j] << 16);
-          csum[2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);
-        }
+        tn_cs_add(csum, u32x4{v.x, v.y, v.z, v.w});
       }
     }
 #pragma unroll
@@ -297,14 +450,8 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
       bf16x8 af[2], bfr[2];
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        const bf16raw* pa = Ab + ks * 16 * TN_DLD + a_off[i];
-        const bf16raw* pb = Bb + ks * 16 * TN_DLD + b_off[i];
-        union { bf16x8 v; s16x4 h[2]; } ua, ub;
-        ua.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa));
-        ua.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pa + 4 * TN_DLD));
-        ub.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pb));
-        ub.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(pb + 4 * TN_DLD));
-        af[i] = ua.v; bfr[i] = ub.v;
+        af[i] = tn_tr_pair<TN_DLD>(Ab + ks * 16 * TN_DLD + a_off[i]);
+        bfr[i] = tn_tr_pair<TN_DLD>(Bb + ks * 16 * TN_DLD + b_off[i]);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i)
@@ -317,40 +464,21 @@ __global__ __launch_bounds__(NT_THREADS) void gemm_tn_bf16_dma_kernel(
 #undef TN_STAGE_DMA
   if (do_cs) {
     float* red = reinterpret_cast<float*>(smem);            // [16][128]
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[cs_row * 128 + cs_chunk * 8 + j] = csum[j];
-    __syncthreads();
-    if (tid < 128 && r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a += red[r * 128 + tid];
-      out.cslab[(long)split * out.slab_stride + r0 + tid] = a;
-    }
-    __syncthreads();
+    tn_cs_put<128>(red, cs_row, cs_chunk * 8, csum);
+    tn_cs_fold<16, 128>(red, out, t, 0, tid);
   }
   float* stage = reinterpret_cast<float*>(smem) + wave * 64 * STAGE_LD;
   stage_acc(stage, acc, lane);
   __builtin_amdgcn_s_waitcnt(0xc07f);
   __builtin_amdgcn_wave_barrier();
-  tn_store(out, stage, split, r0 + wm * 64, c0 + wn * 64, lane);
+  tn_store<8, STAGE_LD, 1>(out, stage, t.split, r0 + wm * 64, c0 + wn * 64 + (lane & 7) * 8, lane);
 }
 
 // ---- bf16, 256x128 output tile, LDS-DMA ring with counted vmcnt ----------------------------
 // Mirror of gemm_nt's <4,3,32> ring: 8 waves (4x2, each 64x64), 32 token rows per stage
 // (A [32][256] + B [32][128] bf16 = 24 KB), 3 stages = 72 KB -> two workgroups per CU.  Chunk
 // swizzle ^((row&3)<<2) on the DMA source side keeps the transpose reads conflict free.
-// Transpose reads are issued as inline asm: hipcc puts `s_waitcnt vmcnt(0)` in front of every LDS read it emits itself
-// while LDS-DMA requests are outstanding (it cannot prove the read does not alias the DMA destination), which drains
-// the whole lookahead at the top of every load section -- measured: DMA-only 483 us + MFMA-only 486 us = 1047 us for
-// 150528x768x3072 instead of overlapping.  The price: the compiler does not count these reads either, so every load
-// section ends in an explicit lgkmcnt(0) and the fragments are pinned behind it (TP_PIN) before the MFMAs use them.
-typedef __attribute__((address_space(3))) char tn_lds_char;
-template <int OFF> __device__ inline s16x4 tn_tr_read(unsigned addr) {
-  s16x4 d;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(d) : "v"(addr), "n"(OFF) : "memory");
-  return d;
-}
-template <int N> __device__ inline void tn_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// Transpose reads are inline asm (tn_tr_frag, see there).
 constexpr int TR_BKM = 32, TR_NBUF = 3, TR_A_LD = 256, TR_B_LD = 128;
 constexpr int TR_STAGE = TR_BKM * (TR_A_LD + TR_B_LD);      // elements per stage
 
@@ -362,13 +490,8 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_bf16_ring_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);          // split-major runs per XCD (see the pp kernel)
-  const int split = bid / tiles12;
-  const int tile = bid - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 256, c0 = t2 * 128;
-  const int m_begin = split * m_per_split;
-  const int m_end = min(M, m_begin + m_per_split);
+  const TnTile t = tn_tile<256, 128, true, false>(M, m_per_split, tiles2, tiles12);
+  const int t2 = t.t2, r0 = t.r0, c0 = t.c0, m_begin = t.m_begin, m_end = t.m_end;
 
   // DMA: A piece = 2 rows x 512 B (lane -> row lane>>5, physical chunk lane&31), 2 pieces per wave;
   //      B piece = 4 rows x 256 B (lane -> row lane>>4, physical chunk lane&15), 1 piece per wave.
@@ -390,40 +513,18 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_bf16_ring_kernel(
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int row = (wave * 2 + j) * 2 + a_prow;
-      tn_dma16(A + map_row(amap, mt + row) * lda + a_col[j], Ab + (wave * 2 + j) * 512);
+      dma16(A + map_row(amap, mt + row) * lda + a_col[j], Ab + (wave * 2 + j) * 512);
     }
-    tn_dma16(B + map_row(bmap, mt + b_row) * ldb + b_col, Bb + wave * 512);
+    dma16(B + map_row(bmap, mt + b_row) * ldb + b_col, Bb + wave * 512);
   };
-  // ragged tile (registers, zero fill)
   auto stage_ragged = [&](int buf, int mt) {
     bf16raw* Ab = ring + buf * TR_STAGE;
-    bf16raw* Bb = Ab + TR_BKM * TR_A_LD;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int row = (tid >> 5) + 16 * it;
-      const int lc = (tid & 31) ^ ((row & 3) << 2);
-      uint4 va = make_uint4(0, 0, 0, 0);
-      if (mt + row < m_end && r0 + lc * 8 < out.N1)
-        va = *reinterpret_cast<const uint4*>(A + map_row(amap, mt + row) * lda + r0 + lc * 8);
-      *reinterpret_cast<uint4*>(Ab + row * TR_A_LD + (tid & 31) * 8) = va;
-    }
-    {
-      const int row = tid >> 4;
-      const int lc = (tid & 15) ^ ((row & 3) << 2);
-      uint4 vb = make_uint4(0, 0, 0, 0);
-      if (mt + row < m_end && c0 + lc * 8 < out.N2)
-        vb = *reinterpret_cast<const uint4*>(B + map_row(bmap, mt + row) * ldb + c0 + lc * 8);
-      *reinterpret_cast<uint4*>(Bb + row * TR_B_LD + (tid & 15) * 8) = vb;
-    }
+    tn_stage_ragged<TR_BKM, TR_A_LD / 8, 512>(Ab, A, lda, amap, mt, m_end, r0, out.N1, tid);
+    tn_stage_ragged<TR_BKM, TR_B_LD / 8, 512>(Ab + TR_BKM * TR_A_LD, B, ldb, bmap, mt, m_end, c0, out.N2, tid);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  tn_zero(acc);
   const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
   const int tr_sw = ((lane & 15) >> 2) << 2;
   int a_off[2], b_off[2];
@@ -456,7 +557,7 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_bf16_ring_kernel(
       stage_ragged(buf, m_begin + ti * TR_BKM);
       __builtin_amdgcn_s_waitcnt(0xc07f);                                // ds_writes visible before the raw barrier
     }
-    if (ti + TR_NBUF - 2 < n_full) tn_wait_vmcnt<3 * (TR_NBUF - 2)>(); else tn_wait_vmcnt<0>();
+    if (ti + TR_NBUF - 2 < n_full) wait_vmcnt<3 * (TR_NBUF - 2)>(); else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
     {
       const int nxt = ti + TR_NBUF - 1;
@@ -470,23 +571,16 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_bf16_ring_kernel(
       u32x4 v_[2];
       asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:8192\n\ts_waitcnt lgkmcnt(0)"
                    : "=&v"(v_[0]), "=&v"(v_[1]) : "v"(stage_b + 2u * (cs_row * TR_A_LD + cs_pc * 8)) : "memory");
-#pragma unroll
-      for (int it = 0; it < 2; ++it)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          csum[2 * j] += __uint_as_float(v_[it][j] << 16);
-          csum[2 * j + 1] += __uint_as_float(v_[it][j] & 0xffff0000u);
-        }
+      tn_cs_add(csum, v_[0]);
+      tn_cs_add(csum, v_[1]);
     }
-    // per 16-deep k step: 8 transpose reads (inline asm: see tn_tr_read), an explicit wait that pins the fragments, 4 MFMAs
+    // per 16-deep k step: 8 transpose reads (inline asm: see tn_tr_frag), an explicit wait that pins the fragments, 4 MFMAs
 #define TR_KSTEP(KA_, KB_)                                                                               \
     {                                                                                                    \
       bf16x8 af[2], bfr[2];                                                                              \
       _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                    \
-        const unsigned pa = stage_b + 2u * a_off[i], pb = stage_b + 2u * (TR_BKM * TR_A_LD + b_off[i]);  \
-        union { bf16x8 v; s16x4 h[2]; } u_;                                                              \
-        u_.h[0] = tn_tr_read<KA_>(pa); u_.h[1] = tn_tr_read<KA_ + 2048>(pa); af[i] = u_.v;               \
-        u_.h[0] = tn_tr_read<KB_>(pb); u_.h[1] = tn_tr_read<KB_ + 1024>(pb); bfr[i] = u_.v;              \
+        af[i] = tn_tr_frag<KA_, 8 * TR_A_LD>(stage_b + 2u * a_off[i]);                                   \
+        bfr[i] = tn_tr_frag<KB_, 8 * TR_B_LD>(stage_b + 2u * (TR_BKM * TR_A_LD + b_off[i]));             \
       }                                                                                                  \
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(af[0]), "+v"(af[1]), "+v"(bfr[0]), "+v"(bfr[1]));       \
       _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int j = 0; j < 2; ++j)        \
@@ -500,34 +594,16 @@ __global__ __launch_bounds__(512, 4) void gemm_tn_bf16_ring_kernel(
   __syncthreads();
   if (want_cs) {
     float* red = reinterpret_cast<float*>(smem);            // [16][256]
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[cs_row * 256 + cs_chunk * 8 + j] = csum[j];
-    __syncthreads();
-    if (tid < 256 && r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a += red[r * 256 + tid];
-      out.cslab[(long)split * out.slab_stride + (long)t2 * out.N1 + r0 + tid] = a;
-    }
-    __syncthreads();
+    tn_cs_put<256>(red, cs_row, cs_chunk * 8, csum);
+    tn_cs_fold<16, 256>(red, out, t, t2, tid);
   }
   float* stg = reinterpret_cast<float*>(smem) + wave * 32 * STAGE_LD;
-  float* dst = out.slab + (long)split * out.slab_stride;
 #pragma unroll
-  for (int mi = 0; mi < 2; ++mi) {
+  for (int mi = 0; mi < 2; ++mi) {              // 32-row halves: half the staging, two workgroups per CU
     stage_acc_half(stg, acc[mi], lane);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
-    for (int e = 0; e < 4; ++e) {
-      const int rw = e * 8 + (lane >> 3);
-      const int r = r0 + wm * 64 + mi * 32 + rw, c = c0 + wn * 64 + (lane & 7) * 8;
-      if (r >= out.N1 || c >= out.N2) continue;
-      const float* sp = stg + rw * STAGE_LD + (lane & 7) * 8;
-      float* d = dst + (long)r * out.N2 + c;
-      *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(sp);
-      *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(sp + 4);
-    }
+    tn_store<4, STAGE_LD, 1>(out, stg, t.split, r0 + wm * 64 + mi * 32, c0 + wn * 64 + (lane & 7) * 8, lane);
     __builtin_amdgcn_s_waitcnt(0xc07f);
     __builtin_amdgcn_wave_barrier();
   }
@@ -554,7 +630,142 @@ constexpr int TP_RING_BYTES = 2 * TP_BUF * 2;    // 131072
 constexpr int TP_STG_LD = 64;
 constexpr int TP_LDS_BYTES = TP_RING_BYTES + 8 * 16 * TP_STG_LD * 4;
 
-__device__ inline void tp_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+// ---- the LDS-DMA feeder of the two 256x256 kernels ----------------------------------------------
+// A region is two sub-blocks of [64 token rows][64 columns] (128-B rows), one per column half.
+// DMA: piece p = 8 token rows x 128 B of sub-block p/8 (the same request shape as gemm_nt's: one full
+// line per row); a wave owns the PPW pieces PPW*wave .. PPW*wave + PPW - 1 (2 with 8 waves, 4 with 4: 16 per region).
+// lane -> row 8*(p%8) + lane/8, physical chunk lane%8, logical chunk = physical ^ (((row>>1)&1)<<2): rows r, r+2 swap
+// 64-B halves, which puts the four rows a transpose read touches in one LDS cycle on four disjoint bank quarters.
+// The wave's pieces are rows prow0 + 8 j of the same sub-block (PPW*wave is a multiple of PPW, so the next PPW - 1 pieces
+// do not leave the sub-block) and (prow >> 1) & 1 is the same for all of them: ONE column offset per operand serves every
+// piece and both region halves (+64 for A1, +128 for B1).
+// Row maps without a division per DMA: phys(m) = base + m + (m / grp) * skip.  Every region kind is requested for K
+// tiles 0, 1, 2, ... in order, so the state of its NEXT request lives in SGPRs and is stepped by one tile after each
+// request (`advance`, pure SALU, called from the following load section): the scalar byte address of the tile's first
+// row (column origin included), how many of its 64 rows come before the next row-map group (`crs`, >= 64: all) and
+// how many are inside M (`vld`).  The request itself (`issue_piece`, which sits between the MFMAs of an MMA section) is
+// branch-free: per piece a lane picks one of two scalar row addresses (this group / the next one) and one of two
+// constant offsets (its own row / row 0 of the tile for rows beyond M, which are zeroed in LDS afterwards) -- about a
+// dozen VALU instructions per region.  It used to be ~100 instructions of per-lane 64-bit address arithmetic and
+// branches, which made every MMA section 2.3x as long as its 8 MFMAs (tools/tn_timeline.py: 600 cycles).
+constexpr int TP_FAR = 1 << 28;     // `crs` of a map without groups
+template <int PPW>
+struct TnFeeder {
+  bf16raw* lds;
+  int wave, lane, last_valid;
+  long lda, ldb;
+  int grp_a, grp_b;
+  int prow0, rc, acol_l;          // first piece's row; region column 0..127; lane part of the A column (the tile origin r0 is scalar)
+  unsigned voff_a, voff_b;        // per-lane byte offsets of piece 0 from the (scalar) address of the K tile's first row; piece j = 8 j rows further
+  int trm[4], crs[4], vld[4];     // per region kind (0 = A0, 1 = B0, 2 = B1, 3 = A1): rows into the row-map group, rows before the next, rows inside M
+  const char* sp[4];
+  long step64_a, step64_b;        // bytes per K tile
+  long skipb_a, skipb_b;          // bytes per row-map group crossing
+
+  __device__ __forceinline__ TnFeeder(bf16raw* lds_, int wave_, int lane_, const bf16raw* A, long lda_, const vtx_rowmap& amap,
+                                      const bf16raw* B, long ldb_, const vtx_rowmap& bmap, int M, const TnTile& t, int last_valid_)
+      : lds(lds_), wave(wave_), lane(lane_), last_valid(last_valid_), lda(lda_), ldb(ldb_), grp_a(amap.grp), grp_b(bmap.grp) {
+    const int pc0 = wave * PPW, sub = pc0 >> 3;
+    prow0 = (pc0 & 7) * 8 + (lane >> 3);
+    rc = sub * 64 + ((lane & 7) ^ (((prow0 >> 1) & 1) << 2)) * 8;
+    acol_l = (rc >> 6) * 128 + (rc & 63);        // A1: + 64.  B column = c0 + rc (B1: + 128)
+    voff_a = 2u * (unsigned)(prow0 * (int)lda + acol_l); voff_b = 2u * (unsigned)(prow0 * (int)ldb + rc);
+    step64_a = 2L * TP_BK * lda; step64_b = 2L * TP_BK * ldb;
+    skipb_a = 2L * amap.skip * lda; skipb_b = 2L * bmap.skip * ldb;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool isA = k == 0 || k == 3;
+      const vtx_rowmap& mp = isA ? amap : bmap;
+      const int g = mp.grp;
+      const int q = g > 0 ? t.m_begin / g : 0;
+      trm[k] = g > 0 ? t.m_begin - q * g : 0;
+      crs[k] = g > 0 ? g - trm[k] : TP_FAR;
+      vld[k] = M - t.m_begin;
+      const long phys0 = (long)mp.base + t.m_begin + (long)q * mp.skip;
+      sp[k] = reinterpret_cast<const char*>(isA ? A + phys0 * lda + t.r0 + (k == 3 ? 64 : 0) : B + phys0 * ldb + t.c0 + (k == 2 ? 128 : 0));
+    }
+  }
+  __device__ __forceinline__ bf16raw* piece(int kind, int kt, int j) const {
+    return lds + (kt & 1) * TP_BUF + kind * TP_REGION + wave * (PPW * 512) + j * 512;
+  }
+  __device__ __forceinline__ void issue_piece(int kind, int kt, int j) {   // piece j of this wave
+    bf16raw* dst = piece(kind, kt, j);
+    const bool isA = kind == 0 || kind == 3;
+    const char* lo = sp[kind];
+    const char* hi = lo + (isA ? skipb_a : skipb_b);
+    const unsigned vo = isA ? voff_a : voff_b, vc = 2u * (unsigned)(isA ? acol_l : rc);
+    const unsigned step8 = 16u * (unsigned)(isA ? lda : ldb);
+    const int row = prow0 + 8 * j;
+    // Regular K tile (all 64 rows before the next row-map group and inside M -- a scalar test; all but one tile in
+    // ~24 of the spatial / temporal row maps and every tile of the identity map): scalar base + the lane's constant
+    // offset, i.e. the request is `s_mov m0` + one saddr-form DMA instruction and fits an MFMA gap.  The general
+    // form below is a dozen dependent vector instructions per piece: two of them per MMA section stretched it by a
+    // third (tools/tn_timeline.py: 500 cycles for 8 MFMAs).
+    if (crs[kind] >= TP_BK && vld[kind] >= TP_BK) {
+      // (inline asm: written with the builtin, hipcc merges this branch with the general one below and the request is
+      // again a per-lane 64-bit address built from a dozen instructions)
+      const unsigned m0v = (unsigned)(unsigned long)(tn_lds_char*)dst;
+      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
+                   :: "v"(vo + j * step8), "s"(lo), "s"(m0v) : "memory", "m0");
+      return;
+    }
+    const char* base = row >= crs[kind] ? hi : lo;
+    const unsigned o = row < vld[kind] ? vo + j * step8 : vc;
+    dma16(reinterpret_cast<const bf16raw*>(base + o), dst);
+  }
+  __device__ __forceinline__ void issue(int kind, int kt) {
+#pragma unroll
+    for (int j = 0; j < PPW; ++j) issue_piece(kind, kt, j);
+  }
+  __device__ __forceinline__ void advance(int kind) {     // step the request state of `kind` to its next K tile
+    const bool isA = kind == 0 || kind == 3;
+    const int g = isA ? grp_a : grp_b;
+    sp[kind] += isA ? step64_a : step64_b;
+    vld[kind] -= TP_BK;
+    if (g > 0) {
+      trm[kind] += TP_BK;
+      if (trm[kind] >= g) { trm[kind] -= g; sp[kind] += isA ? skipb_a : skipb_b; }
+      crs[kind] = g - trm[kind];
+    }
+  }
+  __device__ __forceinline__ void zero_tail(int kt) {     // rows >= last_valid of tile kt (this wave's own pieces)
+#pragma unroll
+    for (int kind = 0; kind < 4; ++kind)
+#pragma unroll
+      for (int j = 0; j < PPW; ++j)
+        if (prow0 + 8 * j >= last_valid) *reinterpret_cast<uint4*>(piece(kind, kt, j) + lane * 8) = make_uint4(0, 0, 0, 0);
+  }
+};
+
+// Column sums of the two 256x256 kernels: which 16-byte words of an A region a thread sums.  Thread -> sub-block
+// tid / (8 R), physical chunk tid % 8 of rows (tid / 8) % R + {0, R, 2R, ..} (R = 32 with 512 threads, 16 with 256; the rows
+// share bit 1, so the chunk's swizzle is the same for all of them).
+template <int R>
+struct TnCsLane {
+  unsigned sub, row, pc;
+  __device__ __forceinline__ explicit TnCsLane(unsigned tid) : sub(tid / (8 * R)), row((tid >> 3) & (R - 1)), pc(tid & 7) {}
+  // element offset of the first word inside a region
+  __device__ __forceinline__ unsigned lds_off() const { return sub * 4096 + row * 64 + pc * 8; }
+  // tile column of that word in A0: logical chunk pc ^ (((row >> 1) & 1) << 2) of sub-block `sub` = tile columns
+  // sub * 128 + [0, 64); the A1 word is 64 columns further
+  __device__ __forceinline__ int tile_col() const { return sub * 128 + (pc ^ (((row >> 1) & 1) << 2)) * 8; }
+};
+
+// One 16-row pass of the 256x256 kernels' epilogue: half HALF of the accumulator pair (a0 | a1) -- 16 rows x 64 columns
+// -- through the wave's [16][TP_STG_LD] staging block to slab rows r_base + [0, 16), the lane's 8 columns at c.
+template <int HALF>
+__device__ __forceinline__ void tn_epi16(const TnOut& o, float* stg, const f32x16& a0, const f32x16& a1, int split, int r_base, int c, int lane) {
+  const int col = lane & 31, rhalf = (lane >> 5) * 4;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) stg[((r & 3) + 8 * (r >> 2) + rhalf) * TP_STG_LD + col] = a0[8 * HALF + r];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) stg[((r & 3) + 8 * (r >> 2) + rhalf) * TP_STG_LD + 32 + col] = a1[8 * HALF + r];
+  lgkm0();
+  __builtin_amdgcn_wave_barrier();
+  tn_store<2, TP_STG_LD, 2>(o, stg, split, r_base, c, lane);
+  lgkm0();
+  __builtin_amdgcn_wave_barrier();
+}
 
 template <bool TRACE>
 __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
@@ -573,115 +784,15 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
         trace[((long)blockIdx.x * 8 + trace_kt) * 24 + e] = (long long)__builtin_amdgcn_s_memtime();
     }
   };
-  // XCD-aware order: the tiles of one split read the same token rows, so give every XCD a contiguous
-  // run of the split-major work list (its L2 then serves each A / B row to all the tiles that need it;
-  // round-robin placement re-fetches every panel once per XCD: 1.85 GB instead of 0.39 GB at 768x3072)
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = bid / tiles12;
-  const int tile = bid - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 256, c0 = t2 * 256;
-  const int m_begin = split * m_per_split;
-  const int m_end = (split == (int)(gridDim.x / tiles12) - 1) ? M : m_begin + m_per_split;   // last split: + remainder
-  const int span = m_end - m_begin;
+  const TnTile t = tn_tile<256, 256, true, true>(M, m_per_split, tiles2, tiles12);
+  const int t2 = t.t2, r0 = t.r0, c0 = t.c0;
+  const int span = t.m_end - t.m_begin;
   const int nk = (span + TP_BK - 1) / TP_BK;      // >= 2 (host guarantees m_per_split >= 128)
   const int last_valid = span - (nk - 1) * TP_BK; // rows of the last tile that are inside the span
-
-  // A region is two sub-blocks of [64 token rows][64 columns] (128-B rows), one per column half.
-  // DMA: piece p = 8 token rows x 128 B of sub-block p/8 (the same request shape as gemm_nt's: one full
-  // line per row); this wave owns pieces 2*wave, 2*wave+1.  lane -> row 8*(p%8) + lane/8, physical
-  // chunk lane%8, logical chunk = physical ^ (((row>>1)&1)<<2): rows r, r+2 swap 64-B halves, which puts
-  // the four rows a transpose read touches in one LDS cycle on four disjoint bank quarters.
-  // The wave's two pieces are rows prow0 and prow0 + 8 of the same sub-block (2*wave is even, so 2*wave + 1 does not
-  // leave the sub-block) and (prow >> 1) & 1 is the same for both: ONE column offset per operand serves both pieces
-  // and both region halves (+64 for A1, +128 for B1).
-  const int pc0 = wave * 2, sub = pc0 >> 3;
-  const int prow0 = (pc0 & 7) * 8 + (lane >> 3);
-  const int rc = sub * 64 + ((lane & 7) ^ (((prow0 >> 1) & 1) << 2)) * 8;   // region column 0..127
-  const int acol_l = (rc >> 6) * 128 + (rc & 63);        // lane part of the A column (tile origin r0 is added as a scalar); A1: + 64
-  // B column = c0 + rc (B1: + 128): wave wc owns columns wc*32+[0,32) of each half
-  // per-lane byte offsets of piece 0 from the (scalar) address of the K tile's first row; piece 1 = 8 rows further
-  const unsigned voff_a = 2u * (unsigned)(prow0 * (int)lda + acol_l), voff_b = 2u * (unsigned)(prow0 * (int)ldb + rc);
-  // Row maps without a division per DMA: phys(m) = base + m + (m / grp) * skip.  Every region kind is requested for K
-  // tiles 0, 1, 2, ... in order, so the state of its NEXT request lives in SGPRs and is stepped by one tile after each
-  // request (`advance`, pure SALU, called from the following load section): the scalar byte address of the tile's first
-  // row (column origin included), how many of its 64 rows come before the next row-map group (`crs`, >= 64: all) and
-  // how many are inside M (`vld`).  The request itself (`issue`, which sits between the MFMAs of an MMA section) is
-  // branch-free: per piece a lane picks one of two scalar row addresses (this group / the next one) and one of two
-  // constant offsets (its own row / row 0 of the tile for rows beyond M, which are zeroed in LDS afterwards) -- about a
-  // dozen VALU instructions per region.  It used to be ~100 instructions of per-lane 64-bit address arithmetic and
-  // branches, which made every MMA section 2.3x as long as its 8 MFMAs (tools/tn_timeline.py: 600 cycles).
-  int trm[4], crs[4], vld[4];
-  const char* sp[4];
-  const long step64_a = 2L * TP_BK * lda, step64_b = 2L * TP_BK * ldb;          // bytes per K tile
-  const long skipb_a = 2L * amap.skip * lda, skipb_b = 2L * bmap.skip * ldb;    // bytes per row-map group crossing
-  constexpr int TP_FAR = 1 << 28;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool isA = k == 0 || k == 3;
-    const vtx_rowmap& mp = isA ? amap : bmap;
-    const int g = mp.grp;
-    const int q = g > 0 ? m_begin / g : 0;
-    trm[k] = g > 0 ? m_begin - q * g : 0;
-    crs[k] = g > 0 ? g - trm[k] : TP_FAR;
-    vld[k] = M - m_begin;
-    const long phys0 = (long)mp.base + m_begin + (long)q * mp.skip;
-    sp[k] = reinterpret_cast<const char*>(isA ? A + phys0 * lda + r0 + (k == 3 ? 64 : 0) : B + phys0 * ldb + c0 + (k == 2 ? 128 : 0));
-  }
-  auto issue_piece = [&](int kind, int kt, int j) {   // kind: 0 = A0, 1 = B0, 2 = B1, 3 = A1; piece j of this wave
-    bf16raw* dst = lds + (kt & 1) * TP_BUF + kind * TP_REGION + wave * 1024;
-    const bool isA = kind == 0 || kind == 3;
-    const char* lo = sp[kind];
-    const char* hi = lo + (isA ? skipb_a : skipb_b);
-    const unsigned vo = isA ? voff_a : voff_b, vc = 2u * (unsigned)(isA ? acol_l : rc);
-    const unsigned step8 = 16u * (unsigned)(isA ? lda : ldb);
-    const int row = prow0 + 8 * j;
-    // Regular K tile (all 64 rows before the next row-map group and inside M -- a scalar test; all but one tile in
-    // ~24 of the spatial / temporal row maps and every tile of the identity map): scalar base + the lane's constant
-    // offset, i.e. the request is `s_mov m0` + one saddr-form DMA instruction and fits an MFMA gap.  The general
-    // form below is a dozen dependent vector instructions per piece: two of them per MMA section stretched it by a
-    // third (tools/tn_timeline.py: 500 cycles for 8 MFMAs).
-    if (crs[kind] >= TP_BK && vld[kind] >= TP_BK) {
-      // (inline asm: written with the builtin, hipcc merges this branch with the general one below and the request is
-      // again a per-lane 64-bit address built from a dozen instructions)
-      const unsigned m0v = (unsigned)(unsigned long)(tn_lds_char*)(dst + j * 512);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                   :: "v"(vo + j * step8), "s"(lo), "s"(m0v) : "memory", "m0");
-      return;
-    }
-    const char* base = row >= crs[kind] ? hi : lo;
-    const unsigned o = row < vld[kind] ? vo + j * step8 : vc;
-    tn_dma16(reinterpret_cast<const bf16raw*>(base + o), dst + j * 512);
-  };
-  auto issue = [&](int kind, int kt) { issue_piece(kind, kt, 0); issue_piece(kind, kt, 1); };
-  auto advance = [&](int kind) {                  // step the request state of `kind` to its next K tile
-    const bool isA = kind == 0 || kind == 3;
-    const int g = isA ? amap.grp : bmap.grp;
-    sp[kind] += isA ? step64_a : step64_b;
-    vld[kind] -= TP_BK;
-    if (g > 0) {
-      trm[kind] += TP_BK;
-      if (trm[kind] >= g) { trm[kind] -= g; sp[kind] += isA ? skipb_a : skipb_b; }
-      crs[kind] = g - trm[kind];
-    }
-  };
-  auto zero_tail = [&](int kt) {                  // rows >= last_valid of tile kt (this wave's own pieces)
-#pragma unroll
-    for (int kind = 0; kind < 4; ++kind)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        if (prow0 + 8 * j >= last_valid)
-          *reinterpret_cast<uint4*>(lds + (kt & 1) * TP_BUF + kind * TP_REGION + wave * 1024 + j * 512 + lane * 8) =
-              make_uint4(0, 0, 0, 0);
-  };
+  TnFeeder<2> fd(lds, wave, lane, A, lda, amap, B, ldb, bmap, M, t, last_valid);
 
   f32x16 acc[4][2];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  tn_zero(acc);
 
   // transposed fragment addressing inside a region: token row ks*16 + tr_row (+4), column c
   const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
@@ -699,51 +810,36 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
   }
   const unsigned lds_b = (unsigned)(unsigned long)(tn_lds_char*)smem;
   const unsigned fa_addr[2] = {lds_b + 2u * fa_off[0], lds_b + 2u * fa_off[1]}, fb_addr = lds_b + 2u * fb_off;
-  // column sums: thread -> sub-block tid>>8, physical chunk tid&7 of rows (tid>>3)&31 and +32
+  // column sums: two rows, 32 apart, per thread and region (TnCsLane<32>)
   const bool want_cs = out.cslab != nullptr;
   bool do_cs = false;                              // this K tile is one of ours
   int cs_next = t2;                                // next K tile whose A regions this workgroup sums
-  const int cs_sub = tid >> 8, cs_row = (tid >> 3) & 31, cs_pc = tid & 7;
   float cs0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define TP_COLSUM(buf_, kind_, cs_)                                                                      \
   if (do_cs) {                                                                                           \
     u32x4 v_[2];                                                                                         \
     /* the address is rebuilt from the thread index here: kept live across the loop it is spilled, and a scratch reload \
-       waits for vmcnt(0), i.e. for the whole DMA look-ahead */                                          \
+       waits for vmcnt(0), i.e. for the whole DMA look-ahead.  It is TnCsLane<32>::lds_off() spelled out: through \
+       the struct the trace instantiation spills one more scalar register */                             \
     unsigned t_ = threadIdx.x;                                                                           \
     asm volatile("" : "+v"(t_));                                                                         \
     const unsigned ca_ = lds_b + 2u * ((t_ >> 8) * 4096 + ((t_ >> 3) & 31) * 64 + (t_ & 7) * 8);        \
     asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:4096\n\ts_waitcnt lgkmcnt(0)"        \
                  : "=&v"(v_[0]), "=&v"(v_[1]) : "v"(ca_ + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION)) : "memory"); \
-    _Pragma("unroll") for (int it = 0; it < 2; ++it) _Pragma("unroll") for (int j = 0; j < 4; ++j) {     \
-      cs_[2 * j] += __uint_as_float(v_[it][j] << 16);                                                    \
-      cs_[2 * j + 1] += __uint_as_float(v_[it][j] & 0xffff0000u);                                        \
-    }                                                                                                    \
+    tn_cs_add(cs_, v_[0]);                                                                               \
+    tn_cs_add(cs_, v_[1]);                                                                               \
   }
+// fragments of a region: k step Q at byte offset Q * 2048 (16 rows of 128 B), the pair's second read four rows on
 #define TP_READ_A(buf_, kind_)                                                                           \
   _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                        \
     const unsigned a_ = fa_addr[i] + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION);                       \
-    union { bf16x8 v; s16x4 h[2]; } u_;                                                                  \
-    u_.h[0] = tn_tr_read<0>(a_);    u_.h[1] = tn_tr_read<512>(a_);         fa[i][0] = u_.v;              \
-    u_.h[0] = tn_tr_read<2048>(a_); u_.h[1] = tn_tr_read<2048 + 512>(a_);  fa[i][1] = u_.v;              \
-    u_.h[0] = tn_tr_read<4096>(a_); u_.h[1] = tn_tr_read<4096 + 512>(a_);  fa[i][2] = u_.v;              \
-    u_.h[0] = tn_tr_read<6144>(a_); u_.h[1] = tn_tr_read<6144 + 512>(a_);  fa[i][3] = u_.v;              \
-  }
-#define TP_READ_B(buf_, kind_, fb_)                                                                      \
-  {                                                                                                      \
-    const unsigned a_ = fb_addr + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION);                          \
-    union { bf16x8 v; s16x4 h[2]; } u_;                                                                  \
-    u_.h[0] = tn_tr_read<0>(a_);    u_.h[1] = tn_tr_read<512>(a_);         fb_[0] = u_.v;                \
-    u_.h[0] = tn_tr_read<2048>(a_); u_.h[1] = tn_tr_read<2048 + 512>(a_);  fb_[1] = u_.v;                \
-    u_.h[0] = tn_tr_read<4096>(a_); u_.h[1] = tn_tr_read<4096 + 512>(a_);  fb_[2] = u_.v;                \
-    u_.h[0] = tn_tr_read<6144>(a_); u_.h[1] = tn_tr_read<6144 + 512>(a_);  fb_[3] = u_.v;                \
+    fa[i][0] = tn_tr_frag<0, 512>(a_);    fa[i][1] = tn_tr_frag<2048, 512>(a_);                          \
+    fa[i][2] = tn_tr_frag<4096, 512>(a_); fa[i][3] = tn_tr_frag<6144, 512>(a_);                          \
   }
 #define TP_READ_B_Q(buf_, kind_, fb_, Q_)                                                                \
-  {                                                                                                      \
-    const unsigned a_ = fb_addr + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION);                          \
-    union { bf16x8 v; s16x4 h[2]; } u_;                                                                  \
-    u_.h[0] = tn_tr_read<(Q_) * 2048>(a_); u_.h[1] = tn_tr_read<(Q_) * 2048 + 512>(a_); fb_[Q_] = u_.v;  \
-  }
+  fb_[Q_] = tn_tr_frag<(Q_) * 2048, 512>(fb_addr + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION))
+#define TP_READ_B(buf_, kind_, fb_)                                                                      \
+  { TP_READ_B_Q(buf_, kind_, fb_, 0); TP_READ_B_Q(buf_, kind_, fb_, 1); TP_READ_B_Q(buf_, kind_, fb_, 2); TP_READ_B_Q(buf_, kind_, fb_, 3); }
 #define TP_PIN_A() asm volatile("" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[0][2]), "+v"(fa[0][3]),      \
                                      "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fa[1][2]), "+v"(fa[1][3]))
 #define TP_PIN_B(fb_) asm volatile("" : "+v"(fb_[0]), "+v"(fb_[1]), "+v"(fb_[2]), "+v"(fb_[3]))
@@ -778,14 +874,14 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
 #define TP_BAR() __builtin_amdgcn_s_barrier()
 
   bf16x8 fa[2][4], fb0[4], fb1[4];
-  issue(0, 0); advance(0); issue(1, 0); advance(1); issue(2, 0); advance(2); issue(3, 0); advance(3);
-  issue(0, 1); advance(0); issue(1, 1); advance(1); issue(2, 1); advance(2);
+  fd.issue(0, 0); fd.advance(0); fd.issue(1, 0); fd.advance(1); fd.issue(2, 0); fd.advance(2); fd.issue(3, 0); fd.advance(3);
+  fd.issue(0, 1); fd.advance(0); fd.issue(1, 1); fd.advance(1); fd.issue(2, 1); fd.advance(2);
   // Waits are per region and counted (2 DMA instructions per region; issue order per tile A0 B0 B1 A1, then in the loop
   // A1(kt+1) in P1, A0(kt+2) in P2, B0(kt+2) in P3, B1(kt+2) in P4).  The other group runs ONE BARRIER behind, so a
   // region is complete only two barriers after this wave's own wait: every wait sits a full phase ahead of the first
   // read -- and the B fragments prefetched inside an MMA section are first read one barrier earlier than a load section
   // would read them, so B1(kt+1) is waited for in P4(kt), A0 / B0(kt+1) in P3(kt), A1(kt) in P2(kt).
-  tn_wait_vmcnt<8>();                             // A0(0), B0(0), B1(0) landed; A1(0) A0(1) B0(1) B1(1) in flight
+  wait_vmcnt<8>();                                // A0(0), B0(0), B1(0) landed; A1(0) A0(1) B0(1) B1(1) in flight
   TP_BAR();
   if (wr == 1) TP_BAR();
   if (VTX_TP_PRIO == 2 && wr == 1) __builtin_amdgcn_s_setprio(1);
@@ -812,10 +908,10 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
     if constexpr (TRACE) trace_kt = (kt >= 8 && kt < 16) ? kt - 8 : -1;                                  \
     stamp(0);                                                                                            \
     /* P1: reads A0 (B0 is in X_ already); B1(kt) -- waited for in P4 of the previous tile -- is read during the MFMAs */ \
-    if (kt >= 1 && n1) advance(2);                   /* B1(kt+1) was requested in P4 of the previous tile */ \
+    if (kt >= 1 && n1) fd.advance(2);                /* B1(kt+1) was requested in P4 of the previous tile */ \
     TP_READ_A(buf, 0);                                                                                   \
     TP_COLSUM(buf, 0, cs0);                                                                              \
-    tp_lgkm0();                                                                                          \
+    lgkm0();                                                                                             \
     stamp(1);                                                                                            \
     stamp(2);                                                                                            \
     TP_BAR();                                                                                            \
@@ -827,29 +923,29 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
     TP_BAR();                                                                                            \
     stamp(4);                                                                                            \
     /* P2: no reads (B1 arrived in Y_ during P1); P3 will read A1(kt) */                                 \
-    if (n1) { issue(3, kt + 1); advance(3); }        /* A1(kt+1): requested here, not between the MFMAs (see above) */ \
-    tp_lgkm0();                                                                                          \
+    if (n1) { fd.issue(3, kt + 1); fd.advance(3); }  /* A1(kt+1): requested here, not between the MFMAs (see above) */ \
+    lgkm0();                                                                                             \
     stamp(5);                                                                                            \
-    if (n1) tn_wait_vmcnt<8>(); else tn_wait_vmcnt<0>();                                                 \
+    if (n1) wait_vmcnt<8>(); else wait_vmcnt<0>();                                                       \
     stamp(6);                                                                                            \
     TP_BAR();                                                                                            \
     stamp(7);                                                                                            \
     TP_PIN_B(Y_);                                                                                        \
-    TP_MMA(0, 1, Y_, if (n2) issue_piece(0, kt + 2, 0), if (n2) issue_piece(0, kt + 2, 1), , , , );      \
+    TP_MMA(0, 1, Y_, if (n2) fd.issue_piece(0, kt + 2, 0), if (n2) fd.issue_piece(0, kt + 2, 1), , , , ); \
     stamp(16);                                                                                           \
     TP_BAR();                                                                                            \
     stamp(8);                                                                                            \
     /* P3: reads A1 */                                                                                   \
-    if (n2) advance(0);                                                                                  \
+    if (n2) fd.advance(0);                                                                               \
     TP_READ_A(buf, 3);                                                                                   \
     TP_COLSUM(buf, 3, cs1);                                                                              \
     if (n2) {                                                                                            \
-      tn_wait_vmcnt<6>();                            /* A0(kt+1), B0(kt+1) landed */                     \
+      wait_vmcnt<6>();                               /* A0(kt+1), B0(kt+1) landed */                     \
     } else if (n1) {                                                                                     \
-      tn_wait_vmcnt<0>();                            /* all of the last tile */                          \
-      if (last_valid < TP_BK) zero_tail(kt + 1);                                                         \
+      wait_vmcnt<0>();                               /* all of the last tile */                          \
+      if (last_valid < TP_BK) fd.zero_tail(kt + 1);                                                      \
     }                                                                                                    \
-    tp_lgkm0();                                                                                          \
+    lgkm0();                                                                                             \
     stamp(9);                                                                                            \
     TP_BAR();                                                                                            \
     stamp(10);                                                                                           \
@@ -860,13 +956,13 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
     stamp(11);                                                                                           \
     /* P4: no reads of its own; B0(kt+1) (published by P3's barrier) is read into Y_ during the MFMAs */ \
     if (n2) {                                                                                            \
-      issue(1, kt + 2); advance(1);                  /* B0(kt+2): this section has no reads, see above */ \
-      tn_wait_vmcnt<6>();                            /* B1(kt+1) landed */                               \
+      fd.issue(1, kt + 2); fd.advance(1);            /* B0(kt+2): this section has no reads, see above */ \
+      wait_vmcnt<6>();                               /* B1(kt+1) landed */                               \
     }                                                                                                    \
     stamp(12);                                                                                           \
     TP_BAR();                                                                                            \
     stamp(13);                                                                                           \
-    TP_MMA(2, 0, X_, if (n2) issue_piece(2, kt + 2, 0), if (n2) issue_piece(2, kt + 2, 1),              \
+    TP_MMA(2, 0, X_, if (n2) fd.issue_piece(2, kt + 2, 0), if (n2) fd.issue_piece(2, kt + 2, 1),         \
            if (n1) TP_READ_B_Q(buf ^ 1, 1, Y_, 0), if (n1) TP_READ_B_Q(buf ^ 1, 1, Y_, 1),               \
            if (n1) TP_READ_B_Q(buf ^ 1, 1, Y_, 2), if (n1) TP_READ_B_Q(buf ^ 1, 1, Y_, 3));              \
     stamp(18);                                                                                           \
@@ -891,49 +987,21 @@ __global__ __launch_bounds__(TP_THREADS, 2) void gemm_tn_bf16_pp_kernel(
 #undef TP_MMA
 #undef TP_BAR
   if (want_cs) {
-    // logical chunk of this thread = cs_pc ^ (((cs_row>>1)&1)<<2) (rows cs_row, cs_row+32 share bit 1);
-    // sub-block s of A0 = tile columns s*128 + [0,64), of A1 = s*128 + 64 + [0,64)
     float* red = reinterpret_cast<float*>(smem);            // [32][256] floats = 32 KB (ring is free)
-    const int tc = cs_sub * 128 + (cs_pc ^ (((cs_row >> 1) & 1) << 2)) * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[cs_row * 256 + tc + j] = cs0[j];
-      red[cs_row * 256 + tc + 64 + j] = cs1[j];
-    }
-    __syncthreads();
-    if (tid < 256 && r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 32; ++r) a += red[r * 256 + tid];
-      out.cslab[(long)split * out.slab_stride + (long)t2 * out.N1 + r0 + tid] = a;
-    }
-    __syncthreads();
+    const TnCsLane<32> csl(tid);
+    tn_cs_put<256>(red, csl.row, csl.tile_col(), cs0);
+    tn_cs_put<256>(red, csl.row, csl.tile_col() + 64, cs1);
+    tn_cs_fold<32, 256>(red, out, t, t2, tid);
   }
+  // 16 rows x 64 staged columns per pass: rows r0 + wr*128 + mi*32 + half*16 + [0,16); staged columns [0,32) are
+  // columns wc*32 + [0,32) of the tile's first 128, [32,64) the same of its second 128
   float* stg = reinterpret_cast<float*>(smem + TP_RING_BYTES) + wave * 16 * TP_STG_LD;
-  float* dst = out.slab + (long)split * out.slab_stride;
-#define TP_EPI(mi_, half_)                                                                               \
-  {                                                                                                      \
-    const int col = lane & 31, rhalf = (lane >> 5) * 4;                                                  \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int r = 0; r < 8; ++r)       \
-        stg[((r & 3) + 8 * (r >> 2) + rhalf) * TP_STG_LD + ni * 32 + col] = acc[mi_][ni][8 * (half_) + r]; \
-    tp_lgkm0();                                                                                          \
-    __builtin_amdgcn_wave_barrier();                                                                     \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                      \
-      const int rw = e * 8 + (lane >> 3);                                                                \
-      const int r = r0 + wr * 128 + (mi_) * 32 + (half_) * 16 + rw;                                      \
-      const int c = c0 + ((lane & 7) >> 2) * 128 + wc * 32 + (lane & 3) * 8;                             \
-      if (r < out.N1 && c < out.N2) {                                                                    \
-        const float* sp = stg + rw * TP_STG_LD + (lane & 7) * 8;                                         \
-        float* d = dst + (long)r * out.N2 + c;                                                           \
-        *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(sp);                            \
-        *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(sp + 4);                    \
-      }                                                                                                  \
-    }                                                                                                    \
-    tp_lgkm0();                                                                                          \
-    __builtin_amdgcn_wave_barrier();                                                                     \
+  const int c = c0 + ((lane & 7) >> 2) * 128 + wc * 32 + (lane & 3) * 8;
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi) {
+    tn_epi16<0>(out, stg, acc[mi][0], acc[mi][1], t.split, r0 + wr * 128 + mi * 32, c, lane);
+    tn_epi16<1>(out, stg, acc[mi][0], acc[mi][1], t.split, r0 + wr * 128 + mi * 32 + 16, c, lane);
   }
-  TP_EPI(0, 0) TP_EPI(0, 1) TP_EPI(1, 0) TP_EPI(1, 1) TP_EPI(2, 0) TP_EPI(2, 1) TP_EPI(3, 0) TP_EPI(3, 1)
-#undef TP_EPI
 }
 
 // ---- bf16, 256x256 output tile, ONE wave per SIMD with 128x128 wave tiles (round 5) --------------
@@ -973,88 +1041,15 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 1, wc = wave & 1;
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = bid / tiles12;
-  const int tile = bid - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 256, c0 = t2 * 256;
-  const int m_begin = split * m_per_split;
-  const int m_end = (split == (int)(gridDim.x / tiles12) - 1) ? M : m_begin + m_per_split;   // last split: + remainder
-  const int span = m_end - m_begin;
+  const TnTile t = tn_tile<256, 256, true, true>(M, m_per_split, tiles2, tiles12);
+  const int t2 = t.t2, r0 = t.r0, c0 = t.c0;
+  const int span = t.m_end - t.m_begin;
   const int nk = (span + TP_BK - 1) / TP_BK;      // >= 2 (host guarantees m_per_split >= 128)
   const int last_valid = span - (nk - 1) * TP_BK; // rows of the last tile that are inside the span
-
-  // DMA pieces: a region is 16 pieces of 8 token rows x 128 B (piece p: sub-block p / 8, rows 8 * (p % 8) + lane / 8);
-  // this wave owns pieces 4 * wave .. 4 * wave + 3 -- one sub-block, rows prow0 + 8 j, the same swizzle bit for all four.
-  const int pc0 = wave * 4, sub = pc0 >> 3;
-  const int prow0 = (pc0 & 7) * 8 + (lane >> 3);
-  const int rc = sub * 64 + ((lane & 7) ^ (((prow0 >> 1) & 1) << 2)) * 8;   // region column 0..127
-  const int acol_l = (rc >> 6) * 128 + (rc & 63);
-  const unsigned voff_a = 2u * (unsigned)(prow0 * (int)lda + acol_l), voff_b = 2u * (unsigned)(prow0 * (int)ldb + rc);
-  int trm[4], crs[4], vld[4];
-  const char* sp[4];
-  const long step64_a = 2L * TP_BK * lda, step64_b = 2L * TP_BK * ldb;
-  const long skipb_a = 2L * amap.skip * lda, skipb_b = 2L * bmap.skip * ldb;
-  constexpr int TP_FAR = 1 << 28;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const bool isA = k == 0 || k == 3;
-    const vtx_rowmap& mp = isA ? amap : bmap;
-    const int g = mp.grp;
-    const int q = g > 0 ? m_begin / g : 0;
-    trm[k] = g > 0 ? m_begin - q * g : 0;
-    crs[k] = g > 0 ? g - trm[k] : TP_FAR;
-    vld[k] = M - m_begin;
-    const long phys0 = (long)mp.base + m_begin + (long)q * mp.skip;
-    sp[k] = reinterpret_cast<const char*>(isA ? A + phys0 * lda + r0 + (k == 3 ? 64 : 0) : B + phys0 * ldb + c0 + (k == 2 ? 128 : 0));
-  }
-  auto issue_piece = [&](int kind, int kt, int j) {   // kind: 0 = A0, 1 = B0, 2 = B1, 3 = A1; piece j (0..3) of this wave
-    bf16raw* dst = lds + (kt & 1) * TP_BUF + kind * TP_REGION + wave * 2048;
-    const bool isA = kind == 0 || kind == 3;
-    const char* lo = sp[kind];
-    const char* hi = lo + (isA ? skipb_a : skipb_b);
-    const unsigned vo = isA ? voff_a : voff_b, vc = 2u * (unsigned)(isA ? acol_l : rc);
-    const unsigned step8 = 16u * (unsigned)(isA ? lda : ldb);
-    const int row = prow0 + 8 * j;
-    if (crs[kind] >= TP_BK && vld[kind] >= TP_BK) {   // regular K tile: scalar base + the lane's constant offset (see the ping-pong kernel)
-      const unsigned m0v = (unsigned)(unsigned long)(tn_lds_char*)(dst + j * 512);
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-                   :: "v"(vo + j * step8), "s"(lo), "s"(m0v) : "memory", "m0");
-      return;
-    }
-    const char* base = row >= crs[kind] ? hi : lo;
-    const unsigned o = row < vld[kind] ? vo + j * step8 : vc;
-    tn_dma16(reinterpret_cast<const bf16raw*>(base + o), dst + j * 512);
-  };
-  auto issue = [&](int kind, int kt) { issue_piece(kind, kt, 0); issue_piece(kind, kt, 1); issue_piece(kind, kt, 2); issue_piece(kind, kt, 3); };
-  auto advance = [&](int kind) {
-    const bool isA = kind == 0 || kind == 3;
-    const int g = isA ? amap.grp : bmap.grp;
-    sp[kind] += isA ? step64_a : step64_b;
-    vld[kind] -= TP_BK;
-    if (g > 0) {
-      trm[kind] += TP_BK;
-      if (trm[kind] >= g) { trm[kind] -= g; sp[kind] += isA ? skipb_a : skipb_b; }
-      crs[kind] = g - trm[kind];
-    }
-  };
-  auto zero_tail = [&](int kt) {                  // rows >= last_valid of tile kt (this wave's own pieces)
-#pragma unroll
-    for (int kind = 0; kind < 4; ++kind)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (prow0 + 8 * j >= last_valid)
-          *reinterpret_cast<uint4*>(lds + (kt & 1) * TP_BUF + kind * TP_REGION + wave * 2048 + j * 512 + lane * 8) =
-              make_uint4(0, 0, 0, 0);
-  };
+  TnFeeder<4> fd(lds, wave, lane, A, lda, amap, B, ldb, bmap, M, t, last_valid);
 
   f32x16 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  tn_zero(acc);
 
   // transposed fragment addressing inside a region (as in the ping-pong kernel): token row ks*16 + tr_row (+4), column c
   const int tr_row = 8 * (lane >> 5) + ((lane & 15) >> 2);
@@ -1069,12 +1064,10 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
     fa_addr[i] = lds_b + 2u * (wr * 4096 + off);             // A regions: sub-block wr
     fb_addr[i] = lds_b + 2u * (wc * 4096 + off);             // B regions: sub-block wc
   }
-  // column sums (bias gradient) of the A regions of the K tiles kt % tiles2 == t2: thread -> sub-block tid >> 7,
-  // physical chunk tid & 7 of rows ((tid >> 3) & 15) + {0, 16, 32, 48}
+  // column sums (bias gradient) of the A regions of the K tiles kt % tiles2 == t2: rows csl.row + {0, 16, 32, 48} (TnCsLane)
   constexpr bool want_cs = WANT_CS;
   int cs_next = t2;
-  const int cs_sub = tid >> 7, cs_row = (tid >> 3) & 15, cs_pc = tid & 7;
-  const unsigned cs_addr = lds_b + 2u * (cs_sub * 4096 + cs_row * 64 + cs_pc * 8);
+  const unsigned cs_addr = lds_b + 2u * TnCsLane<16>(tid).lds_off();
   float cs0[8] = {0, 0, 0, 0, 0, 0, 0, 0}, cs1[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   u32x4 csv[4];
 #define TW_CS_READ(buf_, kind_)                                                                          \
@@ -1082,20 +1075,11 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
                "ds_read_b128 %3, %4 offset:6144"                                                         \
                : "=&v"(csv[0]), "=&v"(csv[1]), "=&v"(csv[2]), "=&v"(csv[3])                             \
                : "v"(cs_addr + 2u * ((buf_) * TP_BUF + (kind_) * TP_REGION)) : "memory")
-#define TW_CS_WAIT() { tp_lgkm0(); asm volatile("" : "+v"(csv[0]), "+v"(csv[1]), "+v"(csv[2]), "+v"(csv[3])); }
-#define TW_CS_ADD(cs_, q_)                                                                               \
-  _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                        \
-    cs_[2 * j] += __uint_as_float(csv[q_][j] << 16);                                                     \
-    cs_[2 * j + 1] += __uint_as_float(csv[q_][j] & 0xffff0000u);                                         \
-  }
+#define TW_CS_WAIT() { lgkm0(); asm volatile("" : "+v"(csv[0]), "+v"(csv[1]), "+v"(csv[2]), "+v"(csv[3])); }
+#define TW_CS_ADD(cs_, q_) tn_cs_add(cs_, csv[q_]);
 // (the region kind and the 16-row step travel in the instruction's 16-bit offset field: one address register per operand
 // half and ring buffer instead of one per region, which hipcc hoists out of the loop and spills)
-#define TW_FRAG(dst_, addr_, kind_, ks_)                                                                 \
-  {                                                                                                      \
-    union { bf16x8 v; s16x4 h[2]; } u_;                                                                  \
-    u_.h[0] = tn_tr_read<(kind_) * 16384 + (ks_) * 2048>(addr_);                                         \
-    u_.h[1] = tn_tr_read<(kind_) * 16384 + (ks_) * 2048 + 512>(addr_); dst_ = u_.v;                      \
-  }
+#define TW_FRAG(dst_, addr_, kind_, ks_) { dst_ = tn_tr_frag<(kind_) * 16384 + (ks_) * 2048, 512>(addr_); }
 #define TW_PIN(S_) asm volatile("" : "+v"(S_[0][0]), "+v"(S_[0][1]), "+v"(S_[0][2]), "+v"(S_[0][3]),     \
                                      "+v"(S_[1][0]), "+v"(S_[1][1]), "+v"(S_[1][2]), "+v"(S_[1][3]))
 // the 256 accumulator registers live in the AGPR half of the file: without this the allocator splits their live ranges
@@ -1131,16 +1115,16 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
 // next phase reads have landed (six regions were requested after it; in the last two tiles nothing more is requested:
 // everything), one barrier publishes both
 #define TW_END(n2_)                                                                                      \
-  tp_lgkm0();                                                                                            \
-  if (n2_) tn_wait_vmcnt<24>(); else tn_wait_vmcnt<0>();                                                 \
+  lgkm0();                                                                                               \
+  if (n2_) wait_vmcnt<24>(); else wait_vmcnt<0>();                                                       \
   __builtin_amdgcn_s_barrier();
 
   bf16x8 fa0[2][4], fa1[2][4], fbx[2][4], fby[2][4];
   // prologue: all of K tiles 0 and 1 (the ring's eight slots), then the sets P1(0) multiplies, then A0(2) into the slot
   // A0(0) has just left (the loop continues the request order with B0(2) in P1(0))
-  issue(0, 0); advance(0); issue(1, 0); advance(1); issue(2, 0); advance(2); issue(3, 0); advance(3);
-  issue(0, 1); advance(0); issue(1, 1); advance(1); issue(2, 1); advance(2); issue(3, 1); advance(3);
-  tn_wait_vmcnt<24>();                            // A0(0), B0(0) landed (this wave's pieces)
+  fd.issue(0, 0); fd.advance(0); fd.issue(1, 0); fd.advance(1); fd.issue(2, 0); fd.advance(2); fd.issue(3, 0); fd.advance(3);
+  fd.issue(0, 1); fd.advance(0); fd.issue(1, 1); fd.advance(1); fd.issue(2, 1); fd.advance(2); fd.issue(3, 1); fd.advance(3);
+  wait_vmcnt<24>();                               // A0(0), B0(0) landed (this wave's pieces)
   __builtin_amdgcn_s_barrier();
   {
     const unsigned ra0 = fa_addr[0], ra1 = fa_addr[1], rb0 = fb_addr[0], rb1 = fb_addr[1];
@@ -1148,16 +1132,16 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
     TW_FRAG(fa0[0][2], ra0, 0, 2) TW_FRAG(fa0[1][2], ra1, 0, 2) TW_FRAG(fa0[0][3], ra0, 0, 3) TW_FRAG(fa0[1][3], ra1, 0, 3)
     TW_FRAG(fbx[0][0], rb0, 1, 0) TW_FRAG(fbx[1][0], rb1, 1, 0) TW_FRAG(fbx[0][1], rb0, 1, 1) TW_FRAG(fbx[1][1], rb1, 1, 1)
     TW_FRAG(fbx[0][2], rb0, 1, 2) TW_FRAG(fbx[1][2], rb1, 1, 2) TW_FRAG(fbx[0][3], rb0, 1, 3) TW_FRAG(fbx[1][3], rb1, 1, 3)
-    tp_lgkm0();
+    lgkm0();
     if (want_cs && cs_next == 0) {
       TW_CS_READ(0, 0);
       TW_CS_WAIT();
       TW_CS_ADD(cs0, 0) TW_CS_ADD(cs0, 1) TW_CS_ADD(cs0, 2) TW_CS_ADD(cs0, 3)
     }
-    tn_wait_vmcnt<20>();                          // B1(0), which P1(0) reads, has landed too (five regions were requested after it)
+    wait_vmcnt<20>();                             // B1(0), which P1(0) reads, has landed too (five regions were requested after it)
     __builtin_amdgcn_s_barrier();                 // ... and every wave has read A0(0): its slot takes A0(2)
     TW_PIN(fa0); TW_PIN(fbx);
-    if (nk > 2) { issue(0, 2); advance(0); }
+    if (nk > 2) { fd.issue(0, 2); fd.advance(0); }
   }
   // X_ holds B0(kt), Y_ receives B1(kt) in P1 and B0(kt + 1) in P4: the two sets swap names every K tile
 #define TW_KTILE(kt_, X_, Y_)                                                                            \
@@ -1172,8 +1156,8 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
       TW_MMA(fa0, 0, X_, 0,                                                                              \
              TW_FRAG(Y_[0][0], r0_, 2, 0), TW_FRAG(Y_[1][0], r1_, 2, 0), TW_FRAG(Y_[0][1], r0_, 2, 1), TW_FRAG(Y_[1][1], r1_, 2, 1), \
              TW_FRAG(Y_[0][2], r0_, 2, 2), TW_FRAG(Y_[1][2], r1_, 2, 2), TW_FRAG(Y_[0][3], r0_, 2, 3), TW_FRAG(Y_[1][3], r1_, 2, 3), \
-             if (n2) issue_piece(1, kt + 2, 0), if (n2) issue_piece(1, kt + 2, 1), if (n2) issue_piece(1, kt + 2, 2), \
-             if (n2) issue_piece(1, kt + 2, 3), if (n2) advance(1), , , )                                \
+             if (n2) fd.issue_piece(1, kt + 2, 0), if (n2) fd.issue_piece(1, kt + 2, 1), if (n2) fd.issue_piece(1, kt + 2, 2), \
+             if (n2) fd.issue_piece(1, kt + 2, 3), if (n2) fd.advance(1), , , )                          \
       TW_END(n2)                                                                                         \
       TW_PIN(Y_);                                                                                        \
     }                                                                                                    \
@@ -1184,14 +1168,14 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
       TW_MMA(fa0, 0, Y_, 2,                                                                              \
              TW_FRAG(fa1[0][0], r0_, 3, 0), TW_FRAG(fa1[1][0], r1_, 3, 0), TW_FRAG(fa1[0][1], r0_, 3, 1), TW_FRAG(fa1[1][1], r1_, 3, 1), \
              TW_FRAG(fa1[0][2], r0_, 3, 2), TW_FRAG(fa1[1][2], r1_, 3, 2), TW_FRAG(fa1[0][3], r0_, 3, 3), TW_FRAG(fa1[1][3], r1_, 3, 3), \
-             if (cs_) TW_CS_READ(buf, 3); if (n2) issue_piece(2, kt + 2, 0), if (n2) issue_piece(2, kt + 2, 1),  \
-             if (n2) issue_piece(2, kt + 2, 2), if (n2) issue_piece(2, kt + 2, 3),                       \
-             if (n2) advance(2); if (cs_) { TW_CS_WAIT() TW_CS_ADD(cs1, 0) }, if (cs_) { TW_CS_ADD(cs1, 1) }, \
+             if (cs_) TW_CS_READ(buf, 3); if (n2) fd.issue_piece(2, kt + 2, 0), if (n2) fd.issue_piece(2, kt + 2, 1), \
+             if (n2) fd.issue_piece(2, kt + 2, 2), if (n2) fd.issue_piece(2, kt + 2, 3),                 \
+             if (n2) fd.advance(2); if (cs_) { TW_CS_WAIT() TW_CS_ADD(cs1, 0) }, if (cs_) { TW_CS_ADD(cs1, 1) }, \
              if (cs_) { TW_CS_ADD(cs1, 2) }, if (cs_) { TW_CS_ADD(cs1, 3) })                             \
       if (cs_) cs_next += tiles2;                                                                        \
       if (!n2) {                                   /* the tile after this one is the last: wait for all of it, zero its tail */ \
-        tn_wait_vmcnt<0>();                                                                              \
-        if (n1 && last_valid < TP_BK) zero_tail(kt + 1);                                                 \
+        wait_vmcnt<0>();                                                                                 \
+        if (n1 && last_valid < TP_BK) fd.zero_tail(kt + 1);                                              \
       }                                                                                                  \
       TW_END(n2)                                                                                         \
       TW_PIN(fa1);                                                                                       \
@@ -1204,9 +1188,9 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
              TW_FRAG(fa0[0][0], r0_, 0, 0), TW_FRAG(fa0[1][0], r1_, 0, 0), TW_FRAG(fa0[0][1], r0_, 0, 1), \
              TW_FRAG(fa0[1][1], r1_, 0, 1), TW_FRAG(fa0[0][2], r0_, 0, 2), TW_FRAG(fa0[1][2], r1_, 0, 2), \
              TW_FRAG(fa0[0][3], r0_, 0, 3), TW_FRAG(fa0[1][3], r1_, 0, 3),                     \
-             if (cs_) TW_CS_READ(buf ^ 1, 0); if (n2) issue_piece(3, kt + 2, 0), if (n2) issue_piece(3, kt + 2, 1), \
-             if (n2) issue_piece(3, kt + 2, 2), if (n2) issue_piece(3, kt + 2, 3),                       \
-             if (n2) advance(3); if (cs_) { TW_CS_WAIT() TW_CS_ADD(cs0, 0) }, if (cs_) { TW_CS_ADD(cs0, 1) }, \
+             if (cs_) TW_CS_READ(buf ^ 1, 0); if (n2) fd.issue_piece(3, kt + 2, 0), if (n2) fd.issue_piece(3, kt + 2, 1), \
+             if (n2) fd.issue_piece(3, kt + 2, 2), if (n2) fd.issue_piece(3, kt + 2, 3),                 \
+             if (n2) fd.advance(3); if (cs_) { TW_CS_WAIT() TW_CS_ADD(cs0, 0) }, if (cs_) { TW_CS_ADD(cs0, 1) }, \
              if (cs_) { TW_CS_ADD(cs0, 2) }, if (cs_) { TW_CS_ADD(cs0, 3) })                             \
       TW_END(n2)                                                                                         \
       TW_PIN(fa0);                                                                                       \
@@ -1218,8 +1202,8 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
              TW_FRAG(Y_[0][0], r0_, 1, 0), TW_FRAG(Y_[1][0], r1_, 1, 0), TW_FRAG(Y_[0][1], r0_, 1, 1), \
              TW_FRAG(Y_[1][1], r1_, 1, 1), TW_FRAG(Y_[0][2], r0_, 1, 2), TW_FRAG(Y_[1][2], r1_, 1, 2), \
              TW_FRAG(Y_[0][3], r0_, 1, 3), TW_FRAG(Y_[1][3], r1_, 1, 3),                       \
-             if (n3) issue_piece(0, kt + 3, 0), if (n3) issue_piece(0, kt + 3, 1), if (n3) issue_piece(0, kt + 3, 2), \
-             if (n3) issue_piece(0, kt + 3, 3), if (n3) advance(0), , , )                                \
+             if (n3) fd.issue_piece(0, kt + 3, 0), if (n3) fd.issue_piece(0, kt + 3, 1), if (n3) fd.issue_piece(0, kt + 3, 2), \
+             if (n3) fd.issue_piece(0, kt + 3, 3), if (n3) fd.advance(0), , , )                          \
       TW_END(n3)                                   /* the sixth request behind B1(kt + 1) is this phase's A0(kt + 3) */ \
       TW_PIN(Y_);                                                                                        \
     }                                                                                                    \
@@ -1239,57 +1223,33 @@ __global__ __launch_bounds__(TW_THREADS, 1) void gemm_tn_bf16_w4_kernel(
 #undef TW_MF
 #undef TW_PIN
 #undef TW_FRAG
+  // what the fold and the store need of the thread index is rebuilt from it here: kept live across the loop it is spilled
+  int te = threadIdx.x;
+  asm volatile("" : "+v"(te));
+  const int lane_e = te & 63;
   if (want_cs) {
-    // logical chunk of this thread = cs_pc ^ (((cs_row >> 1) & 1) << 2) (rows cs_row + 16 k share bit 1);
-    // sub-block s of A0 = tile columns s*128 + [0,64), of A1 = s*128 + 64 + [0,64)
     float* red = reinterpret_cast<float*>(smem);            // [16][256] floats = 16 KB (the ring is free: last barrier above)
-    const int tc = cs_sub * 128 + (cs_pc ^ (((cs_row >> 1) & 1) << 2)) * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      red[cs_row * 256 + tc + j] = cs0[j];
-      red[cs_row * 256 + tc + 64 + j] = cs1[j];
-    }
-    __syncthreads();
-    if (r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) a += red[r * 256 + tid];
-      out.cslab[(long)split * out.slab_stride + (long)t2 * out.N1 + r0 + tid] = a;
-    }
-    __syncthreads();
+    const TnCsLane<16> csl(te);
+    tn_cs_put<256>(red, csl.row, csl.tile_col(), cs0);
+    tn_cs_put<256>(red, csl.row, csl.tile_col() + 64, cs1);
+    tn_cs_fold<16, 256>(red, out, t, t2, te);
   }
 #undef TW_CS_READ
 #undef TW_CS_WAIT
 #undef TW_CS_ADD
-  float* stg = reinterpret_cast<float*>(smem + TP_RING_BYTES) + wave * 16 * TP_STG_LD;
-  float* dst = out.slab + (long)split * out.slab_stride;
   // 16 rows x 64 contiguous columns per pass: rows r0 + wr*128 + mi*32 + half*16 + [0,16), columns c0 + jp*128 + wc*64 + [0,64)
-#define TW_EPI(mi_, half_, jp_)                                                                          \
-  {                                                                                                      \
-    __builtin_amdgcn_sched_barrier(0);               /* one pass at a time: hoisted together, the 256 accumulator reads spill */ \
-    const int col = lane & 31, rhalf = (lane >> 5) * 4;                                                  \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int r = 0; r < 8; ++r)       \
-        stg[((r & 3) + 8 * (r >> 2) + rhalf) * TP_STG_LD + ni * 32 + col] = acc[mi_][2 * (jp_) + ni][8 * (half_) + r]; \
-    tp_lgkm0();                                                                                          \
-    __builtin_amdgcn_wave_barrier();                                                                     \
-    _Pragma("unroll") for (int e = 0; e < 2; ++e) {                                                      \
-      const int rw = e * 8 + (lane >> 3);                                                                \
-      const int r = r0 + wr * 128 + (mi_) * 32 + (half_) * 16 + rw;                                      \
-      const int c = c0 + (jp_) * 128 + wc * 64 + (lane & 7) * 8;                                         \
-      if (r < out.N1 && c < out.N2) {                                                                    \
-        const float* sp_ = stg + rw * TP_STG_LD + (lane & 7) * 8;                                        \
-        float* d = dst + (long)r * out.N2 + c;                                                           \
-        *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(sp_);                           \
-        *reinterpret_cast<float4*>(d + 4) = *reinterpret_cast<const float4*>(sp_ + 4);                   \
-      }                                                                                                  \
-    }                                                                                                    \
-    tp_lgkm0();                                                                                          \
-    __builtin_amdgcn_wave_barrier();                                                                     \
-    __builtin_amdgcn_sched_barrier(0);                                                                   \
-  }
-  TW_EPI(0, 0, 0) TW_EPI(0, 1, 0) TW_EPI(1, 0, 0) TW_EPI(1, 1, 0) TW_EPI(2, 0, 0) TW_EPI(2, 1, 0) TW_EPI(3, 0, 0) TW_EPI(3, 1, 0)
-  TW_EPI(0, 0, 1) TW_EPI(0, 1, 1) TW_EPI(1, 0, 1) TW_EPI(1, 1, 1) TW_EPI(2, 0, 1) TW_EPI(2, 1, 1) TW_EPI(3, 0, 1) TW_EPI(3, 1, 1)
-#undef TW_EPI
+  float* stg = reinterpret_cast<float*>(smem + TP_RING_BYTES) + wave * 16 * TP_STG_LD;
+#pragma unroll
+  for (int jp = 0; jp < 2; ++jp)
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const int r = r0 + wr * 128 + mi * 32, c = c0 + jp * 128 + wc * 64 + (lane_e & 7) * 8;
+      __builtin_amdgcn_sched_barrier(0);               // one pass at a time: hoisted together, the 256 accumulator reads spill
+      tn_epi16<0>(out, stg, acc[mi][2 * jp], acc[mi][2 * jp + 1], t.split, r, c, lane_e);
+      __builtin_amdgcn_sched_barrier(0);
+      tn_epi16<1>(out, stg, acc[mi][2 * jp], acc[mi][2 * jp + 1], t.split, r + 16, c, lane_e);
+      __builtin_amdgcn_sched_barrier(0);
+    }
 }
 
 static int tp_splits(int M, int N1, int N2) {
@@ -1301,107 +1261,6 @@ static int tp_splits(int M, int N1, int N2) {
 }
 static bool tp_eligible(int M, int N1, int N2) { return M >= 4096 && N1 % 256 == 0 && N2 % 256 == 0; }
 static bool tp_map_ok(const vtx_rowmap& m) { return m.grp == 0 || m.grp > TP_BK; }
-
-__global__ __launch_bounds__(NT_THREADS) void gemm_tn_f32_kernel(
-    int M, int m_per_split, const float* __restrict__ A, long lda, vtx_rowmap amap,
-    const float* __restrict__ B, long ldb, vtx_rowmap bmap, int tiles2, int tiles12, TnOut out) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  float* As = reinterpret_cast<float*>(smem);              // [16][128]
-  float* Bs = As + TN_BKM32 * TN_LD32;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int split = blockIdx.x / tiles12;
-  const int tile = blockIdx.x - split * tiles12;
-  const int t1 = tile / tiles2, t2 = tile - t1 * tiles2;
-  const int r0 = t1 * 128, c0 = t2 * 128;
-  const int m_begin = split * m_per_split;
-  const int m_end = min(M, m_begin + m_per_split);
-
-  // loader: 16 rows x 32 float4 chunks = 512 chunks -> 2 per thread per operand
-  const int lc = tid & 31, lr = tid >> 5;
-  const bool a_col_ok = (r0 + lc * 4) < out.N1;
-  const bool b_col_ok = (c0 + lc * 4) < out.N2;
-  const int a_col = a_col_ok ? r0 + lc * 4 : 0;
-  const int b_col = b_col_ok ? c0 + lc * 4 : 0;
-  float4 ra[2], rb[2];
-  const float4 z4 = make_float4(0, 0, 0, 0);
-#define TN_GLOAD32(mt_)                                                                                        \
-  {                                                                                                            \
-    const int mt__ = (mt_);                                                                                    \
-    _Pragma("unroll") for (int it = 0; it < 2; ++it) {                                                         \
-      const int m = mt__ + lr + 8 * it;                                                                        \
-      const bool ok = m < m_end;                                                                               \
-      const int mc = m < M ? m : M - 1;                                                                        \
-      ra[it] = *reinterpret_cast<const float4*>(A + map_row(amap, mc) * lda + a_col);                          \
-      rb[it] = *reinterpret_cast<const float4*>(B + map_row(bmap, mc) * ldb + b_col);                          \
-      if (!(ok && a_col_ok)) ra[it] = z4;                                                                      \
-      if (!(ok && b_col_ok)) rb[it] = z4;                                                                      \
-    }                                                                                                          \
-  }
-#define TN_LSTORE32()                                                  \
-  {                                                                    \
-    _Pragma("unroll") for (int it = 0; it < 2; ++it) {                 \
-      const int off = (lr + 8 * it) * TN_LD32 + lc * 4;                \
-      *reinterpret_cast<float4*>(As + off) = ra[it];                   \
-      *reinterpret_cast<float4*>(Bs + off) = rb[it];                   \
-    }                                                                  \
-  }
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int kh = lane >> 5, col = lane & 31;
-  const bool do_cs = out.cslab != nullptr && t2 == 0;
-  float csum[4] = {0, 0, 0, 0};
-  TN_GLOAD32(m_begin);
-  for (int mt = m_begin; mt < m_end; mt += TN_BKM32) {
-    TN_LSTORE32();
-    if (do_cs) {
-#pragma unroll
-      for (int it = 0; it < 2; ++it) { csum[0] += ra[it].x; csum[1] += ra[it].y; csum[2] += ra[it].z; csum[3] += ra[it].w; }
-    }
-    __syncthreads();
-    if (mt + TN_BKM32 < m_end) TN_GLOAD32(mt + TN_BKM32);
-#pragma unroll
-    for (int ks = 0; ks < TN_BKM32 / 2; ++ks) {
-      float af[2], bfr[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        af[i] = As[(ks * 2 + kh) * TN_LD32 + wm * 64 + i * 32 + col];
-        bfr[i] = Bs[(ks * 2 + kh) * TN_LD32 + wn * 64 + i * 32 + col];
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
-    __syncthreads();
-  }
-  if (do_cs) {
-    float* red = reinterpret_cast<float*>(smem);            // [8][128]
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[lr * 128 + lc * 4 + j] = csum[j];
-    __syncthreads();
-    if (tid < 128 && r0 + tid < out.N1) {
-      float a = 0.f;
-#pragma unroll
-      for (int r = 0; r < 8; ++r) a += red[r * 128 + tid];
-      out.cslab[(long)split * out.slab_stride + r0 + tid] = a;
-    }
-    __syncthreads();
-  }
-  float* stage = reinterpret_cast<float*>(smem) + wave * 64 * STAGE_LD;
-  stage_acc(stage, acc, lane);
-  __builtin_amdgcn_s_waitcnt(0xc07f);
-  __builtin_amdgcn_wave_barrier();
-  tn_store(out, stage, split, r0 + wm * 64, c0 + wn * 64, lane);
-}
 
 // ---- column sums (bias gradients): part[blk][N] then reduce -------------------
 template <typename T>
