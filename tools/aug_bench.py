@@ -48,6 +48,15 @@ the kernel-rate yardstick, and (d) that uniform batch given as a list, i.e. thro
 one descriptor read per workgroup.  (a) and (b) are checked for equal bytes first, (c) and (d) likewise; all paths in alternating
 rounds of one run; per path the device time (HIP events around the calls of a round), the host clock around the same calls ending
 in a synchronise, and the resampling kernel alone (a pair of HIP events around each launch, in rounds of its own).
+
+    python tools/aug_bench.py --yuv [--parent-lib PATH/libvtx_ragged.so] [--out profiles/clip_yuv_bench.txt]
+
+times the batch of --ragged given as decoded 4:2:0 planes (csrc/yuv.hip; NV12, the matrix of an untagged stream): (a) `vtx_clips_views_u8`
+on RGB clips converted beforehand -- what a loader pays for today behind a CPU colour conversion --, (b) `vtx_yuv420_to_rgb_u8` on every
+clip and then (a), (c) `vtx_clips_views_yuv420` on the planes.  --parent-lib: a libvtx_ragged.so built at the parent commit, timed as (p)
+on the same RGB clips in the same alternating rounds: its device code is this commit's, so (p) and (a) must agree within (p)'s own
+spread.  (a), (b) and (c) are checked for equal bytes first.  Per path the kernels alone (HIP events around each launch), the whole
+call (host clock around `ClipEval` on the list, ending in a synchronise) and the bytes its kernels have to move.
 """
 import argparse
 import os
@@ -602,16 +611,129 @@ def ragged_main(a):
         f.write(text)
 
 
+def yuv_main(a):
+    import time
+    import numpy as np
+    from vtx import _lib
+    dev = 'cuda:0'
+    B, Ts, T, S, k = a.clips, a.decoded, a.frames, a.size, a.sets
+    sizes = [(256, 340), (340, 256), (240, 320), (360, 480)]
+    hw = [sizes[b % 4] for b in range(B)]
+    ev = aug.ClipEval(img_size=S)
+    g = torch.Generator().manual_seed(0)
+    rnd = lambda *shape: torch.randint(0, 256, shape, dtype=torch.uint8, device=dev)
+    yuvs = [[vtx.YUVClip(rnd(Ts, h, w), rnd(Ts, (h + 1) // 2, (w + 1) // 2, 2)) for h, w in hw] for _ in range(k)]
+    rgbs = [[ops.yuv420_to_rgb_u8(c) for c in clips] for clips in yuvs]
+    frames = np.stack([aug.sample_frames(Ts, T, Ts // T, generator=g) for _ in range(B)]).astype(np.int32)
+    this_lib = _lib.load_ragged()
+    parent_lib = _lib._bind(a.parent_lib, 'the parent\'s libvtx_ragged.so', _lib.RAGGED_SIGNATURES) if a.parent_lib else None
+
+    def with_lib(lib, fn):
+        def run(i):
+            _lib._side['ragged'] = lib                         # the binding calls whichever library is loaded under this key
+            try:
+                return fn(i)
+            finally:
+                _lib._side['ragged'] = this_lib
+        return run
+
+    def rgb_views(i):
+        return ev(rgbs[i % k], frames=frames)
+
+    def convert_then_views(i):
+        return ev([ops.yuv420_to_rgb_u8(c) for c in yuvs[i % k]], frames=frames)
+
+    def fused(i):
+        return ev(yuvs[i % k], frames=frames)
+    want = rgb_views(0)
+    same = torch.equal(convert_then_views(0), want) and torch.equal(fused(0), want)
+    assert same, 'the three routes differ'
+    paths = [('(a) vtx_clips_views_u8 on RGB clips', with_lib(this_lib, rgb_views)),
+             ('(b) vtx_yuv420_to_rgb_u8 + vtx_clips_views_u8', convert_then_views),
+             ('(c) vtx_clips_views_yuv420', fused)]
+    if parent_lib is not None:
+        assert torch.equal(with_lib(parent_lib, rgb_views)(0), want), 'the parent library gives other bytes'
+        paths.insert(0, ('(p) vtx_clips_views_u8 on RGB clips, parent commit', with_lib(parent_lib, rgb_views)))
+    for i in range(a.warmup):
+        for _, fn in paths:
+            fn(i)
+    torch.cuda.synchronize()
+    wall = {n: [] for n, _ in paths}
+    turn = lambda r: paths[r % len(paths):] + paths[:r % len(paths)]   # the order rotates: no path always runs behind the same neighbour
+    for r in range(a.rounds):                                  # alternating: what else runs on the machine hits all alike
+        for n, fn in turn(r):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            torch.cuda.synchronize()
+            wall[n].append((time.perf_counter() - t0) * 1e6 / a.iters)
+    kern = {n: [] for n, _ in paths}                           # events around every launch, in rounds of their own: they slow the host
+    for r in range(a.rounds):
+        for n, fn in turn(r):
+            ops.profile_start(('clips_views', 'clips_views_yuv', 'yuv420_to_rgb'))
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            torch.cuda.synchronize()
+            tot = ops.profile_totals(ops.profile_stop())
+            kern[n].append(sum(v[1] for v in tot.values()) * 1e3 / a.iters)
+    px_sel = T * sum(h * w for h, w in hw)
+    px_all = Ts * sum(h * w for h, w in hw)
+    out_b = B * T * S * S * 3
+    nbytes = {'(p)': 3 * px_sel + out_b, '(a)': 3 * px_sel + out_b, '(b)': int(1.5 * px_all) + 3 * px_all + 3 * px_sel + out_b,
+              '(c)': int(1.5 * px_sel) + out_b}
+    what = {'(p)': 'selected RGB frames read, result written', '(a)': 'selected RGB frames read, result written',
+            '(b)': f'all {Ts} decoded frames of every clip converted: planes read, RGB written; then as (a)',
+            '(c)': 'selected frames of the planes read (1.5 bytes per pixel), result written'}
+    lines = [f'decoded 4:2:0 clips (NV12), {B} clips, {T} of {Ts} decoded frames each, sizes {sizes} in equal shares, ClipEval({S}) '
+             f'(Resize({ev.scale_size}) + centre crop), bicubic, antialias off; {torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} batches per path, the paths in alternating rounds of one run whose order rotates from round to round, after {a.warmup} warm-up batches each; '
+             f'{k} source sets in rotation: {sum(c.numel() for c in rgbs[0]) / 2**20:.0f} MiB of RGB and '
+             f'{sum(p.numel() for c in yuvs[0] for p in c.planes) / 2**20:.0f} MiB of planes each',
+             f'same bytes from (a), (b) and (c): {same}' + ('; (p): the same bytes from the parent library' if parent_lib is not None else ''),
+             'kernel = HIP events around each launch of the path, summed per batch, in rounds of their own; wall = host clock around the whole '
+             'call (tables, checks, one upload, the launches), ending in a synchronise; all per batch; spread = (max - min) / median over the rounds',
+             'bytes = what the kernels of a path have to move, whole frames counted; the upload the caller makes before it is 3 bytes per decoded '
+             f'pixel for (a) and 1.5 for (c): {3 * px_all / 1e6:.1f} MB against {1.5 * px_all / 1e6:.1f} MB per batch',
+             '']
+    med, spread = {}, {}
+    for n, _ in paths:
+        key, kr, w = n[:3], kern[n], wall[n]
+        mk, mw = statistics.median(kr), statistics.median(w)
+        med[key], spread[key] = (mk, mw), ((max(kr) - min(kr)) / mk, (max(w) - min(w)) / mw)
+        lines.append(f'{n:<52} kernel median {mk:8.1f} us  min {min(kr):8.1f}  max {max(kr):8.1f}  spread {100 * spread[key][0]:5.1f} %   '
+                     f'wall median {mw:8.1f} us  min {min(w):8.1f}  max {max(w):8.1f}  spread {100 * spread[key][1]:5.1f} %   '
+                     f'{nbytes[key] / 1e6:7.1f} MB ({what[key]})  {nbytes[key] / mk / 1e6:5.2f} TB/s')
+    lines.append('')
+    if parent_lib is not None:
+        d, bar = med['(a)'][0] - med['(p)'][0], spread['(p)'][0] * med['(p)'][0]
+        lines.append(f'(a) - (p), kernel: {d:+.1f} us against the parent\'s own spread of {bar:.1f} us: '
+                     + ('within it' if abs(d) <= bar else 'OUTSIDE it'))
+    d, bar = med['(c)'][0] - med['(a)'][0], spread['(a)'][0] * med['(a)'][0]
+    lines.append(f'(c) / (a), kernel: {med["(c)"][0] / med["(a)"][0]:.3f} of the time for {nbytes["(c)"] / nbytes["(a)"]:.3f} of the bytes; (c) - (a) = {d:+.1f} us against a '
+                 f'spread of {bar:.1f} us: ' + ('the fused kernel is not slower than the RGB kernel on RGB clips' if d <= bar else
+                                                'the fused kernel is SLOWER than the RGB kernel on RGB clips: it moves fewer bytes in more time, so the bytes do not set its time; '
+                                                'what it adds per tap is arithmetic (5 integer multiply-adds, 3 shifts, 3 clamps) and a third load stream'))
+    lines.append(f'(c) / (b), kernel: {med["(c)"][0] / med["(b)"][0]:.3f}; whole call: (c) / (a) = {med["(c)"][1] / med["(a)"][1]:.3f}, (c) / (b) = {med["(c)"][1] / med["(b)"][1]:.3f}')
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--yuv', action='store_true', help='time a batch of decoded 4:2:0 clips against the RGB route (-> profiles/clip_yuv_bench.txt)')
+    ap.add_argument('--parent-lib', default=None, help='--yuv: a libvtx_ragged.so built at the parent commit, timed beside this one')
     ap.add_argument('--ragged', action='store_true', help='time one call on a list of clips of differing size against one call per clip (-> profiles/clip_ragged_bench.txt)')
     ap.add_argument('--stem', action='store_true', help='time the uint8 stem gather and hog_targets against the float routes (-> profiles/stem_u8_bench.txt)')
     ap.add_argument('--mix', action='store_true', help='time Mixup / CutMix on uint8 clips against the float route (-> profiles/clip_mix_bench.txt)')
     ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
-    ap.add_argument('--decoded', type=int, default=32, help='--views, --ragged: decoded frames per clip')
+    ap.add_argument('--decoded', type=int, default=32, help='--views, --ragged, --yuv: decoded frames per clip')
     ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
     ap.add_argument('--randaug', action='store_true', help='time the RandAugment kernels instead (-> profiles/clip_randaug_bench.txt)')
-    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views, --stem and --ragged')
+    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views, --stem, --ragged and --yuv')
     ap.add_argument('--frames', type=int, default=None, help='default 8; 16 with --stem')
     ap.add_argument('--src', type=int, nargs=2, default=(256, 340))
     ap.add_argument('--size', type=int, default=224)
@@ -623,13 +745,15 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.clips is None:
-        a.clips = 32 if a.views or a.stem or a.ragged else 96
+        a.clips = 32 if a.views or a.stem or a.ragged or a.yuv else 96
     if a.frames is None:
         a.frames = 16 if a.stem else 8
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'clip_ragged_bench.txt' if a.ragged else 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
+        a.out = os.path.join(ROOT, 'profiles', 'clip_yuv_bench.txt' if a.yuv else 'clip_ragged_bench.txt' if a.ragged else 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
                              'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.yuv:
+        return yuv_main(a)
     if a.ragged:
         return ragged_main(a)
     if a.stem:

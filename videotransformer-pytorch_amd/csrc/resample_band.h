@@ -1,6 +1,7 @@
-// resample_band.h -- the separable resampling band of clip_resample_u8_kernel (aug.hip), clip_views_u8_kernel (views.hip)
-// and clips_views_u8_kernel (ragged.hip), written once: the three entry points give the same bytes for the same tables
-// because they run this text.
+// resample_band.h -- the separable resampling band of clip_resample_u8_kernel (aug.hip), clip_views_u8_kernel (views.hip),
+// clips_views_u8_kernel (ragged.hip) and clips_views_yuv420_kernel (yuv.hip), written once: the entry points give the same
+// bytes for the same tables and the same RGB values because they run this text.  What differs is the tap reader: an RGB
+// frame (RgbTaps, here) or 4:2:0 planes converted tap by tap in registers (yuv.hip).
 //
 // One thread per output column x (all three channels), one workgroup per (frame, band of BAND_ROWS output rows, 256
 // columns).  The band's source rows s = lo .. hi-1 are walked once in ascending order: the thread forms the x-resampled
@@ -28,11 +29,26 @@ __device__ inline void clamp_taps(int& f, int& c, int taps, int len) {
   if (f + c > len) { f = len - c < 0 ? 0 : len - c; c = c > len ? len : c; }
 }
 
-// Output rows r0 .. r0 + BAND_ROWS - 1 (those below H) of one column of one frame.  img: the frame [Hs,Ws,3]; fx, cx: the
-// column's raw table entries, wx its weight row of xt floats; yf, yc, yw: the clip's y table rows of H entries (yw: H * yt).
-// store(r, red, green, blue) is called once per live output row r0 + r with the rounded bytes.
-template <typename Store>
-__device__ __forceinline__ void resample_band(const uint8_t* __restrict__ img, int Hs, int Ws, int H, int r0, int fx, int cx,
+// The tap reader of an RGB frame [Hs,Ws,3], the default: a tap is three single-byte loads.  A reader names its Source (what
+// the band is given for a frame, passed by value) and has a static row(source, Ws, s, fx) that gives, for source row s and
+// first tap column fx, a row object whose tap(k) yields the three channels of column fx + k as floats.  The band calls row()
+// once per source row and tap() for k = 0 .. cx-1 in ascending order, all inside the frame.  (Static, and no reader object:
+// with one the compiler orders two scalar selects of the y windows differently in the three RGB kernels.)
+struct RgbTaps {
+  typedef const uint8_t* __restrict__ Source;                      // the frame
+  struct Row {
+    const uint8_t* __restrict__ p;
+    __device__ __forceinline__ float3 tap(int k) const { return make_float3((float)p[3 * k], (float)p[3 * k + 1], (float)p[3 * k + 2]); }
+  };
+  static __device__ __forceinline__ Row row(Source img, int Ws, int s, int fx) { return Row{img + ((long)s * Ws + fx) * 3}; }
+};
+
+// Output rows r0 .. r0 + BAND_ROWS - 1 (those below H) of one column of one frame of Hs x Ws pixels.  src: what Taps reads --
+// RgbTaps (the default): the frame [Hs,Ws,3]; yuv.hip's reader: 4:2:0 planes; fx, cx: the column's raw table entries, wx its
+// weight row of xt floats; yf, yc, yw: the clip's y table rows of H entries (yw: H * yt).  store(r, red, green, blue) is called
+// once per live output row r0 + r with the rounded bytes.
+template <typename Taps = RgbTaps, typename Store>
+__device__ __forceinline__ void resample_band(typename Taps::Source src, int Hs, int Ws, int H, int r0, int fx, int cx,
                                               const float* __restrict__ wx, int xt, const int* __restrict__ yf,
                                               const int* __restrict__ yc, const float* __restrict__ yw, int yt, Store store) {
 #pragma clang fp contract(off)
@@ -53,13 +69,14 @@ __device__ __forceinline__ void resample_band(const uint8_t* __restrict__ img, i
 #pragma unroll
   for (int r = 0; r < BAND_ROWS; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 0.0f;
   for (int s = lo; s < hi; ++s) {
-    const uint8_t* p = img + ((long)s * Ws + fx) * 3;
+    const auto row = Taps::row(src, Ws, s, fx);
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
     for (int k = 0; k < cx; ++k) {
       const float w = wx[k];
-      v0 = v0 + w * (float)p[3 * k];
-      v1 = v1 + w * (float)p[3 * k + 1];
-      v2 = v2 + w * (float)p[3 * k + 2];
+      const float3 t = row.tap(k);
+      v0 = v0 + w * t.x;
+      v1 = v1 + w * t.y;
+      v2 = v2 + w * t.z;
     }
 #pragma unroll
     for (int r = 0; r < BAND_ROWS; ++r) {

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib, ops, functions, aug  # noqa: F401
 from ._lib import VtxError, load, set_option  # noqa: F401
-from .ops import set_input_normalization, MixedClip, hog_targets  # noqa: F401
+from .ops import set_input_normalization, MixedClip, YUVClip, hog_targets  # noqa: F401
 
 _precision = 'auto'
 

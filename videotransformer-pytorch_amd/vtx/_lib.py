@@ -247,6 +247,16 @@ DROPOUT_SIGNATURES = {
                               C.c_ulonglong, cf, C.c_ulonglong, C.c_uint, C.c_ulonglong, vp]),
 }
 
+# libvtx_yuv.so (include/vtx_yuv.h, csrc/yuv.hip): 4:2:0 YUV clips into the resampler, the ninth library.  Must list every symbol the header declares.
+YUV_LIB_PATH = os.environ.get('VTX_YUV_LIB', os.path.join(_PKG, 'libvtx_yuv.so'))
+YUV_CLIP_I32 = 22           # int32 words of one vtx_yuv420_clip record: 3 pointers, Ts Hs Ws Wr, 5 strides, 6 matrix entries, 1 reserved
+YUV_SIGNATURES = {
+    'vtx_yuv_version': (ci, []),
+    'vtx_yuv_last_error_string': (C.c_char_p, []),
+    'vtx_clips_views_yuv420': (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+    'vtx_yuv420_to_rgb_u8': (ci, [vp, ci, ci, ci, vp, vp]),
+}
+
 # key -> (name of the path constant, signatures): every library beside libvtx.so.  The path is read when the library is
 # first loaded.  libvtx_<key>.so exports vtx_<key>_version and vtx_<key>_last_error_string beside its entry points.
 _SIDE = {
@@ -257,6 +267,7 @@ _SIDE = {
     'stem': ('STEM_LIB_PATH', STEM_SIGNATURES),
     'ragged': ('RAGGED_LIB_PATH', RAGGED_SIGNATURES),
     'dropout': ('DROPOUT_LIB_PATH', DROPOUT_SIGNATURES),
+    'yuv': ('YUV_LIB_PATH', YUV_SIGNATURES),
 }
 _lib = None
 _side = {}
@@ -308,6 +319,7 @@ load_mix, mix_call = partial(_load_side, 'mix'), partial(_side_call, 'mix')
 load_stem, stem_call = partial(_load_side, 'stem'), partial(_side_call, 'stem')
 load_ragged, ragged_call = partial(_load_side, 'ragged'), partial(_side_call, 'ragged')
 load_dropout, dropout_call = partial(_load_side, 'dropout'), partial(_side_call, 'dropout')
+load_yuv, yuv_call = partial(_load_side, 'yuv'), partial(_side_call, 'yuv')
 aug_check = partial(_side_check, 'aug')
 
 

@@ -39,6 +39,16 @@ uniform [B,T,S,S,3] ([B*3,T,S,S,3] for ``ClipTest``) in the same number of launc
     batch = [c.cuda(non_blocking=True) for c in decoded]          # 340x256, 256x340, 320x240, ...: no resize on the host
     out = model(aug(batch, frames=[vtx.aug.sample_frames(len(c), 8, 4) for c in decoded]))
 
+Decoded 4:2:0 frames: no decoder yields RGB -- ffmpeg-based readers get [T,H,W,3] by a colour conversion on the CPU workers
+(dataset.py:101-113,163), the GPU's decode engines write NV12 -- so every pipeline also takes a list (or tuple) of ``vtx.YUVClip``,
+NV12 or I420 planes as the decoder left them, of their own sizes, pitches and matrices, wherever it takes a list of uint8 clips:
+half the bytes over PCIe and into the resampler, which converts each tap in registers (libvtx_yuv.so: csrc/yuv.hip,
+include/vtx_yuv.h) and returns the same uniform uint8 RGB result, byte for byte that of the converted clips
+(``ops.yuv420_to_rgb_u8``).  A list holds tensors or YUVClip, not both.
+
+    batch = [vtx.YUVClip(y.cuda(non_blocking=True), uv.cuda(non_blocking=True)) for y, uv in decoded_nv12]      # matrix='bt601'
+    out = model(aug(batch, frames=[vtx.aug.sample_frames(len(c), 8, 4) for c in batch]))
+
 Not built: RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations.
 """
 import math
@@ -362,8 +372,9 @@ def _randaug_plan(draws, H, W):
 def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None, lefts=None):
     """Tables (and colour / RandAugment records) to the device in one copy, then the kernels.  With ``frames`` (int32 [B,T]) or
     ``lefts`` (int32 [B,V]: the x tables then cover the whole resized row and out_hw[1] is the width of a view) the resampling is
-    clip_views_u8's, and its [B,V,T,H,W,3] is returned as [B*V,T,H,W,3].  ``clips`` a list: clips_views_u8's, always; the
-    pointer table and geometry travel at the front of the same copy (the x table of clip b holds xspecs[b][6] columns)."""
+    clip_views_u8's, and its [B,V,T,H,W,3] is returned as [B*V,T,H,W,3].  ``clips`` a list: clips_views_u8's, always (of YUVClip:
+    clips_views_yuv's); the pointer table and geometry travel at the front of the same copy (the x table of clip b holds
+    xspecs[b][6] columns)."""
     ragged = isinstance(clips, (list, tuple))
     xf, xc, xw = _tables(xspecs, mode, antialias)
     yf, yc, yw = _tables(yspecs, mode, antialias)
@@ -390,7 +401,7 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None
     if ragged:                                               # every check of the list happens here, before anything is enqueued
         clips = ops.clips_table(clips, [s[6] for s in xspecs], 'vtx.aug')
         parts.insert(0, clips.host)                          # first: the 8-byte pointers are aligned there
-    dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.kept[0].device if ragged else clips.device)
+    dev = ops.upload_i32(np.concatenate([p.reshape(-1) for p in parts]), clips.device)
     views, at = [], 0
     for p in parts:
         views.append(dev[at:at + p.size].view(p.shape))
@@ -402,7 +413,8 @@ def _run(clips, xspecs, yspecs, out_hw, mode, antialias, draws=None, frames=None
     if gather:
         at = len(parts) - (1 if frames is None else 2)
         if ragged:
-            out = ops.clips_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab, table=table)
+            views_of = ops.clips_views_yuv if clips.yuv else ops.clips_views_u8
+            out = views_of(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab, table=table)
         else:
             out = ops.clip_views_u8(clips, None if frames is None else views[at + 1], views[at], out_hw[1], xtab, ytab)
         out = out.view((-1,) + tuple(out.shape[2:]))
@@ -435,7 +447,7 @@ def _check_clips(clips):
 
 
 def _check_clip_list(clips, frames):
-    """A list of clips [Ts_b,Hs_b,Ws_b,3] and its frames= -> (B, [Hs_b], [Ws_b], int32 frames [B,T] or None).  Host checks of types,
+    """A list of clips [Ts_b,Hs_b,Ws_b,3] (or of YUVClip) and its frames= -> (B, [Hs_b], [Ws_b], int32 frames [B,T] or None).  Host checks of types,
     shapes and indices; where the tensors live is checked with everything else before the upload (ops.clips_table)."""
     shapes = ops.clip_list_shapes(clips, 'vtx.aug')
     frames = _check_frames_ragged(frames, [s[0] for s in shapes])
@@ -447,7 +459,7 @@ class ClipAugment:
     that function's arguments and defaults; ``scale=(0.5, 1.0), color_jitter=None`` is the ``mim`` branch of
     data_trainer.py:61-63; a truthy ``auto_augment`` (the -auto_augment flag, data_trainer.py:82) puts RandAugment() in the place
     of the ColorJitter, whatever the string says.  uint8 CUDA [B,T,Hs,Ws,3], or a list of B uint8 CUDA clips [Ts_b,Hs_b,Ws_b,3] of
-    their own sizes, -> uint8 CUDA [B,T,img_size,img_size,3]."""
+    their own sizes, or a list of B ``vtx.YUVClip`` (decoded 4:2:0 planes), -> uint8 CUDA [B,T,img_size,img_size,3]."""
 
     def __init__(self, img_size=224, scale=None, ratio=None, hflip=0.5, color_jitter=0.4, interpolation='bicubic', antialias=False,
                  auto_augment=None):

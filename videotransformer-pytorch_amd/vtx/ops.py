@@ -592,6 +592,98 @@ class MixedClip:
         return f'MixedClip(uint8 {tuple(self.clip.shape)} on {self.clip.device}, lam={self.lam!r})'
 
 
+#: (matrix, full_range) -> (y_off, c_y, c_rv, c_gu, c_gv, c_bu) of include/vtx_yuv.h: each within one step of its float64 matrix
+#: rounded once, over all 2^24 triples (tests/test_yuv_host.py)
+YUV_MATRICES = {('bt601', False): (16, 298, 409, 100, 208, 516), ('bt709', False): (16, 298, 459, 55, 136, 541),
+                ('bt601', True): (0, 256, 359, 88, 183, 454), ('bt709', True): (0, 256, 403, 48, 120, 475)}
+
+
+def _plane_stride(t, dim, default):
+    """Stride of ``dim`` in elements; an axis of one element has no stride worth reading."""
+    return int(t.stride(dim)) if t.shape[dim] > 1 else int(default)
+
+
+class YUVClip:
+    """A decoded 4:2:0 clip as the decoder left it, for the resampler to convert tap by tap (include/vtx_yuv.h has the
+    contract): ``y`` uint8 [Ts,Hs,Ws]; I420: ``u`` and ``v`` uint8 [Ts,Hc,Wc]; NV12 (``v=None``): ``u`` the interleaved uint8
+    [Ts,Hc,Wc,2] plane; Hc = (Hs + 1) // 2, Wc = (Ws + 1) // 2, odd sizes allowed.  Device tensors on the current device, read
+    in place: row pitches and frame strides are the tensors' strides (a decoder's padded line size is a slice of the wider
+    buffer), only the innermost stride is fixed: 1, and 2 for NV12's chroma columns.  ``matrix``: 'bt601' (the default: what
+    swscale assumes for an untagged stream) or 'bt709', limited range unless ``full_range``; or six integers (y_off, c_y, c_rv,
+    c_gu, c_gv, c_bu), 0 <= y_off <= 255 and |c| <= 4096.  Byte parity with a particular decoder's own RGB output is not
+    claimed (chroma upsampling, rounding and dither differ among them).
+
+    A plain carrier like MixedClip, not a tensor: ``vtx.aug.ClipAugment`` / ``ClipEval`` / ``ClipTest`` take a list of them
+    wherever they take a list of uint8 clips; ``ops.yuv420_to_rgb_u8`` gives the RGB frames.  The models, Mixup and hog_targets
+    take the resampler's RGB output, not this."""
+    __slots__ = ('y', 'u', 'v', 'matrix')
+
+    def __init__(self, y, u, v=None, matrix='bt601', full_range=False):
+        planes = [('y', y), ('u', u)] + ([] if v is None else [('v', v)])
+        for n, p in planes:
+            if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8:
+                raise TypeError(f'YUVClip: {n} must be a uint8 tensor, got {getattr(p, "dtype", type(p).__name__)}')
+        if y.ndim != 3 or y.numel() == 0:
+            raise ValueError(f'YUVClip: y must be a non-empty [Ts,Hs,Ws], got {tuple(y.shape)}')
+        Ts, Hs, Ws = y.shape
+        Hc, Wc = (Hs + 1) // 2, (Ws + 1) // 2
+        want = (Ts, Hc, Wc, 2) if v is None else (Ts, Hc, Wc)
+        for n, p in planes[1:]:
+            if tuple(p.shape) != want:
+                raise ValueError(f'YUVClip: {n} must be {want} for a luma of {(Ts, Hs, Ws)}' + (' (NV12: v=None)' if v is None else '') +
+                                 f', got {tuple(p.shape)}')
+        if v is None:
+            inner = (_plane_stride(u, 3, 1), _plane_stride(u, 2, 2))
+            if inner != (1, 2):
+                raise ValueError(f'YUVClip: the NV12 plane must have U and V adjacent and chroma columns 2 bytes apart, got strides {u.stride()}')
+        for n, p in planes if v is not None else planes[:1]:
+            if _plane_stride(p, 2, 1) != 1:
+                raise ValueError(f'YUVClip: the innermost stride of {n} must be 1, got strides {p.stride()}')
+        if v is not None and [_plane_stride(u, d, 0) for d in (0, 1)] != [_plane_stride(v, d, 0) for d in (0, 1)]:
+            raise ValueError(f'YUVClip: u and v must share their row pitch and frame stride, got strides {u.stride()} and {v.stride()}')
+        for n, p, row in [('y', y, Ws), ('u', u, Wc * (2 if v is None else 1))]:
+            pitch, frame = _plane_stride(p, 1, row), _plane_stride(p, 0, 0)
+            if pitch < row or not 0 <= frame < 2 ** 31 or pitch >= 2 ** 31:
+                raise ValueError(f'YUVClip: {n}: a row pitch of {pitch} (rows of {row} bytes) and a frame stride of {frame} are not supported: '
+                                 f'pitch >= row, 0 <= frame stride < 2^31')
+        if isinstance(matrix, str):
+            if (matrix, bool(full_range)) not in YUV_MATRICES:
+                raise ValueError(f"YUVClip: matrix {matrix!r}: 'bt601', 'bt709' or six integers")
+            m = YUV_MATRICES[(matrix, bool(full_range))]
+        else:
+            try:
+                m = tuple(matrix)
+            except TypeError:
+                raise TypeError(f"YUVClip: matrix must be 'bt601', 'bt709' or six integers, got {type(matrix).__name__}") from None
+            if len(m) != 6 or any(isinstance(c, bool) or not isinstance(c, int) for c in m):
+                raise TypeError(f'YUVClip: matrix must be six integers (y_off, c_y, c_rv, c_gu, c_gv, c_bu), got {m!r}')
+            if not 0 <= m[0] <= 255 or any(abs(c) > 4096 for c in m[1:]):
+                raise ValueError(f'YUVClip: matrix {m}: 0 <= y_off <= 255 and |c| <= 4096 keep the int32 sums in range')
+        need_cuda(y, u, v)
+        self.y, self.u, self.v, self.matrix = y, u, v, m
+
+    nv12 = property(lambda self: self.v is None)
+    planes = property(lambda self: (self.y, self.u) if self.v is None else (self.y, self.u, self.v))
+    shape = property(lambda self: tuple(self.y.shape))
+    device = property(lambda self: self.y.device)
+
+    def __len__(self):
+        return self.y.shape[0]
+
+    def record(self, Wr=0):
+        """The clip's vtx_yuv420_clip record (include/vtx_yuv.h) as int32 [22]; ``Wr``: the columns of its resized row."""
+        import numpy as np
+        Ts, Hs, Ws = self.shape
+        step = 2 if self.nv12 else 1
+        ptrs = np.array([self.y.data_ptr(), self.u.data_ptr(), self.u.data_ptr() + 1 if self.nv12 else self.v.data_ptr()], dtype=np.uint64)
+        nums = [Ts, Hs, Ws, int(Wr), _plane_stride(self.y, 1, Ws), _plane_stride(self.y, 0, 0),
+                _plane_stride(self.u, 1, (Ws + 1) // 2 * step), _plane_stride(self.u, 0, 0), step] + list(self.matrix) + [0]
+        return np.concatenate([ptrs.view(np.int32), np.array(nums, dtype=np.int32)])
+
+    def __repr__(self):
+        return f'YUVClip({"NV12" if self.nv12 else "I420"} {self.shape} on {self.device}, matrix={self.matrix})'
+
+
 def clip_dims(clip):
     """(B, T, C, H, W) of a float [B,T,C,H,W] or a uint8 channels-last [B,T,H,W,3] clip (or the MixedClip of one)."""
     if clip.dtype == torch.uint8:
@@ -994,6 +1086,11 @@ def clip_list_shapes(clips, what):
         raise TypeError(f'{what}: a list or tuple of uint8 [T,H,W,3] clips expected, got {type(clips).__name__}')
     if len(clips) == 0:
         raise ValueError(f'{what}: an empty list of clips')
+    if any(isinstance(c, YUVClip) for c in clips):               # a list of 4:2:0 clips (clips_views_yuv): all of them are
+        for b, c in enumerate(clips):
+            if not isinstance(c, YUVClip):
+                raise TypeError(f'{what}: clip {b} is a {type(c).__name__} beside YUVClip entries: a list holds tensors or YUVClip, not both')
+        return [c.shape for c in clips]
     for b, c in enumerate(clips):
         if not isinstance(c, torch.Tensor):
             raise TypeError(f'{what}: clip {b} is a {type(c).__name__}, not a tensor')
@@ -1007,20 +1104,32 @@ class ClipTable:
     clips made contiguous (referenced here until the launch is enqueued); ``shapes``: [(Ts_b, Hs_b, Ws_b)]; ``widths``: the columns
     of each clip's resized row; ``host``: int32 array [6 * B] -- the B base pointers as little-endian int32 pairs, then B records
     (Ts_b, Hs_b, Ws_b, widths[b]).  The pointers come FIRST: whoever packs ``host`` into a larger upload puts it at the front,
-    where the 8-byte loads of the pointers are aligned.  Only ``clips_table`` makes one."""
-    __slots__ = ('kept', 'shapes', 'widths', 'host')
+    where the 8-byte loads of the pointers are aligned.  Only ``clips_table`` makes one.
+
+    Of a list of ``YUVClip`` (``yuv`` is then True): ``kept`` holds the carriers, whose planes are read in place, and ``host`` is
+    int32 [22 * B], the B records vtx_clips_views_yuv420 reads (include/vtx_yuv.h: each begins with its three pointers)."""
+    __slots__ = ('kept', 'shapes', 'widths', 'host', 'yuv')
+
+    @property
+    def device(self):
+        return self.kept[0].device
 
 
 def clips_table(clips, widths, what='clips_views_u8'):
-    """list or tuple of uint8 CUDA clips [Ts_b,Hs_b,Ws_b,3] on the current device, B row widths -> ClipTable.  Host only: nothing
-    is enqueued but the copies of entries that are not contiguous."""
+    """list or tuple of uint8 CUDA clips [Ts_b,Hs_b,Ws_b,3] on the current device -- or of YUVClip --, B row widths -> ClipTable.
+    Host only: nothing is enqueued but the copies of entries that are not contiguous."""
     import numpy as np
     t = ClipTable()
     t.shapes = clip_list_shapes(clips, what)
-    need_cuda(*clips)
+    t.yuv = isinstance(clips[0], YUVClip)
+    need_cuda(*([p for c in clips for p in c.planes] if t.yuv else clips))
     t.widths = [int(w) for w in widths]
     if len(t.widths) != len(clips):
         raise ValueError(f'{what}: {len(t.widths)} row widths for {len(clips)} clips')
+    if t.yuv:
+        t.kept = list(clips)
+        t.host = np.concatenate([c.record(w) for c, w in zip(clips, t.widths)])
+        return t
     t.kept = [c.contiguous() for c in clips]
     ptrs = np.array([c.data_ptr() for c in t.kept], dtype=np.uint64)
     geom = np.array([s + (w,) for s, w in zip(t.shapes, t.widths)], dtype=np.int32)
@@ -1028,17 +1137,17 @@ def clips_table(clips, widths, what='clips_views_u8'):
     return t
 
 
-def _ragged_index(t, B, hi, what, device):
+def _ragged_index(t, B, hi, what, device, name='clips_views_u8'):
     """frames / left of clips_views_u8: host integers are checked row by row against 0 <= v <= hi[b] (the clip's own numbers)
     -> int32 array [B,n], not yet uploaded."""
     import numpy as np
-    a = _index_rows('clips_views_u8', t, B, what)
+    a = _index_rows(name, t, B, what)
     if isinstance(a, torch.Tensor):
         return a
     bad = ((a < 0) | (a > np.asarray(hi).reshape(B, 1))).any(axis=1)
     if bad.any():
         b = int(np.argmax(bad))
-        raise ValueError(f'clips_views_u8: {what} of clip {b} must lie in 0 .. {hi[b]}, got {int(a[b].min())} .. {int(a[b].max())}')
+        raise ValueError(f'{name}: {what} of clip {b} must lie in 0 .. {hi[b]}, got {int(a[b].min())} .. {int(a[b].max())}')
     return np.ascontiguousarray(a, dtype=np.int32)
 
 
@@ -1056,8 +1165,14 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
     geometry and whatever of frames / left came as host values, in one copy.  A caller with records of its own to upload
     (vtx.aug: tables, colour records and descriptor in one copy) passes the ``ClipTable`` of ``clips_table`` as ``clips`` and
     the int32 [6 * B] device copy of its ``host`` array as ``table``; the list is then not checked again."""
+    return _clips_views('clips_views_u8', False, clips, frames, left, width, xtab, ytab, out, widths, table)
+
+
+def _clips_views(name, yuv, clips, frames, left, width, xtab, ytab, out, widths, table):
+    """clips_views_u8 (yuv False: tensors, vtx_clips_views_u8) and clips_views_yuv (yuv True: YUVClip, vtx_clips_views_yuv420):
+    the same checks, the same upload and the same arguments behind the descriptor."""
     import numpy as np
-    name = 'clips_views_u8'
+    words = _lib.YUV_CLIP_I32 if yuv else 6                      # int32 words of the descriptor per clip
     if isinstance(clips, ClipTable):
         ct = clips
         if widths is not None:
@@ -1066,17 +1181,21 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
         if table is not None:
             raise TypeError(f'{name}: table= goes with the ClipTable it is the device copy of')
         shapes = clip_list_shapes(clips, name)                   # types and shapes before the tables' batch size is read
-        need_cuda(*clips)
         ct = None
+    if isinstance((ct.kept if ct else clips)[0], YUVClip) != yuv:
+        raise TypeError(f'{name}: a list of ' + ('YUVClip is expected, got tensors (clips_views_u8 takes those)' if yuv else
+                                                 'uint8 tensors is expected, got YUVClip (clips_views_yuv takes those)'))
+    if ct is None:
+        need_cuda(*([p for c in clips for p in c.planes] if yuv else clips))
     B, W = len(ct.kept if ct else clips), int(width)
     Wr_max, H = _table_lengths(name, B, xtab, ytab)
     if ct is None:
         ct = clips_table(clips, [Wr_max] * B if widths is None else widths, name)
-    shapes, widths, dev = ct.shapes, ct.widths, ct.kept[0].device
+    shapes, widths, dev = ct.shapes, ct.widths, ct.device
     for b, w in enumerate(widths):
         if not 0 < W <= w <= Wr_max:
             raise ValueError(f'{name}: views of {W} columns do not fit the resized row of {w} of clip {b} (the tables hold {Wr_max})')
-    left = _ragged_index(left, B, [w - W for w in widths], 'left (left + width <= the row of the clip)', dev)
+    left = _ragged_index(left, B, [w - W for w in widths], 'left (left + width <= the row of the clip)', dev, name)
     V = left.shape[1]
     if V > _lib.VIEWS_MAX:
         raise ValueError(f'{name}: {V} views, at most {_lib.VIEWS_MAX}')
@@ -1085,7 +1204,7 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
         if any(s[0] != T for s in shapes):
             raise ValueError(f'{name}: without frame indices every frame is taken and the clips must agree in length, got {[s[0] for s in shapes]}')
     else:
-        frames = _ragged_index(frames, B, [s[0] - 1 for s in shapes], 'frame indices (into the frames of the clip)', dev)
+        frames = _ragged_index(frames, B, [s[0] - 1 for s in shapes], 'frame indices (into the frames of the clip)', dev, name)
         T = frames.shape[1]
     if B * T > 65535:
         raise ValueError(f'{name}: {B} clips x {T} frames exceed the grid (65535)')
@@ -1098,24 +1217,59 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
     if table is None:
         parts = [ct.host] + [a.reshape(-1) for a in (left, frames) if isinstance(a, np.ndarray)]
         up = upload_i32(np.concatenate(parts), dev)
-        table, at = up[:6 * B], 6 * B
+        table, at = up[:words * B], words * B
         if isinstance(left, np.ndarray):
             left, at = up[at:at + left.size].view(left.shape), at + left.size
         if isinstance(frames, np.ndarray):
             frames = up[at:at + frames.size].view(frames.shape)
     else:
         need_cuda(table)
-        if (table.dtype != torch.int32 or table.ndim != 1 or table.numel() != 6 * B or not table.is_contiguous()
+        if (table.dtype != torch.int32 or table.ndim != 1 or table.numel() != words * B or not table.is_contiguous()
                 or table.data_ptr() % 8):
-            raise TypeError(f'{name}: table must be the int32 [{6 * B}] device copy of the ClipTable\'s host array, 8-byte aligned')
+            raise TypeError(f'{name}: table must be the int32 [{words * B}] device copy of the ClipTable\'s host array, 8-byte aligned')
         if isinstance(left, np.ndarray) or isinstance(frames, np.ndarray):
             raise TypeError(f'{name}: with table= frames and left are device tensors (uploaded with it)')
+    tabs = (ptr(frames), ptr(left), ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]), xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]), ptr(ytab[2]),
+            ytab[2].shape[2], stream())
+    if yuv:                                                      # 1.5 source bytes per pixel: the luma and two quarter-size chroma planes
+        src_bytes = sum(T * (s[1] * s[2] + 2 * ((s[1] + 1) // 2) * ((s[2] + 1) // 2)) for s in shapes)
+        with _timed('clips_views_yuv', nbytes=src_bytes + out.numel(), key=f'{B}x{T} yuv420->{V}x{H}x{W}'):
+            _lib.yuv_call('vtx_clips_views_yuv420', B, T, H, V, W, Wr_max, ptr(table), ptr(out), *tabs)
+        return out
     src_bytes = sum(T * s[1] * s[2] * 3 for s in shapes)
     with _timed('clips_views', nbytes=src_bytes + out.numel(), key=f'{B}x{T} ragged->{V}x{H}x{W}'):
         _lib.ragged_call('vtx_clips_views_u8', B, T, H, V, W, Wr_max, ptr(table), table.data_ptr() + 8 * B, ptr(out), ptr(frames),
                          ptr(left), ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]), xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]),
                          ptr(ytab[2]), ytab[2].shape[2], stream())
     return out                                                   # (ct.kept lived until here: the launch is enqueued)
+
+
+# ------------------------------------------------- 4:2:0 YUV clips into the resampler (csrc/yuv.hip -> libvtx_yuv.so)
+def clips_views_yuv(clips, frames, left, width, xtab, ytab, out=None, widths=None, table=None):
+    """clips_views_u8 on decoded 4:2:0 clips: ``clips`` a list or tuple of B ``YUVClip`` (NV12 and I420, sizes, pitches and
+    matrices may differ from clip to clip) -> uint8 [B,V,T,H,width,3], byte for byte clips_views_u8 on the clips
+    ``yuv420_to_rgb_u8`` would write, which never exist: each tap is converted in registers.  Every other argument, every check
+    and the one upload are clips_views_u8's; ``table``: the int32 [22 * B] device copy of the ClipTable's ``host`` array."""
+    return _clips_views('clips_views_yuv', True, clips, frames, left, width, xtab, ytab, out, widths, table)
+
+
+def yuv420_to_rgb_u8(clip, out=None):
+    """The plain conversion of one ``YUVClip`` -> uint8 [Ts,Hs,Ws,3] (include/vtx_yuv.h: nearest chroma siting, the clip's
+    integer matrix), for callers that want the RGB frames.  ``out``: a contiguous uint8 [Ts,Hs,Ws,3] device tensor to write into."""
+    if not isinstance(clip, YUVClip):
+        raise TypeError(f'yuv420_to_rgb_u8: a YUVClip is expected, got {type(clip).__name__}')
+    need_cuda(*clip.planes)
+    Ts, Hs, Ws = clip.shape
+    if out is None:
+        out = torch.empty(Ts, Hs, Ws, 3, dtype=torch.uint8, device=clip.device)
+    else:
+        need_cuda(out)
+        if out.dtype != torch.uint8 or tuple(out.shape) != (Ts, Hs, Ws, 3) or not out.is_contiguous():
+            raise TypeError(f'yuv420_to_rgb_u8: out must be a contiguous uint8 {(Ts, Hs, Ws, 3)} tensor, got {out.dtype} {tuple(out.shape)}')
+    rec = upload_i32(clip.record(), clip.device)
+    with _timed('yuv420_to_rgb', nbytes=Ts * (Hs * Ws + 2 * ((Hs + 1) // 2) * ((Ws + 1) // 2)) + out.numel(), key=f'{Ts}x{Hs}x{Ws}'):
+        _lib.yuv_call('vtx_yuv420_to_rgb_u8', ptr(rec), Ts, Hs, Ws, ptr(out), stream())
+    return out
 
 
 # ------------------------------------------------- clip-batch mixing, accuracy (csrc/head.hip)
