@@ -57,6 +57,14 @@ clip and then (a), (c) `vtx_clips_views_yuv420` on the planes.  --parent-lib: a 
 on the same RGB clips in the same alternating rounds: its device code is this commit's, so (p) and (a) must agree within (p)'s own
 spread.  (a), (b) and (c) are checked for equal bytes first.  Per path the kernels alone (HIP events around each launch), the whole
 call (host clock around `ClipEval` on the list, ending in a synchronise) and the bytes its kernels have to move.
+
+    python tools/aug_bench.py --yuv10 [--out profiles/clip_yuv10_bench.txt]
+
+times the same batch given as decoded 10-bit planes (csrc/yuv10.hip): `vtx_clips_views_yuv10` on (P) P010 clips, (L) yuv420p10le clips and
+(M) a list that alternates P010 clips with NV12 ones, against (a) `vtx_clips_views_yuv420` on the same content as NV12 (the samples without
+their two low bits), (b) `vtx_clips_views_u8` on RGB clips converted beforehand and (c) `vtx_yuv10_to_rgb_u8` on every decoded frame and
+then (b).  (P), (L), (b) and (c) are checked for equal bytes first, the halves of (M) against (P) and (a).  Columns as for --yuv, and the
+bytes a caller uploads per batch for each form.
 """
 import argparse
 import os
@@ -722,18 +730,118 @@ def yuv_main(a):
         f.write(text)
 
 
+def yuv10_main(a):
+    import time
+    import numpy as np
+    dev = 'cuda:0'
+    B, Ts, T, S, k = a.clips, a.decoded, a.frames, a.size, a.sets
+    sizes = [(256, 340), (340, 256), (240, 320), (360, 480)]
+    hw = [sizes[b % 4] for b in range(B)]
+    ev = aug.ClipEval(img_size=S)
+    g = torch.Generator().manual_seed(0)
+    rnd = lambda *shape: torch.randint(0, 1024, shape, dtype=torch.int16, device=dev)        # 10-bit samples
+    p010s, p10les, nv12s, mixes = [], [], [], []
+    for _ in range(k):
+        planes = [(rnd(Ts, h, w), rnd(Ts, (h + 1) // 2, (w + 1) // 2, 2)) for h, w in hw]
+        msb = lambda p: (p.to(torch.int32) << 6).to(torch.int16)                         # the sample in the upper 10 bits of its word
+        p010s.append([vtx.YUVClip(msb(y), msb(uv), depth=10) for y, uv in planes])
+        p10les.append([vtx.YUVClip(y, uv[..., 0].contiguous(), uv[..., 1].contiguous(), depth=10) for y, uv in planes])
+        nv12s.append([vtx.YUVClip((y >> 2).to(torch.uint8), (uv >> 2).to(torch.uint8)) for y, uv in planes])
+        mixes.append([p010s[-1][b] if b % 8 < 4 else nv12s[-1][b] for b in range(B)])    # every size in both depths
+    rgbs = [[ops.yuv420_to_rgb_u8(c) for c in clips] for clips in p010s]
+    frames = np.stack([aug.sample_frames(Ts, T, Ts // T, generator=g) for _ in range(B)]).astype(np.int32)
+    on = lambda lists: (lambda i: ev(lists[i % k], frames=frames))
+    paths = [('(P) vtx_clips_views_yuv10 on P010', on(p010s)), ('(L) vtx_clips_views_yuv10 on yuv420p10le', on(p10les)),
+             ('(M) vtx_clips_views_yuv10 on P010 and NV12, half each', on(mixes)), ('(a) vtx_clips_views_yuv420 on NV12', on(nv12s)),
+             ('(b) vtx_clips_views_u8 on RGB clips', on(rgbs)),
+             ('(c) vtx_yuv10_to_rgb_u8 + vtx_clips_views_u8', lambda i: ev([ops.yuv420_to_rgb_u8(c) for c in p010s[i % k]], frames=frames))]
+    out = {n[:3]: fn(0) for n, fn in paths}
+    same = all(torch.equal(out[n], out['(b)']) for n in ('(P)', '(L)', '(c)'))
+    ten = torch.tensor([b % 8 < 4 for b in range(B)], device=dev)
+    same_mix = torch.equal(out['(M)'][ten], out['(P)'][ten]) and torch.equal(out['(M)'][~ten], out['(a)'][~ten])
+    assert same and same_mix, 'the routes differ'
+    del out
+    for i in range(a.warmup):
+        for _, fn in paths:
+            fn(i)
+    torch.cuda.synchronize()
+    wall = {n: [] for n, _ in paths}
+    turn = lambda r: paths[r % len(paths):] + paths[:r % len(paths)]   # the order rotates: no path always runs behind the same neighbour
+    for r in range(a.rounds):                                  # alternating: what else runs on the machine hits all alike
+        for n, fn in turn(r):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            torch.cuda.synchronize()
+            wall[n].append((time.perf_counter() - t0) * 1e6 / a.iters)
+    kern = {n: [] for n, _ in paths}                           # events around every launch, in rounds of their own: they slow the host
+    for r in range(a.rounds):
+        for n, fn in turn(r):
+            ops.profile_start(('clips_views', 'clips_views_yuv', 'clips_views_yuv10', 'yuv10_to_rgb'))
+            for i in range(a.iters):
+                fn(r * a.iters + i)
+            torch.cuda.synchronize()
+            tot = ops.profile_totals(ops.profile_stop())
+            kern[n].append(sum(v[1] for v in tot.values()) * 1e3 / a.iters)
+    px = [h * w for h, w in hw]
+    px_sel, px_all = T * sum(px), Ts * sum(px)
+    px_ten = T * sum(p for b, p in enumerate(px) if b % 8 < 4)
+    out_b = B * T * S * S * 3
+    nbytes = {'(P)': 3 * px_sel + out_b, '(L)': 3 * px_sel + out_b, '(M)': 3 * px_ten + int(1.5 * (px_sel - px_ten)) + out_b,
+              '(a)': int(1.5 * px_sel) + out_b, '(b)': 3 * px_sel + out_b, '(c)': 3 * px_all + 3 * px_all + 3 * px_sel + out_b}
+    what = {'(P)': 'selected frames of the planes read (1.5 samples of 2 bytes per pixel), result written', '(L)': 'as (P)',
+            '(M)': 'as (P) for one half of the clips, 1.5 bytes per pixel for the other', '(a)': 'selected frames of the planes read (1.5 bytes per pixel), result written',
+            '(b)': 'selected RGB frames read, result written',
+            '(c)': f'all {Ts} decoded frames of every clip converted: planes read, RGB written; then as (b)'}
+    up_ten = Ts * sum(p for b, p in enumerate(px) if b % 8 < 4)
+    lines = [f'decoded 10-bit 4:2:0 clips, {B} clips, {T} of {Ts} decoded frames each, sizes {sizes} in equal shares, ClipEval({S}) '
+             f'(Resize({ev.scale_size}) + centre crop), bicubic, antialias off; {torch.cuda.get_device_name(0)}',
+             f'{a.rounds} rounds of {a.iters} batches per path, the paths in alternating rounds of one run whose order rotates from round to round, after {a.warmup} warm-up batches each; '
+             f'{k} source sets in rotation: {sum(p.numel() * 2 for c in p010s[0] for p in c.planes) / 2**20:.0f} MiB of 10-bit planes, '
+             f'{sum(p.numel() for c in nv12s[0] for p in c.planes) / 2**20:.0f} MiB of NV12 planes and {sum(c.numel() for c in rgbs[0]) / 2**20:.0f} MiB of RGB each',
+             f'same bytes from (P), (L), (b) and (c): {same}; the 10-bit clips of (M) as in (P), its 8-bit clips as in (a): {same_mix}',
+             'kernel = HIP events around each launch of the path, summed per batch, in rounds of their own; wall = host clock around the whole '
+             'call (tables, checks, one upload, the launches), ending in a synchronise; all per batch; spread = (max - min) / median over the rounds',
+             'bytes = what the kernels of a path have to move, whole frames counted',
+             f'upload a caller makes per batch before the call (all {Ts} decoded frames): P010 or yuv420p10le {3 * px_all / 1e6:.1f} MB, the mix '
+             f'{(3 * up_ten + 1.5 * (px_all - up_ten)) / 1e6:.1f} MB, NV12 {1.5 * px_all / 1e6:.1f} MB, RGB24 (after a CPU conversion) {3 * px_all / 1e6:.1f} MB',
+             '']
+    med, spread = {}, {}
+    for n, _ in paths:
+        key, kr, w = n[:3], kern[n], wall[n]
+        mk, mw = statistics.median(kr), statistics.median(w)
+        med[key], spread[key] = (mk, mw), ((max(kr) - min(kr)) / mk, (max(w) - min(w)) / mw)
+        lines.append(f'{n:<54} kernel median {mk:8.1f} us  min {min(kr):8.1f}  max {max(kr):8.1f}  spread {100 * spread[key][0]:5.1f} %   '
+                     f'wall median {mw:8.1f} us  min {min(w):8.1f}  max {max(w):8.1f}  spread {100 * spread[key][1]:5.1f} %   '
+                     f'{nbytes[key] / 1e6:7.1f} MB ({what[key]})  {nbytes[key] / mk / 1e6:5.2f} TB/s')
+    lines.append('')
+    for key in ('(P)', '(L)', '(M)'):
+        mk, mw = med[key]
+        d, bar = mk - med['(b)'][0], spread['(b)'][0] * med['(b)'][0]
+        lines.append(f'{key} kernel: {mk / med["(a)"][0]:.3f} x (a), {mk / med["(b)"][0]:.3f} x (b) ({d:+.1f} us against (b)\'s own spread of {bar:.1f} us: '
+                     + ('not slower' if d <= bar else 'SLOWER') + f'), {mk / med["(c)"][0]:.3f} x (c);  whole call: {mw / med["(a)"][1]:.3f} x (a), '
+                     f'{mw / med["(b)"][1]:.3f} x (b), {mw / med["(c)"][1]:.3f} x (c)')
+    text = '\n'.join(lines) + '\n'
+    print(text, end='')
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(text)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--yuv10', action='store_true', help='time a batch of decoded 10-bit 4:2:0 clips against the 8-bit and RGB routes (-> profiles/clip_yuv10_bench.txt)')
     ap.add_argument('--yuv', action='store_true', help='time a batch of decoded 4:2:0 clips against the RGB route (-> profiles/clip_yuv_bench.txt)')
     ap.add_argument('--parent-lib', default=None, help='--yuv: a libvtx_ragged.so built at the parent commit, timed beside this one')
     ap.add_argument('--ragged', action='store_true', help='time one call on a list of clips of differing size against one call per clip (-> profiles/clip_ragged_bench.txt)')
     ap.add_argument('--stem', action='store_true', help='time the uint8 stem gather and hog_targets against the float routes (-> profiles/stem_u8_bench.txt)')
     ap.add_argument('--mix', action='store_true', help='time Mixup / CutMix on uint8 clips against the float route (-> profiles/clip_mix_bench.txt)')
     ap.add_argument('--views', action='store_true', help='time clip_views_u8 against the composition it replaces (-> profiles/clip_views_bench.txt)')
-    ap.add_argument('--decoded', type=int, default=32, help='--views, --ragged, --yuv: decoded frames per clip')
+    ap.add_argument('--decoded', type=int, default=32, help='--views, --ragged, --yuv, --yuv10: decoded frames per clip')
     ap.add_argument('--short-side', type=int, default=256, help='--views: the Resize of the test pipeline')
     ap.add_argument('--randaug', action='store_true', help='time the RandAugment kernels instead (-> profiles/clip_randaug_bench.txt)')
-    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views, --stem, --ragged and --yuv')
+    ap.add_argument('--clips', type=int, default=None, help='default 96; 32 with --views, --stem, --ragged, --yuv and --yuv10')
     ap.add_argument('--frames', type=int, default=None, help='default 8; 16 with --stem')
     ap.add_argument('--src', type=int, nargs=2, default=(256, 340))
     ap.add_argument('--size', type=int, default=224)
@@ -745,13 +853,15 @@ def main():
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.clips is None:
-        a.clips = 32 if a.views or a.stem or a.ragged or a.yuv else 96
+        a.clips = 32 if a.views or a.stem or a.ragged or a.yuv or a.yuv10 else 96
     if a.frames is None:
         a.frames = 16 if a.stem else 8
     if a.out is None:
-        a.out = os.path.join(ROOT, 'profiles', 'clip_yuv_bench.txt' if a.yuv else 'clip_ragged_bench.txt' if a.ragged else 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
+        a.out = os.path.join(ROOT, 'profiles', 'clip_yuv10_bench.txt' if a.yuv10 else 'clip_yuv_bench.txt' if a.yuv else 'clip_ragged_bench.txt' if a.ragged else 'stem_u8_bench.txt' if a.stem else 'clip_mix_bench.txt' if a.mix else 'clip_views_bench.txt' if a.views else
                              'clip_randaug_bench.txt' if a.randaug else 'clip_aug_bench.txt')
     assert torch.cuda.is_available(), 'aug_bench needs a GPU'
+    if a.yuv10:
+        return yuv10_main(a)
     if a.yuv:
         return yuv_main(a)
     if a.ragged:

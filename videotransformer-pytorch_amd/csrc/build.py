@@ -33,7 +33,8 @@ SIDE = ['aug',        # clip augmentation: crop-resize + flip, colour jitter
         'stem',       # the MViT stem gather from bytes, HOG of selected frames (hog_kernel.h, shared with hog.hip)
         'ragged',     # views of clips that differ in source size
         'dropout',    # mask, DropPath scale and residual in one launch, the mask regenerated in the backward
-        'yuv']        # 4:2:0 YUV clips (NV12, I420) into the resampler: colour conversion on each tap
+        'yuv',        # 4:2:0 YUV clips (NV12, I420) into the resampler: colour conversion on each tap
+        'yuv10']      # 10-bit 4:2:0 clips (P010, yuv420p10le), alone or mixed with 8-bit ones: one record type, one launch
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-fno-gpu-rdc', '-Wno-unused-result', '-Wno-unused-value', '-Wno-inline-asm',
          '-Wno-cuda-compat']
 EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contraction
@@ -44,7 +45,8 @@ EXTRA = {'hog.hip': ['-ffp-contract=off'],         # bit-exact HOG: no fma contr
          'stem.hip': ['-ffp-contract=off'],        # hog_kernel.h as hog.hip compiles it; normalise: three roundings per tap
          'ragged.hip': ['-ffp-contract=off'],      # views.hip's weighted sums, byte for byte
          'dropout.hip': ['-ffp-contract=off'],     # mask, scale, row scale, residual: four float32 operations, one rounding on the store
-         'yuv.hip': ['-ffp-contract=off']}         # ragged.hip's weighted sums on converted taps, byte for byte
+         'yuv.hip': ['-ffp-contract=off'],         # ragged.hip's weighted sums on converted taps, byte for byte
+         'yuv10.hip': ['-ffp-contract=off']}       # likewise, on taps of either depth
 # (output, sources, link flags).  -Bsymbolic: a side library's own definitions of the helpers common.h declares, whatever else
 # the process has loaded
 LIBRARIES = [(OUT, SOURCES, [])] + [(os.path.join(PKG, f'libvtx_{n}.so'), [n + '.hip'], ['-Wl,-Bsymbolic']) for n in SIDE]

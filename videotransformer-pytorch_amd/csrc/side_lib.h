@@ -1,4 +1,4 @@
-// side_lib.h -- what every library beside libvtx.so (aug, randaug, views, mix, stem, ragged, dropout, yuv) defines for itself.
+// side_lib.h -- what every library beside libvtx.so (aug, randaug, views, mix, stem, ragged, dropout, yuv, yuv10) defines for itself.
 //
 // common.h declares vtx::set_error and vtx::check_launch; api.hip holds libvtx.so's definitions.  A side library shares
 // nothing with libvtx.so, so it carries its own: VTX_SIDE_LIB(name), written once at file scope of the library's one

@@ -257,6 +257,16 @@ YUV_SIGNATURES = {
     'vtx_yuv420_to_rgb_u8': (ci, [vp, ci, ci, ci, vp, vp]),
 }
 
+# libvtx_yuv10.so (include/vtx_yuv10.h, csrc/yuv10.hip): 10-bit 4:2:0 clips, alone or mixed with 8-bit ones, into the resampler, the tenth library.  Must list every symbol the header declares.
+YUV10_LIB_PATH = os.environ.get('VTX_YUV10_LIB', os.path.join(_PKG, 'libvtx_yuv10.so'))
+YUV10_CLIP_I32 = 24         # int32 words of one vtx_yuv10_clip record: 3 pointers, Ts Hs Ws Wr, 5 strides, depth, shift, 6 matrix entries, 1 reserved
+YUV10_SIGNATURES = {
+    'vtx_yuv10_version': (ci, []),
+    'vtx_yuv10_last_error_string': (C.c_char_p, []),
+    'vtx_clips_views_yuv10': (ci, [ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp]),
+    'vtx_yuv10_to_rgb_u8': (ci, [vp, ci, ci, ci, vp, vp]),
+}
+
 # key -> (name of the path constant, signatures): every library beside libvtx.so.  The path is read when the library is
 # first loaded.  libvtx_<key>.so exports vtx_<key>_version and vtx_<key>_last_error_string beside its entry points.
 _SIDE = {
@@ -268,6 +278,7 @@ _SIDE = {
     'ragged': ('RAGGED_LIB_PATH', RAGGED_SIGNATURES),
     'dropout': ('DROPOUT_LIB_PATH', DROPOUT_SIGNATURES),
     'yuv': ('YUV_LIB_PATH', YUV_SIGNATURES),
+    'yuv10': ('YUV10_LIB_PATH', YUV10_SIGNATURES),
 }
 _lib = None
 _side = {}
@@ -320,6 +331,7 @@ load_stem, stem_call = partial(_load_side, 'stem'), partial(_side_call, 'stem')
 load_ragged, ragged_call = partial(_load_side, 'ragged'), partial(_side_call, 'ragged')
 load_dropout, dropout_call = partial(_load_side, 'dropout'), partial(_side_call, 'dropout')
 load_yuv, yuv_call = partial(_load_side, 'yuv'), partial(_side_call, 'yuv')
+load_yuv10, yuv10_call = partial(_load_side, 'yuv10'), partial(_side_call, 'yuv10')
 aug_check = partial(_side_check, 'aug')
 
 

@@ -49,6 +49,10 @@ include/vtx_yuv.h) and returns the same uniform uint8 RGB result, byte for byte 
     batch = [vtx.YUVClip(y.cuda(non_blocking=True), uv.cuda(non_blocking=True)) for y, uv in decoded_nv12]      # matrix='bt601'
     out = model(aug(batch, frames=[vtx.aug.sample_frames(len(c), 8, 4) for c in batch]))
 
+10-bit streams (HEVC Main10, AV1; P010 from the decode engines, yuv420p10le from ffmpeg-based readers) are int16 / uint16 planes
+of the same shapes, ``vtx.YUVClip(y, uv, depth=10)``, and go into the same list beside 8-bit clips: a list with a 10-bit clip in
+it is one launch of libvtx_yuv10.so (csrc/yuv10.hip, include/vtx_yuv10.h) for all of its clips.
+
 Not built: RandomGrayscale, hue jitter, RandAugment's ``fill`` and other interpolations.
 """
 import math

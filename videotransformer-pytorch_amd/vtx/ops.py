@@ -603,6 +603,29 @@ def _plane_stride(t, dim, default):
     return int(t.stride(dim)) if t.shape[dim] > 1 else int(default)
 
 
+#: the same table for 10-bit samples (include/vtx_yuv10.h): 12 fractional bits, ``yuv10_matrix`` of the two standards; each within
+#: one step of its float64 matrix rounded once (tests/test_yuv10_host.py)
+YUV10_MATRICES = {('bt601', False): (64, 1192, 1634, 401, 832, 2066), ('bt709', False): (64, 1192, 1836, 218, 546, 2163),
+                  ('bt601', True): (0, 1021, 1431, 351, 729, 1809), ('bt709', True): (0, 1021, 1608, 191, 478, 1895)}
+#: depth -> (largest y_off, largest |c|) of its conversion contract
+_YUV_BOUNDS = {8: (255, 4096), 10: (1023, 16384)}
+
+
+def yuv10_matrix(kr, kb, full_range=False):
+    """Luma weights (Kr, Kb) of a standard -> the six integers (y_off, c_y, c_rv, c_gu, c_gv, c_bu) of the 10-bit contract
+    (include/vtx_yuv10.h): floor(4096 * k + 0.5) of the float64 matrix -- limited range: luma 64 .. 940 scaled by 255 / 876, chroma
+    by 255 / 896; full range: 255 / 1023 for both.  (0.299, 0.114) and (0.2126, 0.0722) give ``YUV10_MATRICES``; BT.2020 is
+    (0.2627, 0.0593)."""
+    import math
+    kr, kb = float(kr), float(kb)
+    kg = 1.0 - kr - kb
+    if not (0.0 < kr < 1.0 and 0.0 < kb < 1.0 and kg > 0.0):
+        raise ValueError(f'yuv10_matrix: luma weights kr={kr}, kb={kb} must be positive and sum to less than 1')
+    sy, sc = (255.0 / 1023.0, 255.0 / 1023.0) if full_range else (255.0 / 876.0, 255.0 / 896.0)
+    ks = (sy, 2.0 * (1.0 - kr) * sc, 2.0 * kb * (1.0 - kb) / kg * sc, 2.0 * kr * (1.0 - kr) / kg * sc, 2.0 * (1.0 - kb) * sc)
+    return (0 if full_range else 64,) + tuple(int(math.floor(4096.0 * k + 0.5)) for k in ks)
+
+
 class YUVClip:
     """A decoded 4:2:0 clip as the decoder left it, for the resampler to convert tap by tap (include/vtx_yuv.h has the
     contract): ``y`` uint8 [Ts,Hs,Ws]; I420: ``u`` and ``v`` uint8 [Ts,Hc,Wc]; NV12 (``v=None``): ``u`` the interleaved uint8
@@ -613,16 +636,30 @@ class YUVClip:
     c_gu, c_gv, c_bu), 0 <= y_off <= 255 and |c| <= 4096.  Byte parity with a particular decoder's own RGB output is not
     claimed (chroma upsampling, rounding and dither differ among them).
 
-    A plain carrier like MixedClip, not a tensor: ``vtx.aug.ClipAugment`` / ``ClipEval`` / ``ClipTest`` take a list of them
-    wherever they take a list of uint8 clips; ``ops.yuv420_to_rgb_u8`` gives the RGB frames.  The models, Mixup and hog_targets
-    take the resampler's RGB output, not this."""
-    __slots__ = ('y', 'u', 'v', 'matrix')
+    ``depth=10`` (include/vtx_yuv10.h): the same shapes of int16 or uint16 planes (the bits are read as unsigned), one 16-bit
+    word per sample; ``v=None`` is then P010's interleaved plane, three planes are yuv420p10le.  ``msb_aligned``: the sample
+    sits in the upper 10 bits of its word (True, what P010 says) or the lower 10 (False, yuv420p10le); None takes what the
+    layout says.  The other bits of a word are ignored.  The presets are then the 10-bit ones (``YUV10_MATRICES``), six
+    integers obey 0 <= y_off <= 1023 and |c| <= 16384 (``yuv10_matrix`` makes them from a standard's luma weights).
 
-    def __init__(self, y, u, v=None, matrix='bt601', full_range=False):
+    A plain carrier like MixedClip, not a tensor: ``vtx.aug.ClipAugment`` / ``ClipEval`` / ``ClipTest`` take a list of them
+    -- 8-bit and 10-bit clips in one list -- wherever they take a list of uint8 clips; ``ops.yuv420_to_rgb_u8`` gives the RGB
+    frames.  The models, Mixup and hog_targets take the resampler's RGB output, not this."""
+    __slots__ = ('y', 'u', 'v', 'matrix', 'depth', 'shift')
+
+    def __init__(self, y, u, v=None, matrix='bt601', full_range=False, depth=8, msb_aligned=None):
+        if isinstance(depth, bool) or depth not in (8, 10):
+            raise ValueError(f'YUVClip: depth must be 8 or 10, got {depth!r} (12-bit and deeper content is not supported)')
+        if msb_aligned is not None and not isinstance(msb_aligned, bool):
+            raise ValueError(f'YUVClip: msb_aligned must be True, False or None, got {msb_aligned!r}')
+        if depth == 8 and msb_aligned:
+            raise ValueError('YUVClip: msb_aligned goes with depth=10: an 8-bit sample fills its byte')
+        dtypes, named = ((torch.uint8,), 'a uint8 tensor') if depth == 8 else ((torch.int16, torch.uint16), 'an int16 or uint16 tensor at depth=10')
+        size = 1 if depth == 8 else 2                            # bytes of a sample
         planes = [('y', y), ('u', u)] + ([] if v is None else [('v', v)])
         for n, p in planes:
-            if not isinstance(p, torch.Tensor) or p.dtype != torch.uint8:
-                raise TypeError(f'YUVClip: {n} must be a uint8 tensor, got {getattr(p, "dtype", type(p).__name__)}')
+            if not isinstance(p, torch.Tensor) or p.dtype not in dtypes:
+                raise TypeError(f'YUVClip: {n} must be {named}, got {getattr(p, "dtype", type(p).__name__)}')
         if y.ndim != 3 or y.numel() == 0:
             raise ValueError(f'YUVClip: y must be a non-empty [Ts,Hs,Ws], got {tuple(y.shape)}')
         Ts, Hs, Ws = y.shape
@@ -635,21 +672,23 @@ class YUVClip:
         if v is None:
             inner = (_plane_stride(u, 3, 1), _plane_stride(u, 2, 2))
             if inner != (1, 2):
-                raise ValueError(f'YUVClip: the NV12 plane must have U and V adjacent and chroma columns 2 bytes apart, got strides {u.stride()}')
+                raise ValueError(f'YUVClip: the {"NV12" if size == 1 else "P010"} plane must have U and V adjacent and chroma columns 2 '
+                                 f'{"bytes" if size == 1 else "samples"} apart, got strides {u.stride()}')
         for n, p in planes if v is not None else planes[:1]:
             if _plane_stride(p, 2, 1) != 1:
                 raise ValueError(f'YUVClip: the innermost stride of {n} must be 1, got strides {p.stride()}')
         if v is not None and [_plane_stride(u, d, 0) for d in (0, 1)] != [_plane_stride(v, d, 0) for d in (0, 1)]:
             raise ValueError(f'YUVClip: u and v must share their row pitch and frame stride, got strides {u.stride()} and {v.stride()}')
         for n, p, row in [('y', y, Ws), ('u', u, Wc * (2 if v is None else 1))]:
-            pitch, frame = _plane_stride(p, 1, row), _plane_stride(p, 0, 0)
-            if pitch < row or not 0 <= frame < 2 ** 31 or pitch >= 2 ** 31:
-                raise ValueError(f'YUVClip: {n}: a row pitch of {pitch} (rows of {row} bytes) and a frame stride of {frame} are not supported: '
+            pitch, frame = _plane_stride(p, 1, row) * size, _plane_stride(p, 0, 0) * size
+            if pitch < row * size or not 0 <= frame < 2 ** 31 or pitch >= 2 ** 31:
+                raise ValueError(f'YUVClip: {n}: a row pitch of {pitch} (rows of {row * size} bytes) and a frame stride of {frame} are not supported: '
                                  f'pitch >= row, 0 <= frame stride < 2^31')
+        presets = YUV_MATRICES if depth == 8 else YUV10_MATRICES
         if isinstance(matrix, str):
-            if (matrix, bool(full_range)) not in YUV_MATRICES:
+            if (matrix, bool(full_range)) not in presets:
                 raise ValueError(f"YUVClip: matrix {matrix!r}: 'bt601', 'bt709' or six integers")
-            m = YUV_MATRICES[(matrix, bool(full_range))]
+            m = presets[(matrix, bool(full_range))]
         else:
             try:
                 m = tuple(matrix)
@@ -657,12 +696,14 @@ class YUVClip:
                 raise TypeError(f"YUVClip: matrix must be 'bt601', 'bt709' or six integers, got {type(matrix).__name__}") from None
             if len(m) != 6 or any(isinstance(c, bool) or not isinstance(c, int) for c in m):
                 raise TypeError(f'YUVClip: matrix must be six integers (y_off, c_y, c_rv, c_gu, c_gv, c_bu), got {m!r}')
-            if not 0 <= m[0] <= 255 or any(abs(c) > 4096 for c in m[1:]):
-                raise ValueError(f'YUVClip: matrix {m}: 0 <= y_off <= 255 and |c| <= 4096 keep the int32 sums in range')
+            y_max, c_max = _YUV_BOUNDS[depth]
+            if not 0 <= m[0] <= y_max or any(abs(c) > c_max for c in m[1:]):
+                raise ValueError(f'YUVClip: matrix {m}: 0 <= y_off <= {y_max} and |c| <= {c_max} keep the int32 sums in range')
         need_cuda(y, u, v)
-        self.y, self.u, self.v, self.matrix = y, u, v, m
+        self.y, self.u, self.v, self.matrix, self.depth = y, u, v, m, depth
+        self.shift = 6 if depth == 10 and (v is None if msb_aligned is None else msb_aligned) else 0
 
-    nv12 = property(lambda self: self.v is None)
+    nv12 = property(lambda self: self.v is None)                 # the interleaved layout: NV12, or P010 at depth 10
     planes = property(lambda self: (self.y, self.u) if self.v is None else (self.y, self.u, self.v))
     shape = property(lambda self: tuple(self.y.shape))
     device = property(lambda self: self.y.device)
@@ -670,8 +711,15 @@ class YUVClip:
     def __len__(self):
         return self.y.shape[0]
 
+    @property
+    def source_bytes(self):
+        """Bytes of the samples of one frame: the luma and two quarter-size chroma planes, 1 or 2 bytes each."""
+        _, Hs, Ws = self.shape
+        return (Hs * Ws + 2 * ((Hs + 1) // 2) * ((Ws + 1) // 2)) * (2 if self.depth == 10 else 1)
+
     def record(self, Wr=0):
-        """The clip's vtx_yuv420_clip record (include/vtx_yuv.h) as int32 [22]; ``Wr``: the columns of its resized row."""
+        """The clip's vtx_yuv420_clip record (include/vtx_yuv.h) as int32 [22]; ``Wr``: the columns of its resized row.  Of an
+        8-bit clip (``record10`` serves both depths)."""
         import numpy as np
         Ts, Hs, Ws = self.shape
         step = 2 if self.nv12 else 1
@@ -680,7 +728,22 @@ class YUVClip:
                 _plane_stride(self.u, 1, (Ws + 1) // 2 * step), _plane_stride(self.u, 0, 0), step] + list(self.matrix) + [0]
         return np.concatenate([ptrs.view(np.int32), np.array(nums, dtype=np.int32)])
 
+    def record10(self, Wr=0):
+        """The clip's vtx_yuv10_clip record (include/vtx_yuv10.h) as int32 [24], of a clip of either depth: pitches and frame
+        strides in bytes, the chroma step in samples, depth, shift."""
+        import numpy as np
+        Ts, Hs, Ws = self.shape
+        step, size = 2 if self.nv12 else 1, 2 if self.depth == 10 else 1
+        ptrs = np.array([self.y.data_ptr(), self.u.data_ptr(), self.u.data_ptr() + size if self.nv12 else self.v.data_ptr()], dtype=np.uint64)
+        nums = [Ts, Hs, Ws, int(Wr), _plane_stride(self.y, 1, Ws) * size, _plane_stride(self.y, 0, 0) * size,
+                _plane_stride(self.u, 1, (Ws + 1) // 2 * step) * size, _plane_stride(self.u, 0, 0) * size, step, self.depth,
+                self.shift] + list(self.matrix) + [0]
+        return np.concatenate([ptrs.view(np.int32), np.array(nums, dtype=np.int32)])
+
     def __repr__(self):
+        if getattr(self, 'depth', 8) == 10:
+            return (f'YUVClip({"P010" if self.nv12 else "yuv420p10"} {"msb" if self.shift else "lsb"}-aligned {self.shape} on {self.device}, '
+                    f'matrix={self.matrix})')
         return f'YUVClip({"NV12" if self.nv12 else "I420"} {self.shape} on {self.device}, matrix={self.matrix})'
 
 
@@ -1107,8 +1170,10 @@ class ClipTable:
     where the 8-byte loads of the pointers are aligned.  Only ``clips_table`` makes one.
 
     Of a list of ``YUVClip`` (``yuv`` is then True): ``kept`` holds the carriers, whose planes are read in place, and ``host`` is
-    int32 [22 * B], the B records vtx_clips_views_yuv420 reads (include/vtx_yuv.h: each begins with its three pointers)."""
-    __slots__ = ('kept', 'shapes', 'widths', 'host', 'yuv')
+    int32 [22 * B], the B records vtx_clips_views_yuv420 reads (include/vtx_yuv.h: each begins with its three pointers).  With
+    at least one 10-bit clip in the list ``deep`` is True and ``host`` is int32 [24 * B], the records of every clip, 8-bit ones
+    included, as vtx_clips_views_yuv10 reads them (include/vtx_yuv10.h)."""
+    __slots__ = ('kept', 'shapes', 'widths', 'host', 'yuv', 'deep')
 
     @property
     def device(self):
@@ -1122,13 +1187,14 @@ def clips_table(clips, widths, what='clips_views_u8'):
     t = ClipTable()
     t.shapes = clip_list_shapes(clips, what)
     t.yuv = isinstance(clips[0], YUVClip)
+    t.deep = t.yuv and any(c.depth == 10 for c in clips)
     need_cuda(*([p for c in clips for p in c.planes] if t.yuv else clips))
     t.widths = [int(w) for w in widths]
     if len(t.widths) != len(clips):
         raise ValueError(f'{what}: {len(t.widths)} row widths for {len(clips)} clips')
     if t.yuv:
         t.kept = list(clips)
-        t.host = np.concatenate([c.record(w) for c, w in zip(clips, t.widths)])
+        t.host = np.concatenate([c.record10(w) if t.deep else c.record(w) for c, w in zip(clips, t.widths)])
         return t
     t.kept = [c.contiguous() for c in clips]
     ptrs = np.array([c.data_ptr() for c in t.kept], dtype=np.uint64)
@@ -1169,10 +1235,10 @@ def clips_views_u8(clips, frames, left, width, xtab, ytab, out=None, widths=None
 
 
 def _clips_views(name, yuv, clips, frames, left, width, xtab, ytab, out, widths, table):
-    """clips_views_u8 (yuv False: tensors, vtx_clips_views_u8) and clips_views_yuv (yuv True: YUVClip, vtx_clips_views_yuv420):
-    the same checks, the same upload and the same arguments behind the descriptor."""
+    """clips_views_u8 (yuv False: tensors, vtx_clips_views_u8) and clips_views_yuv (yuv True: YUVClip, vtx_clips_views_yuv420, or
+    vtx_clips_views_yuv10 for a list with a 10-bit clip in it): the same checks, the same upload and the same arguments behind
+    the descriptor."""
     import numpy as np
-    words = _lib.YUV_CLIP_I32 if yuv else 6                      # int32 words of the descriptor per clip
     if isinstance(clips, ClipTable):
         ct = clips
         if widths is not None:
@@ -1192,6 +1258,7 @@ def _clips_views(name, yuv, clips, frames, left, width, xtab, ytab, out, widths,
     if ct is None:
         ct = clips_table(clips, [Wr_max] * B if widths is None else widths, name)
     shapes, widths, dev = ct.shapes, ct.widths, ct.device
+    words = (_lib.YUV10_CLIP_I32 if ct.deep else _lib.YUV_CLIP_I32) if yuv else 6       # int32 words of the descriptor per clip
     for b, w in enumerate(widths):
         if not 0 < W <= w <= Wr_max:
             raise ValueError(f'{name}: views of {W} columns do not fit the resized row of {w} of clip {b} (the tables hold {Wr_max})')
@@ -1231,6 +1298,11 @@ def _clips_views(name, yuv, clips, frames, left, width, xtab, ytab, out, widths,
             raise TypeError(f'{name}: with table= frames and left are device tensors (uploaded with it)')
     tabs = (ptr(frames), ptr(left), ptr(xtab[0]), ptr(xtab[1]), ptr(xtab[2]), xtab[2].shape[2], ptr(ytab[0]), ptr(ytab[1]), ptr(ytab[2]),
             ytab[2].shape[2], stream())
+    if yuv and ct.deep:                                          # one launch for both depths: 1.5 samples per pixel of 1 or 2 bytes
+        src_bytes = sum(T * c.source_bytes for c in ct.kept)
+        with _timed('clips_views_yuv10', nbytes=src_bytes + out.numel(), key=f'{B}x{T} yuv420p10->{V}x{H}x{W}'):
+            _lib.yuv10_call('vtx_clips_views_yuv10', B, T, H, V, W, Wr_max, ptr(table), ptr(out), *tabs)
+        return out
     if yuv:                                                      # 1.5 source bytes per pixel: the luma and two quarter-size chroma planes
         src_bytes = sum(T * (s[1] * s[2] + 2 * ((s[1] + 1) // 2) * ((s[2] + 1) // 2)) for s in shapes)
         with _timed('clips_views_yuv', nbytes=src_bytes + out.numel(), key=f'{B}x{T} yuv420->{V}x{H}x{W}'):
@@ -1249,13 +1321,18 @@ def clips_views_yuv(clips, frames, left, width, xtab, ytab, out=None, widths=Non
     """clips_views_u8 on decoded 4:2:0 clips: ``clips`` a list or tuple of B ``YUVClip`` (NV12 and I420, sizes, pitches and
     matrices may differ from clip to clip) -> uint8 [B,V,T,H,width,3], byte for byte clips_views_u8 on the clips
     ``yuv420_to_rgb_u8`` would write, which never exist: each tap is converted in registers.  Every other argument, every check
-    and the one upload are clips_views_u8's; ``table``: the int32 [22 * B] device copy of the ClipTable's ``host`` array."""
+    and the one upload are clips_views_u8's; ``table``: the int32 [22 * B] device copy of the ClipTable's ``host`` array.
+
+    A list whose clips are all 8-bit launches vtx_clips_views_yuv420 (libvtx_yuv.so).  A list with at least one 10-bit clip
+    (P010, yuv420p10le: ``YUVClip(depth=10)``) launches vtx_clips_views_yuv10 (libvtx_yuv10.so, include/vtx_yuv10.h) once, for all
+    of its clips; the records are then 24 int32 each, and the 8-bit clips' bytes are those of the other route."""
     return _clips_views('clips_views_yuv', True, clips, frames, left, width, xtab, ytab, out, widths, table)
 
 
 def yuv420_to_rgb_u8(clip, out=None):
-    """The plain conversion of one ``YUVClip`` -> uint8 [Ts,Hs,Ws,3] (include/vtx_yuv.h: nearest chroma siting, the clip's
-    integer matrix), for callers that want the RGB frames.  ``out``: a contiguous uint8 [Ts,Hs,Ws,3] device tensor to write into."""
+    """The plain conversion of one ``YUVClip`` -> uint8 [Ts,Hs,Ws,3] (include/vtx_yuv.h, of a 10-bit clip include/vtx_yuv10.h:
+    nearest chroma siting, the clip's integer matrix), for callers that want the RGB frames.  ``out``: a contiguous uint8
+    [Ts,Hs,Ws,3] device tensor to write into."""
     if not isinstance(clip, YUVClip):
         raise TypeError(f'yuv420_to_rgb_u8: a YUVClip is expected, got {type(clip).__name__}')
     need_cuda(*clip.planes)
@@ -1266,6 +1343,11 @@ def yuv420_to_rgb_u8(clip, out=None):
         need_cuda(out)
         if out.dtype != torch.uint8 or tuple(out.shape) != (Ts, Hs, Ws, 3) or not out.is_contiguous():
             raise TypeError(f'yuv420_to_rgb_u8: out must be a contiguous uint8 {(Ts, Hs, Ws, 3)} tensor, got {out.dtype} {tuple(out.shape)}')
+    if clip.depth == 10:
+        rec = upload_i32(clip.record10(), clip.device)
+        with _timed('yuv10_to_rgb', nbytes=Ts * clip.source_bytes + out.numel(), key=f'{Ts}x{Hs}x{Ws}'):
+            _lib.yuv10_call('vtx_yuv10_to_rgb_u8', ptr(rec), Ts, Hs, Ws, ptr(out), stream())
+        return out
     rec = upload_i32(clip.record(), clip.device)
     with _timed('yuv420_to_rgb', nbytes=Ts * (Hs * Ws + 2 * ((Hs + 1) // 2) * ((Ws + 1) // 2)) + out.numel(), key=f'{Ts}x{Hs}x{Ws}'):
         _lib.yuv_call('vtx_yuv420_to_rgb_u8', ptr(rec), Ts, Hs, Ws, ptr(out), stream())
