@@ -67,7 +67,10 @@ const char* vtx_last_error_string(void);
  * attention of more than 256 tokens back to the fp32 VALU kernels and touches nothing else), "attn_f32" = mfma|valu (library
  * version 230; fp32 attention of more than 32 tokens with head_dim 64, without `probs`: mfma, the default, runs the exact-fp32 MFMA
  * kernels of csrc/attn_f32.hip -- fp32 operands, scores, probabilities and accumulators, the VALU kernels' arithmetic in another
- * summation order; valu restores the VALU kernels bit for bit; bf16 is not touched by either value), "tn_cus" = n (compute units the weight-gradient
+ * summation order; valu restores the VALU kernels bit for bit; bf16 is not touched by either value), "attn_hd" = mfma|valu (bf16
+ * attention of more than 32 tokens with head_dim 32, 96 or 128: mfma, the default, runs the chunk-streaming MFMA kernels of
+ * csrc/attn_hd.hip; valu the VALU kernels, which serve everything else at those head dims; head_dim 64 is not touched by either
+ * value), "tn_cus" = n (compute units the weight-gradient
  * kernel's one-round slab split is sized for: 256; 240 leaves room for 16 CUs held by a collective in flight -- another, equally fixed
  * summation order of the slabs), "attn_hw_fwd", "attn_hw_bwd" = n
  * (short-sequence attention: n heads of a row tile per workgroup, 0 = one head and four row tiles; defaults 16 / 4), "pp_grid", "pp_cg",
@@ -199,7 +202,7 @@ int vtx_colsum(int dtype, int M, int N, const void* A, long lda, vtx_rowmap amap
 /* ------------------------------------------------------------------ Attention
  * softmax(q k^T * scale) v per (sequence, head).  Replaces transformer.py:
  * 167-174 and the rearranges around it (:250, :352-356, :375).  qkv feature
- * order [3][head][hd] (:167).
+ * order [3][head][hd] (:167); hd = 32, 64, 96 or 128 (any other: VTX_EINVAL).
  * mode VTX_ATTN_CONTIG: sequence s = rows [s*L, (s+1)*L) of qkv / out.
  * mode VTX_ATTN_SPACE : divided spatial attention.  qkv is in natural token
  *   order [B, 1+P*T, 3D]; sequence s=(b,t) has L = 1+P tokens: i=0 is the cls

@@ -29,7 +29,7 @@ int check_launch(const char* what) {
 
 // ---- options -------------------------------------------------------------------------
 static const char* const kNtNames[] = {"auto", "pp256", "dma2", "ring128x3", "ring128x4k32", "ring256x3", "ring256x3k32", "ring256x4k32"};
-static const char* const kAttnF32Names[] = {"valu", "mfma"};
+static const char* const kAttnF32Names[] = {"valu", "mfma"};     // also attn_hd's
 static const char* const kTnNames[] = {"auto", "pp256", "ring", "dma2", "w4"};
 
 // One row per option: {environment variable (none: not settable from the environment), name}, how the value parses, the field.
@@ -47,6 +47,7 @@ static const OptRow kOptions[] = {
     {{"VTX_ATTN_VALU", "attn_valu"}, OPT_FLAG, &Options::attn_valu},
     {{"VTX_ATTN_LONG", "attn_long"}, OPT_FLAG, &Options::attn_long},
     {{"VTX_ATTN_F32", "attn_f32"}, OPT_ENUM, &Options::attn_f32, VTX_ENUM(kAttnF32Names)},
+    {{"VTX_ATTN_HD", "attn_hd"}, OPT_ENUM, &Options::attn_hd, VTX_ENUM(kAttnF32Names)},
     {{"VTX_ATTN_HW_FWD", "attn_hw_fwd"}, OPT_INT, &Options::attn_hw_fwd, 0, INT_MAX, 1},
     {{"VTX_ATTN_HW_BWD", "attn_hw_bwd"}, OPT_INT, &Options::attn_hw_bwd, 0, INT_MAX, 1},
     {{"VTX_ATTN_FUSED", "attn_fused"}, OPT_CLAMP, &Options::attn_fused, 0, 2},

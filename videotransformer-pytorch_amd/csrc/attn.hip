@@ -14,7 +14,8 @@
 // run the MFMA kernels of attn_mfma.hip, more than 256 (785 spatial at 448^2, 1569
 // joint) those of attn_long.hip; fp32 with head_dim 64 and more than 32 tokens runs the exact-fp32 MFMA kernels of
 // attn_f32.hip.  These kernels are the fp32 path of up to 32 tokens, the `probs` pass (and the forward in front of it)
-// and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  Algorithmic bytes per (sequence, head):
+// and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  At head_dim 32, 96 and 128 they are everything but bf16 above 32
+// tokens (attn_hd.hip; attn_hd=valu sends that back here too).  Algorithmic bytes per (sequence, head):
 // read 3*L*hd, write L*hd elements (+ L fp32 lse).
 #include <stdlib.h>
 #include "attn_common.h"
@@ -179,13 +180,17 @@ __global__ __launch_bounds__(AT_THREADS) void attn_fwd_kernel(AttnP p, const T* 
 }
 
 // Backward pass A: thread per query.  dq_i = scale * sum_j p_ij (dO_i.v_j - delta_i) k_j; also writes delta.
-template <typename T, int HD>
+// NP > 1 (head_dim 96 and 128): blockIdx.z picks one of NP column parts of dq, so that a thread accumulates HD / NP columns
+// (q, dO and all of dq are 3 HD floats a thread: more than the 256 vector registers from HD = 96 on); the parts repeat the scores.  The one-part form of <bf16, 96> spilled to scratch
+// and returned wrong dq on the device, for a reason that was not found (profiles/attn_hd_bench.txt, 1); NP = 1 is the kernel as it was.
+template <typename T, int HD, int NP>
 __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(AttnP p, const T* __restrict__ qkv, const T* __restrict__ o,
                                                                  const T* __restrict__ dout, const float* __restrict__ lse,
                                                                  float* __restrict__ delta, T* __restrict__ dqkv,
                                                                  T* __restrict__ dqkv_cls) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int h = blockIdx.y, D = p.H * HD;
+  constexpr int HP = HD / NP;
+  const int h = blockIdx.y, D = p.H * HD, part = NP > 1 ? blockIdx.z : 0;
   const Who w = who_am_i(p);
   const int KT = p.G > 1 ? p.L : AT_KT;
   const int seq_ld = KT * HD + Tile<HD>::SEQ_PAD;
@@ -193,10 +198,10 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(AttnP p, const 
   float* Vs = sm + p.G * seq_ld;
   const int s = w.s0 + w.g;
 
-  float q[HD], dO[HD], dq[HD];
+  float q[HD], dO[HD], dq[HP];
   float my_lse = 0.f, my_delta = 0.f;
 #pragma unroll
-  for (int e = 0; e < HD; ++e) dq[e] = 0.f;
+  for (int e = 0; e < HP; ++e) dq[e] = 0.f;
   if (w.active) {
     load_vec<T, HD>(qkv + in_row(p, s, w.i) * p.ld_qkv + h * HD, q);
     const long orow = out_row(p, s, w.i);
@@ -211,7 +216,7 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(AttnP p, const 
     for (int e = 0; e < HD; ++e) q[e] *= p.scale;
     const long li = ((long)s * p.H + h) * p.L + w.i;
     my_lse = lse[li];
-    delta[li] = my_delta;
+    if (part == 0) delta[li] = my_delta;
   }
   for (int k0 = 0; k0 < p.L; k0 += KT) {
     const int nk = min(KT, p.L - k0);
@@ -228,15 +233,15 @@ __global__ __launch_bounds__(AT_THREADS) void attn_bwd_dq_kernel(AttnP p, const 
     for (int j = 0; j < nk; ++j) {
       const float pij = __expf(dot_lds<HD>(q, Kg + j * HD) - my_lse);
       const float dp = dot_lds<HD>(dO, Vg + j * HD);
-      axpy_lds<HD>(dq, pij * (dp - my_delta), Kg + j * HD);
+      axpy_lds<HP>(dq, pij * (dp - my_delta), Kg + j * HD + part * HP);
     }
   }
   if (w.active) {
 #pragma unroll
-    for (int e = 0; e < HD; ++e) dq[e] *= p.scale;
+    for (int e = 0; e < HP; ++e) dq[e] *= p.scale;
     T* dst = attn_cls_row(p, w.i) ? dqkv_cls + (long)s * p.ld_dqkv + h * HD
                                                     : dqkv + in_row(p, s, w.i) * p.ld_dqkv + h * HD;
-    store_vec<T, HD>(dst, dq);
+    store_vec<T, HP>(dst + part * HP, dq);
   }
 }
 
@@ -304,7 +309,7 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
 // Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins.  The mode matters
 // up to 32 tokens only: CONTIG and TIME_CLS are packed, SPACE_NOCLS runs the one-workgroup kernels at one tile, SPACE (no model
 // has P < 32) the VALU kernels as before.
-enum Route { SMALL, MFMA, LONG, F32, VALU };
+enum Route { SMALL, MFMA, LONG, F32, VALU, HDIM };
 static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // VTX_ATTN_VALU=1 forces the VALU path.
   if (options().attn_valu) return VALU;
@@ -316,12 +321,16 @@ static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu sends them back here, and
   // so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
   if (options().attn_f32 && !probs && attn_f32_eligible(dtype, L, hd)) return F32;
+  // bf16, head_dim 32 / 96 / 128, more than 32 tokens -> chunk-streaming MFMA kernels (attn_hd.hip); VTX_ATTN_HD=valu sends them
+  // back here.  Everything else at those head dims (fp32, up to 32 tokens) has no other kernel: the routes above all ask for 64.
+  if (options().attn_hd && attn_hd_eligible(dtype, L, hd)) return HDIM;
   return VALU;
 }
 
 static int make_params(const vtx_attn_desc* d, AttnP& p, const char* who) {
   VTX_REQUIRE(d->S > 0 && d->L > 0 && d->H > 0, VTX_EINVAL, "%s: bad shape S=%d L=%d H=%d", who, d->S, d->L, d->H);
-  VTX_REQUIRE(d->hd == 64, VTX_EINVAL, "%s: head_dim %d unsupported (64 only)", who, d->hd);
+  VTX_REQUIRE(d->hd == 32 || d->hd == 64 || d->hd == 96 || d->hd == 128, VTX_EINVAL, "%s: head_dim %d unsupported (32, 64, 96, 128)", who,
+              d->hd);
   VTX_REQUIRE(d->mode == VTX_ATTN_CONTIG || d->mode == VTX_ATTN_SPACE || d->mode == VTX_ATTN_TIME_CLS ||
                   d->mode == VTX_ATTN_SPACE_NOCLS,
               VTX_EINVAL, "%s: bad mode", who);
@@ -352,25 +361,50 @@ static size_t attn_lds(const AttnP& p, int hd, bool with_stats) {
   return b;
 }
 
-// The VALU launches, once per element type.  PROBS = 1 recomputes the probabilities from the lse that a forward left.
-template <typename T, int PROBS>
-static int valu_fwd_launch(const AttnP& p, const vtx_attn_desc* d, hipStream_t st) {
-  hipLaunchKernelGGL((attn_fwd_kernel<T, 64, PROBS>), attn_grid(p), attn_block(p), attn_lds(p, 64, false), st, p, (const T*)d->qkv,
+// The VALU launches, once per element type and head dim.  PROBS = 1 recomputes the probabilities from the lse that a forward left.
+// At head_dim 128 the tiles pass 64 KB (one sequence: 2 (64 * 128 + 4) * 4 B = 65568; packed, G * L <= 128: up to 132.2 KB with
+// the lse / delta rows of the dk / dv pass), hence the opt-in; 160 KB is the CU's.
+template <typename T, int HD, int PROBS>
+static int valu_fwd_launch_hd(const AttnP& p, const vtx_attn_desc* d, hipStream_t st) {
+  const size_t lds = attn_lds(p, HD, false);
+  allow_lds<attn_fwd_kernel<T, HD, PROBS>>(lds);
+  hipLaunchKernelGGL((attn_fwd_kernel<T, HD, PROBS>), attn_grid(p), attn_block(p), lds, st, p, (const T*)d->qkv,
                      (T*)d->out, d->lse, PROBS ? d->probs : nullptr);
   return check_launch(PROBS ? "attn_probs" : "attn_fwd");
 }
-template <typename T>
-static int valu_bwd_launch(const AttnP& p, const vtx_attn_bwd_desc* d, hipStream_t st) {
+template <typename T, int PROBS>
+static int valu_fwd_launch(const AttnP& p, const vtx_attn_desc* d, hipStream_t st) {
+  switch (d->hd) {                                   // make_params admits no other
+    case 32: return valu_fwd_launch_hd<T, 32, PROBS>(p, d, st);
+    case 96: return valu_fwd_launch_hd<T, 96, PROBS>(p, d, st);
+    case 128: return valu_fwd_launch_hd<T, 128, PROBS>(p, d, st);
+    default: return valu_fwd_launch_hd<T, 64, PROBS>(p, d, st);
+  }
+}
+template <typename T, int HD>
+static int valu_bwd_launch_hd(const AttnP& p, const vtx_attn_bwd_desc* d, hipStream_t st) {
   const dim3 grid = attn_grid(p), block = attn_block(p);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, 64>), grid, block, attn_lds(p, 64, false), st, p, (const T*)d->f.qkv, (const T*)d->f.out,
+  const size_t lds = attn_lds(p, HD, false), lds_dkv = attn_lds(p, HD, true);
+  constexpr int NP = HD > 64 ? 2 : 1;                // column parts of dq (attn_bwd_dq_kernel)
+  allow_lds<attn_bwd_dq_kernel<T, HD, NP>>(lds);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<T, HD, NP>), dim3(grid.x, grid.y, NP), block, lds, st, p, (const T*)d->f.qkv, (const T*)d->f.out,
                      (const T*)d->dout, d->f.lse, d->delta, (T*)d->dqkv, (T*)d->dqkv_cls);
   const int rc = check_launch("attn_bwd_dq");
   if (rc) return rc;
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, 64>), grid, block, attn_lds(p, 64, true), st, p, (const T*)d->f.qkv, (const T*)d->dout,
+  allow_lds<attn_bwd_dkv_kernel<T, HD>>(lds_dkv);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, HD>), grid, block, lds_dkv, st, p, (const T*)d->f.qkv, (const T*)d->dout,
                      d->f.lse, d->delta, (T*)d->dqkv, (T*)d->dqkv_cls);
   return check_launch("attn_bwd_dkv");
 }
-
+template <typename T>
+static int valu_bwd_launch(const AttnP& p, const vtx_attn_bwd_desc* d, hipStream_t st) {
+  switch (d->f.hd) {
+    case 32: return valu_bwd_launch_hd<T, 32>(p, d, st);
+    case 96: return valu_bwd_launch_hd<T, 96>(p, d, st);
+    case 128: return valu_bwd_launch_hd<T, 128>(p, d, st);
+    default: return valu_bwd_launch_hd<T, 64>(p, d, st);
+  }
+}
 
 }  // namespace vtx
 
@@ -389,6 +423,7 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
     case MFMA: rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st); break;
     case LONG: rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st); break;
     case F32: rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st); break;
+    case HDIM: rc = attn_fwd_hd_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case VALU: rc = f32 ? valu_fwd_launch<float, 0>(p, d, st) : valu_fwd_launch<bf16raw, 0>(p, d, st); break;
   }
   if (rc || !d->probs) return rc;
@@ -417,6 +452,7 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
     case MFMA: return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case HDIM: return attn_bwd_hd_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case VALU: break;
   }
   return d->f.dtype == VTX_F32 ? valu_bwd_launch<float>(p, d, st) : valu_bwd_launch<bf16raw>(p, d, st);

@@ -285,5 +285,10 @@ bool attn_f32_eligible(int dtype, int L, int hd);
 int attn_fwd_f32_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_f32_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                         float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);
+// attn_hd.hip (head_dim 32, 96, 128)
+bool attn_hd_eligible(int dtype, int L, int hd);
+int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
+int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
+                       void* dqkv, void* dqkv_cls, hipStream_t st);
 
 }  // namespace vtx

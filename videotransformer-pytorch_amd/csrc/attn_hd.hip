@@ -1,0 +1,519 @@
+// attn_hd.hip -- bf16 MFMA attention core for head_dim 32, 96 and 128, more than 32 tokens per sequence, all four layouts.
+//
+// The structure is the chunk streaming of attn_stream.h (read its header first: transposed scores, a workgroup of 4 waves owns 128
+// queries -- 128 keys in the dk / dv kernel --, the other operands stream through two LDS stages, one barrier per chunk, dk / dv
+// with one workgroup per key block walking all queries: fixed summation order, no atomics, no workspace), and the formulation is
+// that of attn_long.hip: v_mfma_f32_32x32x16_bf16, swizzled [rows][64] bf16 tiles, transposed operands through
+// ds_read_b64_tr_b16 (sw_off / frag_rows_o / frag_cols_o of attn_common.h, unchanged).  What differs is the head: attn_stream.h
+// and its two policies fix 64 columns (h * 64, two accumulator tiles, four k-steps) and are left exactly as they are, so that
+// the head_dim-64 kernels compile to the same objects; the three bodies are restated here over HD.
+//
+// A head is NS = ceil(HD / 64) column slabs of the [rows][64] tile, the last one half used at 32 and 96 (its upper 32 columns
+// are never written and never read):
+//   scores         HD / 16 chained k-steps, step ks from slab ks / 4                    (2 | 6 | 8 MFMAs per 32 x 32 score tile)
+//   accumulators   HD / 32 f32x16 tiles, tile n from slab n / 2, column half n % 2      (1 | 3 | 4)
+//   no padded products: the half-used slab costs LDS, not matrix instructions.
+// LDS: one operand of a chunk is NS slabs of CHUNK = 64 rows: 8 KiB at one slab, 16 KiB at two; a stage holds two operands and
+// there are two stages: 32 KiB at head_dim 32, 64 KiB at 96 and 128 (+ 1 KiB of lse / delta in the dk / dv kernel).  At 32 that
+// admits three workgroups a CU, and three measured 11 % faster than two with 128-row chunks (the kernel waits on softmax VALU work
+// and chunk stores, not on the matrix pipe); at 96 / 128 two fit the CU's 160 KiB.
+// Registers (per lane, f32x16 = 16): row fragments HD / 4 per operand; forward acc HD / 2 + CHUNK / 2 of scores; dk / dv holds
+// 2 * HD / 2 of accumulators + 2 * HD / 4 of K and V fragments + 64 of S, dP, P, dS: 112 | 208 | 256 at 32 | 96 | 128, and
+// 8 | 24 | 32 of the chunk in flight, before addresses.  The dk / dv kernel is therefore bounded to two workgroups a CU at 96 (256 registers, 76 B of scratch a lane:
+// 6 - 10 % faster than one workgroup without scratch) and to one at 128 (388 registers; bounded to two it spills 296 B and
+// runs 1.4 - 1.8 x slower); forward and dq run two a CU at 96 / 128.  profiles/attn_hd_bench.txt has what the compiler made of it.
+//
+// Masking as in attn_stream.h: keys >= L have zero K / V rows and score -1e30 before the max; query rows >= L keep to their lane
+// and are never stored; in the dk / dv kernel padded query rows carry lse = +1e30.
+// FLOPs per (sequence, head): forward 4 L^2 HD, backward 10 L^2 HD (+ 4 L^2 HD recomputed scores).
+#include "attn_common.h"
+
+namespace vtx {
+namespace hdim {
+
+constexpr int THREADS = 256;
+constexpr int ROWS = 128;                          // queries (keys in the dk / dv kernel) of one workgroup: 4 waves x 32
+
+template <int HD> struct Geo {
+  static_assert(HD == 32 || HD == 96 || HD == 128, "head dims of this file");
+  static constexpr int NS = (HD + 63) / 64;        // column slabs of a row
+  static constexpr int NK = HD / 16;               // k-steps of a score tile
+  static constexpr int NT = HD / 32;               // accumulator tiles of a result row
+  static constexpr int CHUNK = 64;                 // rows of the streamed operands per LDS stage
+  static constexpr int KC = CHUNK / 32;
+  static constexpr int SLAB = CHUNK * 64;          // elements of one [CHUNK][64] slab
+  static constexpr int TILE = NS * SLAB;           // one operand of a chunk (8 KiB at one slab, 16 KiB at two)
+  static constexpr int STAGE = 2 * TILE;
+  static constexpr int PR = HD / 8;                // 16-byte pieces of a row
+  static constexpr int PER = CHUNK * PR / THREADS; // pieces of one operand per thread
+  static_assert(CHUNK * PR % THREADS == 0, "whole pieces per thread");
+  static constexpr size_t LDS_KV = (size_t)2 * STAGE * sizeof(bf16raw);
+  static constexpr size_t LDS_DKV = LDS_KV + (size_t)2 * 2 * CHUNK * sizeof(float);
+};
+
+struct Who {
+  int lane, wave, h, D, s, row0, row;              // row0: first of the wave's 32 rows; row: this lane's
+  bool active;                                     // wave-uniform; an idle wave still fills and meets the barriers
+  RowLin li, lo;
+};
+template <int HD>
+__device__ inline Who who(const AttnP& p) {
+  Who w;
+  w.lane = threadIdx.x & 63;
+  w.wave = threadIdx.x >> 6;
+  w.h = blockIdx.y;
+  w.D = p.H * HD;
+  const int nb = (p.L + ROWS - 1) / ROWS;          // blockIdx.x -> (sequence, 128-row block of that sequence)
+  w.s = blockIdx.x / nb;
+  w.row0 = (blockIdx.x - w.s * nb) * ROWS + w.wave * 32;
+  w.row = w.row0 + (w.lane & 31);
+  w.active = w.row0 < p.L;
+  w.li = lin_in(p, w.s);
+  w.lo = lin_out(p, w.s);
+  return w;
+}
+
+__device__ inline bf16raw* lds_base() {
+  extern __shared__ __attribute__((aligned(16))) char sm_raw[];
+  return reinterpret_cast<bf16raw*>(sm_raw);
+}
+
+// Rows row0 .. row0 + CHUNK - 1 of two operands of one sequence, in flight between two chunks.
+template <int HD> struct Pre { uint4 a[Geo<HD>::PER], b[Geo<HD>::PER]; };
+
+// Issue the loads of one chunk (rows >= L read as zero; a chunk wholly beyond L issues nothing).
+template <int HD>
+__device__ __forceinline__ void chunk_load(Pre<HD>& x, const bf16raw* b0, long ld0, const RowLin& r0, const bf16raw* b1, long ld1,
+                                           const RowLin& r1, int row0, int L) {
+  typedef Geo<HD> G;
+#pragma unroll
+  for (int i = 0; i < G::PER; ++i) {
+    const int id = threadIdx.x + i * THREADS;
+    const int rr = id / G::PR, c = id - rr * G::PR;
+    const int r = row0 + rr;
+    x.a[i] = make_uint4(0, 0, 0, 0);
+    x.b[i] = make_uint4(0, 0, 0, 0);
+    if (r < L) {
+      x.a[i] = *reinterpret_cast<const uint4*>(b0 + lin_row(r0, r) * ld0 + c * 8);
+      x.b[i] = *reinterpret_cast<const uint4*>(b1 + lin_row(r1, r) * ld1 + c * 8);
+    }
+  }
+}
+template <int HD>
+__device__ __forceinline__ void chunk_store(const Pre<HD>& x, bf16raw* t0, bf16raw* t1) {
+  typedef Geo<HD> G;
+#pragma unroll
+  for (int i = 0; i < G::PER; ++i) {
+    const int id = threadIdx.x + i * THREADS;
+    const int rr = id / G::PR, c = id - rr * G::PR;
+    const int off = (c >> 3) * G::SLAB + rr * 64 + (((c & 7) ^ sw_of(rr)) << 3);
+    *reinterpret_cast<uint4*>(t0 + off) = x.a[i];
+    *reinterpret_cast<uint4*>(t1 + off) = x.b[i];
+  }
+}
+
+// A row's HD columns (this lane's half of every 16) in registers; rows beyond nvalid read row nvalid - 1 (load_row_frags).
+template <int HD> struct Frag { bf16x8 f[Geo<HD>::NK]; };
+template <int HD>
+__device__ __forceinline__ void load_frag(Frag<HD>& f, const bf16raw* base, long ld, int col0, const RowLin& rl, int row, int nvalid,
+                                          int lane) {
+  const int rc = row < nvalid ? row : nvalid - 1;
+  const bf16raw* src = base + lin_row(rl, rc) * ld + col0 + 8 * (lane >> 5);
+#pragma unroll
+  for (int ks = 0; ks < Geo<HD>::NK; ++ks) {
+    union { bf16x8 v; uint4 u; } x;
+    x.u = *reinterpret_cast<const uint4*>(src + ks * 16);
+    f.f[ks] = x.v;
+  }
+}
+template <int HD>
+__device__ __forceinline__ float frag_dot(const Frag<HD>& a, const Frag<HD>& b) {
+  float s = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < Geo<HD>::NK; ++ks) s = frag_dot2(a.f[ks], b.f[ks], s);
+  return s;
+}
+
+// C[i][j] = sum_d tile[row0 + i][d] frag_j[d] for 32 tile rows
+template <int HD>
+__device__ __forceinline__ f32x16 scores(const bf16raw* t, int row0, const Frag<HD>& b, const FragOff& fo) {
+  typedef Geo<HD> G;
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(t, row0, 0, fo), b.f[0], zero, 0, 0, 0);
+#pragma unroll
+  for (int ks = 1; ks < G::NK; ++ks)
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(t + (ks >> 2) * G::SLAB, row0, ks & 3, fo), b.f[ks], st, 0, 0, 0);
+  return st;
+}
+// acc[n][d][j] += sum_i tile[row0 + i][32 n + d] c[i][j], c as scores() left it
+template <int HD>
+__device__ __forceinline__ void accum(f32x16 (&acc)[Geo<HD>::NT], const bf16raw* t, int row0, const f32x16& c, const FragOff& fo) {
+  typedef Geo<HD> G;
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    float pf[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pf[j] = c[8 * s2 + j];
+    const bf16x8 pb = pack8(pf);
+#pragma unroll
+    for (int n = 0; n < G::NT; ++n)
+      acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(t + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), pb, acc[n], 0, 0, 0);
+  }
+}
+// The dk / dv products of one 32-query tile: the S and dP chains interleaved, then dv and dk fed together (attn_long.hip).
+template <int HD>
+__device__ __forceinline__ void dkv_tile(f32x16 (&dk)[Geo<HD>::NT], f32x16 (&dv)[Geo<HD>::NT], const bf16raw* Qs, const bf16raw* Os,
+                                         const float* Ls, const float* Ds, int row0, const Frag<HD>& kf, const Frag<HD>& vf, float c2,
+                                         const FragOff& fo, int lane) {
+  typedef Geo<HD> G;
+  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, row0, 0, fo), kf.f[0], zero, 0, 0, 0);
+  f32x16 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, row0, 0, fo), vf.f[0], zero, 0, 0, 0);
+#pragma unroll
+  for (int ks = 1; ks < G::NK; ++ks) {
+    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs + (ks >> 2) * G::SLAB, row0, ks & 3, fo), kf.f[ks], st, 0, 0, 0);
+    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os + (ks >> 2) * G::SLAB, row0, ks & 3, fo), vf.f[ks], dp, 0, 0, 0);
+  }
+  float pr[16], ds[16];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const int qrow = row0 + 8 * g + 4 * (lane >> 5);
+    const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
+    const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
+    const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = 4 * g + j;
+      const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
+      pr[r] = e;
+      ds[r] = e * (dp[r] - dvv[j]);                // the softmax scale is applied once to dk at the store
+    }
+  }
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    const bf16x8 pb = pack8(pr + 8 * s2);
+    const bf16x8 dsb = pack8(ds + 8 * s2);
+#pragma unroll
+    for (int n = 0; n < G::NT; ++n) {
+      dv[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), pb, dv[n], 0, 0, 0);
+      dk[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), dsb, dk[n], 0, 0, 0);
+    }
+  }
+}
+
+// Store a [32 x HD] result held transposed (lane & 31 = row, registers = HD columns in NT C tiles): slab by slab through the
+// wave's swizzled [32][64] staging tile, whole 16-byte pieces of a row per lane (store_rows_T of attn_common.h, for NT tiles).
+// ptr_of_row(r) -> destination of tile row r (HD bf16), or nullptr for a padded row.
+template <int HD, typename PtrFn>
+__device__ __forceinline__ void store_rows(bf16raw* stg, const f32x16 (&acc)[Geo<HD>::NT], float mul, int lane, PtrFn ptr_of_row) {
+  typedef Geo<HD> G;
+  const int row = lane & 31;
+#pragma unroll
+  for (int s = 0; s < G::NS; ++s) {
+    const int ntile = G::NT - 2 * s < 2 ? G::NT - 2 * s : 2;     // C tiles of this slab
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+      if (nt < ntile) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const int col = nt * 32 + 8 * g + 4 * (lane >> 5);
+          union { bf16x4 v; uint2 u; } w;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) w.v[j] = (__bf16)(acc[2 * s + nt][4 * g + j] * mul);
+          *reinterpret_cast<uint2*>(stg + sw_off(row, col)) = w.u;
+        }
+      }
+    wave_lds_sync();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int r = i * 8 + (lane >> 3), c = lane & 7;
+      const uint4 v = *reinterpret_cast<const uint4*>(stg + r * 64 + ((c ^ sw_of(r)) << 3));
+      bf16raw* dst = ptr_of_row(r);
+      if (dst && c < ntile * 4) *reinterpret_cast<uint4*>(dst + s * 64 + c * 8) = v;
+    }
+    wave_lds_sync();
+  }
+}
+
+// ------------------------------------------------------------------------------------------------ forward
+template <int HD>
+__global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void fwd_kernel(AttnP p, const bf16raw* __restrict__ qkv, bf16raw* __restrict__ out,
+                                                         float* __restrict__ lse) {
+  typedef Geo<HD> G;
+  constexpr int CHUNK = G::CHUNK, KC = G::KC;
+  bf16raw* sm = lds_base();
+  const Who w = who<HD>(p);
+  const int lane = w.lane, h = w.h;
+  const bf16raw* kb = qkv + w.D + h * HD;
+  const bf16raw* vb = qkv + 2 * w.D + h * HD;
+  Frag<HD> qf;
+  load_frag<HD>(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
+  Pre<HD> pre;
+  chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
+  chunk_store<HD>(pre, sm, sm + G::TILE);
+  __syncthreads();
+  const FragOff ln = make_frag_off(lane);
+  const float c2 = p.scale * LOG2E;
+  f32x16 acc[G::NT];
+#pragma unroll
+  for (int n = 0; n < G::NT; ++n) zero16(acc[n]);
+  float m = -1e30f, l = 0.f;                       // running max of the RAW scores (scale > 0)
+  const int nch = (p.L + CHUNK - 1) / CHUNK;
+  for (int c = 0; c < nch; ++c) {
+    const bf16raw* Ks = sm + (c & 1) * G::STAGE;
+    const bf16raw* Vs = Ks + G::TILE;
+    chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
+    if (w.active) {
+      const int nrows = min(CHUNK, p.L - c * CHUNK);
+      const int nt = (nrows + 31) >> 5;
+      f32x16 st[KC];                               // (tiles beyond nt stay undefined: every use below is guarded)
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < nt) st[t] = scores<HD>(Ks, t * 32, qf, ln);
+      float bm = -1e30f;
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < nt) {
+          if (t * 32 + 32 > nrows) {               // the tile that holds padded keys
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (t * 32 + crow(r, lane) >= nrows) st[t][r] = -1e30f;
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) bm = fmaxf(bm, st[t][r]);
+        }
+      bm = fmaxf(bm, __shfl_xor(bm, 32, 64));
+      const float mn = fmaxf(m, bm);
+      const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);
+      m = mn;
+      const float mc = mn * c2;
+      float bl = 0.f;
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < nt) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) { const float e = __builtin_amdgcn_exp2f(fmaf(st[t][r], c2, -mc)); st[t][r] = e; bl += e; }
+        }
+      bl += __shfl_xor(bl, 32, 64);
+      l = l * alpha + bl;
+      if (c > 0) {
+#pragma unroll
+        for (int n = 0; n < G::NT; ++n)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[n][r] *= alpha;
+      }
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < nt) accum<HD>(acc, Vs, t * 32, st[t], ln);
+    }
+    if (c + 1 < nch) {
+      bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE; // last read in iteration c - 1, behind that iteration's barrier
+      chunk_store<HD>(pre, nx, nx + G::TILE);
+    }
+    __syncthreads();
+  }
+  if (!w.active) return;
+  bf16raw* stg = sm + w.wave * MA_STAGE_ELEMS;     // every wave is past the last chunk: the stages are free
+  store_rows<HD>(stg, acc, 1.0f / l, lane, [&](int r) -> bf16raw* {
+    const int qq = w.row0 + r;
+    return qq < p.L ? out + lin_row(w.lo, qq) * p.ld_out + h * HD : nullptr;
+  });
+  if (w.row < p.L && lane < 32) lse[((long)w.s * p.H + h) * p.L + w.row] = (m * c2) * LN2 + __logf(l);
+}
+
+// ------------------------------------------------------------------------------------------------ backward: dq (+ delta)
+template <int HD>
+__global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void bwd_dq_kernel(AttnP p, const bf16raw* __restrict__ qkv, const bf16raw* __restrict__ o,
+                                                            const bf16raw* __restrict__ dout, const float* __restrict__ lse,
+                                                            float* __restrict__ delta, bf16raw* __restrict__ dqkv,
+                                                            bf16raw* __restrict__ dqkv_cls) {
+  typedef Geo<HD> G;
+  constexpr int CHUNK = G::CHUNK, KC = G::KC;
+  bf16raw* sm = lds_base();
+  const Who w = who<HD>(p);
+  const int lane = w.lane, h = w.h;
+  const bf16raw* kb = qkv + w.D + h * HD;
+  const bf16raw* vb = qkv + 2 * w.D + h * HD;
+  Frag<HD> qf, df;
+  float dl;                                        // delta = rowsum(dO * O): this lane's half of the row's columns
+  {
+    Frag<HD> of;
+    load_frag<HD>(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
+    load_frag<HD>(df, dout, p.ld_dout, h * HD, w.lo, w.row, p.L, lane);
+    load_frag<HD>(of, o, p.ld_out, h * HD, w.lo, w.row, p.L, lane);
+    dl = frag_dot<HD>(df, of);
+  }
+  dl += __shfl_xor(dl, 32, 64);
+  float l2 = 0.f;
+  if (w.row < p.L) {
+    const long lidx = ((long)w.s * p.H + h) * p.L + w.row;
+    l2 = lse[lidx] * LOG2E;
+    if (lane < 32) delta[lidx] = dl;
+  }
+  Pre<HD> pre;
+  chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
+  chunk_store<HD>(pre, sm, sm + G::TILE);
+  __syncthreads();
+  const FragOff ln = make_frag_off(lane);
+  const float c2 = p.scale * LOG2E;
+  f32x16 acc[G::NT];
+#pragma unroll
+  for (int n = 0; n < G::NT; ++n) zero16(acc[n]);
+  const int nch = (p.L + CHUNK - 1) / CHUNK;
+  for (int c = 0; c < nch; ++c) {
+    const bf16raw* Ks = sm + (c & 1) * G::STAGE;
+    const bf16raw* Vs = Ks + G::TILE;
+    chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
+    if (w.active) {
+      const int nrows = min(CHUNK, p.L - c * CHUNK);
+      const int nt = (nrows + 31) >> 5;
+#pragma unroll
+      for (int t = 0; t < KC; ++t)
+        if (t < nt) {
+          const f32x16 st = scores<HD>(Ks, t * 32, qf, ln);
+          f32x16 ds = scores<HD>(Vs, t * 32, df, ln);
+          // dS = P (dP - delta); the softmax scale is applied once to dq at the store.  A padded key has zero K and V rows:
+          // its dS is finite and multiplies zeros; it is zeroed all the same, which keeps the pack clean.
+#pragma unroll
+          for (int r = 0; r < 16; ++r) ds[r] = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -l2)) * (ds[r] - dl);
+          if (t * 32 + 32 > nrows) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (t * 32 + crow(r, lane) >= nrows) ds[r] = 0.f;
+          }
+          accum<HD>(acc, Ks, t * 32, ds, ln);
+        }
+    }
+    if (c + 1 < nch) {
+      bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE;
+      chunk_store<HD>(pre, nx, nx + G::TILE);
+    }
+    __syncthreads();
+  }
+  if (!w.active) return;
+  bf16raw* stg = sm + w.wave * MA_STAGE_ELEMS;
+  store_rows<HD>(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
+    const int qq = w.row0 + r;
+    if (qq >= p.L) return nullptr;
+    return attn_cls_row(p, qq) ? dqkv_cls + (long)w.s * p.ld_dqkv + h * HD : dqkv + lin_row(w.li, qq) * p.ld_dqkv + h * HD;
+  });
+}
+
+// ------------------------------------------------------------------------------------------------ backward: dk, dv
+// Lanes = keys: wave w of the workgroup of key block kb owns the key tile kb * 4 + w and walks ALL queries of the sequence.
+template <int HD>
+__global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_dkv_kernel(AttnP p, const bf16raw* __restrict__ qkv,
+                                                                            const bf16raw* __restrict__ dout,
+                                                                            const float* __restrict__ lse, const float* __restrict__ delta,
+                                                                            bf16raw* __restrict__ dqkv, bf16raw* __restrict__ dqkv_cls) {
+  typedef Geo<HD> G;
+  constexpr int CHUNK = G::CHUNK, QC = G::KC;
+  bf16raw* sm = lds_base();
+  float* stats = reinterpret_cast<float*>(sm + 2 * G::STAGE);    // [stage][lse * log2(e) | delta][CHUNK]
+  const Who w = who<HD>(p);
+  const int lane = w.lane, h = w.h, D = w.D;
+  const bf16raw* qb = qkv + h * HD;
+  const bf16raw* ob = dout + h * HD;
+  const float* lb = lse + ((long)w.s * p.H + h) * p.L;
+  const float* db = delta + ((long)w.s * p.H + h) * p.L;
+  Frag<HD> kf, vf;
+  load_frag<HD>(kf, qkv, p.ld_qkv, D + h * HD, w.li, w.row, p.L, lane);
+  load_frag<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, w.li, w.row, p.L, lane);
+  // thread t < CHUNK: lse of chunk row t (scaled; +huge on padded rows -> P = 0); CHUNK <= t < 2 CHUNK: delta of chunk row t - CHUNK
+  const int srow = threadIdx.x & (CHUNK - 1);
+  const bool is_lse = threadIdx.x < CHUNK, has_stat = threadIdx.x < 2 * CHUNK;
+  auto stat_load = [&](int row0) -> float {
+    const int r = row0 + srow;
+    if (!has_stat || r >= p.L) return is_lse ? 1e30f : 0.f;
+    return is_lse ? lb[r] * LOG2E : db[r];
+  };
+  Pre<HD> pre;
+  chunk_load<HD>(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, 0, p.L);
+  float sv = stat_load(0);
+  chunk_store<HD>(pre, sm, sm + G::TILE);
+  if (has_stat) stats[threadIdx.x] = sv;
+  __syncthreads();
+  const FragOff ln = make_frag_off(lane);
+  const float c2 = p.scale * LOG2E;
+  f32x16 dk[G::NT], dv[G::NT];
+#pragma unroll
+  for (int n = 0; n < G::NT; ++n) { zero16(dk[n]); zero16(dv[n]); }
+  const int nch = (p.L + CHUNK - 1) / CHUNK;
+  for (int c = 0; c < nch; ++c) {
+    const bf16raw* Qs = sm + (c & 1) * G::STAGE;
+    const bf16raw* Os = Qs + G::TILE;
+    const float* Ls = stats + (c & 1) * 2 * CHUNK;
+    const float* Ds = Ls + CHUNK;
+    chunk_load<HD>(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, (c + 1) * CHUNK, p.L);
+    sv = stat_load((c + 1) * CHUNK);
+    if (w.active) {
+      const int nrows = min(CHUNK, p.L - c * CHUNK);
+      const int nt = (nrows + 31) >> 5;
+#pragma unroll
+      for (int t = 0; t < QC; ++t)
+        // padded query rows: Ls = +huge -> P = 0, zero Q / dO rows; padded keys only feed dk / dv rows that are never stored
+        if (t < nt) dkv_tile<HD>(dk, dv, Qs, Os, Ls, Ds, t * 32, kf, vf, c2, ln, lane);
+    }
+    if (c + 1 < nch) {
+      bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE;
+      chunk_store<HD>(pre, nx, nx + G::TILE);
+      if (has_stat) stats[((c + 1) & 1) * 2 * CHUNK + threadIdx.x] = sv;
+    }
+    __syncthreads();
+  }
+  if (!w.active) return;
+  bf16raw* stg = sm + w.wave * MA_STAGE_ELEMS;
+  auto base_of = [&](int r) -> bf16raw* {
+    const int kk = w.row0 + r;
+    if (kk >= p.L) return nullptr;
+    return attn_cls_row(p, kk) ? dqkv_cls + (long)w.s * p.ld_dqkv : dqkv + lin_row(w.li, kk) * p.ld_dqkv;
+  };
+  store_rows<HD>(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * HD : nullptr; });
+  store_rows<HD>(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * HD : nullptr; });
+}
+
+// host side ---------------------------------------------------------------------------------------
+static dim3 grid_of(const AttnP& p) { return dim3((unsigned)p.S * (unsigned)cdiv(p.L, ROWS), p.H); }
+
+template <int HD>
+static int fwd_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+  hipLaunchKernelGGL(fwd_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_KV, st, p, (const bf16raw*)qkv, (bf16raw*)out, lse);
+  return check_launch("attn_fwd_hd");
+}
+template <int HD>
+static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
+                      void* dqkv_cls, hipStream_t st) {
+  hipLaunchKernelGGL(bwd_dq_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_KV, st, p, (const bf16raw*)qkv, (const bf16raw*)o,
+                     (const bf16raw*)dout, lse, delta, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
+  const int rc = check_launch("attn_bwd_dq_hd");
+  if (rc) return rc;
+  allow_lds<bwd_dkv_kernel<HD>>(Geo<HD>::LDS_DKV);
+  hipLaunchKernelGGL(bwd_dkv_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_DKV, st, p, (const bf16raw*)qkv, (const bf16raw*)dout,
+                     lse, (const float*)delta, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
+  return check_launch("attn_bwd_dkv_hd");
+}
+
+}  // namespace hdim
+
+bool attn_hd_eligible(int dtype, int L, int hd) { return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && L > 32; }
+
+int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdim::fwd_launch<32>(p, qkv, out, lse, st);
+    case 96: return hdim::fwd_launch<96>(p, qkv, out, lse, st);
+    case 128: return hdim::fwd_launch<128>(p, qkv, out, lse, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_hd: head_dim %d", hd);
+}
+
+int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
+                       void* dqkv, void* dqkv_cls, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdim::bwd_launch<32>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+    case 96: return hdim::bwd_launch<96>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+    case 128: return hdim::bwd_launch<128>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_hd: head_dim %d", hd);
+}
+
+}  // namespace vtx
