@@ -68,9 +68,10 @@ const char* vtx_last_error_string(void);
  * version 230; fp32 attention of more than 32 tokens with head_dim 64, without `probs`: mfma, the default, runs the exact-fp32 MFMA
  * kernels of csrc/attn_f32.hip -- fp32 operands, scores, probabilities and accumulators, the VALU kernels' arithmetic in another
  * summation order; valu restores the VALU kernels bit for bit; bf16 is not touched by either value), "attn_hd" = mfma|valu (bf16
- * attention of more than 32 tokens with head_dim 32, 96 or 128: mfma, the default, runs the chunk-streaming MFMA kernels of
- * csrc/attn_hd.hip; valu the VALU kernels, which serve everything else at those head dims; head_dim 64 is not touched by either
- * value), "tn_cus" = n (compute units the weight-gradient
+ * attention with head_dim 32, 96 or 128: mfma, the default, runs the MFMA kernels of csrc/attn_hd.hip -- chunk-streaming above
+ * 32 tokens in every layout, packed (32 / L sequences a tile) for up to 32 tokens in VTX_ATTN_CONTIG and VTX_ATTN_TIME_CLS; valu
+ * the VALU kernels, which serve everything else at those head dims (fp32, VTX_ATTN_SPACE and VTX_ATTN_SPACE_NOCLS of up to 32
+ * tokens, the `probs` pass); head_dim 64 is not touched by either value), "tn_cus" = n (compute units the weight-gradient
  * kernel's one-round slab split is sized for: 256; 240 leaves room for 16 CUs held by a collective in flight -- another, equally fixed
  * summation order of the slabs), "attn_hw_fwd", "attn_hw_bwd" = n
  * (short-sequence attention: n heads of a row tile per workgroup, 0 = one head and four row tiles; defaults 16 / 4), "pp_grid", "pp_cg",

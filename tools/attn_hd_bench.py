@@ -1,10 +1,11 @@
 """Self-attention by head dim at equal FLOPs (GPU box only): D = 768 as 24 x 32, 12 x 64, 8 x 96 and 6 x 128, bf16.
 
-    python tools/attn_hd_bench.py [spatial] [joint] [temporal] [hd=32,64,96,128] [rounds=5] [iters=5]
+    python tools/attn_hd_bench.py [spatial] [joint] [temporal] [temporal_cls] [hd=32,64,96,128] [rounds=5] [iters=5]
 
-  spatial    96 clips x 8 frames, VTX_ATTN_SPACE, L = 197 (the headline workload's spatial attention)
-  joint      8 clips, VTX_ATTN_CONTIG, L = 1569
-  temporal   S = 96 * 196, VTX_ATTN_CONTIG, L = 8 (the packed kernels: VALU at 32 / 96 / 128, MFMA at 64)
+  spatial       96 clips x 8 frames, VTX_ATTN_SPACE, L = 197 (the headline workload's spatial attention)
+  joint         8 clips, VTX_ATTN_CONTIG, L = 1569
+  temporal      S = 96 * 196, VTX_ATTN_CONTIG, L = 8 (the packed kernels of each head dim; attn_hd=valu: the packed VALU kernels)
+  temporal_cls  B = 96, P = 196, T = 8, VTX_ATTN_TIME_CLS, L = 9 (the temporal attention of the space-then-time order)
 
 Every (head dim, attn_hd value) pair is a configuration; a round times the forward and the backward of every configuration
 once (`iters` launches behind two warm-up launches, device events), and the rounds are interleaved, so that drift of the
@@ -23,7 +24,7 @@ for p in (ROOT, os.path.join(ROOT, 'videotransformer-pytorch_amd')):
 import torch  # noqa: E402
 import vtx  # noqa: E402
 from vtx import ops  # noqa: E402
-from vtx._lib import ATTN_CONTIG, ATTN_SPACE  # noqa: E402
+from vtx._lib import ATTN_CONTIG, ATTN_SPACE, ATTN_TIME_CLS  # noqa: E402
 
 DEV = 'cuda:0'
 ROOF = 2500.0
@@ -47,6 +48,9 @@ def shape_of(name):
     if name == 'spatial':
         B, T, P = 96, 8, 196
         return ATTN_SPACE, B * T, P + 1, B, T, P, B * (P * T + 1), B * P * T + B * T
+    if name == 'temporal_cls':
+        B, T, P = 96, 8, 196
+        return ATTN_TIME_CLS, B * P, T + 1, B, T, P, B * (P * T + 1), B * P * T + B * P
     S, L = (8, 1569) if name == 'joint' else (96 * 196, 8)
     return ATTN_CONTIG, S, L, 0, 0, 0, S * L, S * L
 
@@ -58,8 +62,8 @@ def bench(name, hds, rounds, iters, has_option):
     qkv, do = r(rin, 3 * D), r(rout, D)
     o = torch.empty(rout, D, device=DEV, dtype=bf)
     dqkv = torch.empty(rin, 3 * D, device=DEV, dtype=bf)
-    dcls = torch.empty(max(S, 1), 3 * D, device=DEV, dtype=bf) if mode == ATTN_SPACE else None
-    configs = [(hd, v) for hd in hds for v in (('mfma', 'valu') if hd != 64 and has_option and L > 32 else ('-',))]
+    dcls = torch.empty(max(S, 1), 3 * D, device=DEV, dtype=bf) if mode in (ATTN_SPACE, ATTN_TIME_CLS) else None
+    configs = [(hd, v) for hd in hds for v in (('mfma', 'valu') if hd != 64 and has_option else ('-',))]
     times = {c: ([], []) for c in configs}
     for _ in range(rounds):
         for hd, v in configs:
@@ -82,7 +86,7 @@ def bench(name, hds, rounds, iters, has_option):
 
 def main():
     kv = dict(a.split('=') for a in sys.argv[1:] if '=' in a)
-    names = [a for a in sys.argv[1:] if '=' not in a] or ['spatial', 'joint', 'temporal']
+    names = [a for a in sys.argv[1:] if '=' not in a] or ['spatial', 'joint', 'temporal', 'temporal_cls']
     hds = [int(h) for h in kv.get('hd', '32,64,96,128').split(',')]
     try:
         vtx.set_option('attn_hd', 'mfma')

@@ -309,7 +309,7 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
 // Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins.  The mode matters
 // up to 32 tokens only: CONTIG and TIME_CLS are packed, SPACE_NOCLS runs the one-workgroup kernels at one tile, SPACE (no model
 // has P < 32) the VALU kernels as before.
-enum Route { SMALL, MFMA, LONG, F32, VALU, HDIM };
+enum Route { SMALL, MFMA, LONG, F32, VALU, HDIM, HDSMALL };
 static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // VTX_ATTN_VALU=1 forces the VALU path.
   if (options().attn_valu) return VALU;
@@ -322,8 +322,12 @@ static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
   if (options().attn_f32 && !probs && attn_f32_eligible(dtype, L, hd)) return F32;
   // bf16, head_dim 32 / 96 / 128, more than 32 tokens -> chunk-streaming MFMA kernels (attn_hd.hip); VTX_ATTN_HD=valu sends them
-  // back here.  Everything else at those head dims (fp32, up to 32 tokens) has no other kernel: the routes above all ask for 64.
+  // back here.
   if (options().attn_hd && attn_hd_eligible(dtype, L, hd)) return HDIM;
+  // bf16, head_dim 32 / 96 / 128, up to 32 tokens, CONTIG or TIME_CLS -> packed MFMA kernels (attn_hd.hip), under the same switch.
+  // Everything else at those head dims (fp32; SPACE and SPACE_NOCLS of up to 32 tokens, which no model reaches) has no other
+  // kernel: the routes above all ask for 64.
+  if (options().attn_hd && attn_hd_small_eligible(dtype, mode, L, hd)) return HDSMALL;
   return VALU;
 }
 
@@ -424,6 +428,7 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
     case LONG: rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st); break;
     case F32: rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st); break;
     case HDIM: rc = attn_fwd_hd_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
+    case HDSMALL: rc = attn_fwd_hd_small_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case VALU: rc = f32 ? valu_fwd_launch<float, 0>(p, d, st) : valu_fwd_launch<bf16raw, 0>(p, d, st); break;
   }
   if (rc || !d->probs) return rc;
@@ -453,6 +458,7 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
     case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case HDIM: return attn_bwd_hd_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case HDSMALL: return attn_bwd_hd_small_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
     case VALU: break;
   }
   return d->f.dtype == VTX_F32 ? valu_bwd_launch<float>(p, d, st) : valu_bwd_launch<bf16raw>(p, d, st);

@@ -290,5 +290,10 @@ bool attn_hd_eligible(int dtype, int L, int hd);
 int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
                        void* dqkv, void* dqkv_cls, hipStream_t st);
+// attn_hd.hip, up to 32 tokens (CONTIG, TIME_CLS): the packed kernels
+bool attn_hd_small_eligible(int dtype, int mode, int L, int hd);
+int attn_fwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
+int attn_bwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                             void* dqkv_cls, hipStream_t st);
 
 }  // namespace vtx

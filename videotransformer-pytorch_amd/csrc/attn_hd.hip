@@ -1,4 +1,5 @@
-// attn_hd.hip -- bf16 MFMA attention core for head_dim 32, 96 and 128, more than 32 tokens per sequence, all four layouts.
+// attn_hd.hip -- bf16 MFMA attention core for head_dim 32, 96 and 128: more than 32 tokens per sequence in all four layouts
+// (namespace hdim, described here), up to 32 tokens in the layouts CONTIG and TIME_CLS (namespace hdsmall, at the end of the file).
 //
 // The structure is the chunk streaming of attn_stream.h (read its header first: transposed scores, a workgroup of 4 waves owns 128
 // queries -- 128 keys in the dk / dv kernel --, the other operands stream through two LDS stages, one barrier per chunk, dk / dv
@@ -495,7 +496,346 @@ static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void
 
 }  // namespace hdim
 
+// =====================================================================================================================
+// Up to 32 tokens, layouts CONTIG and TIME_CLS: the packed formulation of attn_mfma.hip's attn_fwd_small_kernel /
+// attn_bwd_small_kernel (read the comment there), over HD.  G = 32 / L sequences share one 32-row tile under a block-diagonal
+// mask, ONE WAVE handles a (tile, head) pair end to end, row fragments come straight from HBM, the transposed operands sit in
+// wave-private LDS tiles, whole rows are stored through the idle tile, delta is neither read nor written.
+// A wave-private tile is Geo<HD>::NS slabs of the swizzled [32][64] tile (4 KiB at head_dim 32, 8 KiB at 96 and 128; the
+// upper half of the last slab is never written and never read at 32 and 96: a 32-column slab would need a swizzle and readers
+// of its own for 2 KiB a wave).  Forward: one tile (V).  Backward: tile A (K, then Q), tile B (dO) and 32 lse + 32 delta:
+// 8.25 KiB at 32, 16.25 KiB at 96 / 128 -- that is what bounds the waves of a CU there (9 of them in 160 KiB; a workgroup
+// of 4 takes 65 KiB, hence the opt-in), and the register bound follows it: two waves a SIMD, 256 registers.
+// attn_hw_fwd / attn_hw_bwd mean what they mean at head_dim 64 (n heads of a row tile per workgroup, head groups of a tile in
+// consecutive workgroups; 0 = one head, four row tiles), capped at MAXW = 8 waves: at 96 / 128 for the forward's registers and
+// the backward's LDS (D = 768 has 8 and 6 heads there), at 32 because 8 heads measured faster than 16 (temporal forward at 24
+// heads: 0.191 against 0.245 ms, profiles/attn_hd_small_bench.txt).
+// =====================================================================================================================
+namespace hdsmall {
+
+using hdim::Frag;
+using hdim::Geo;
+
+template <int HD> struct Sm {
+  static constexpr int SLAB = 32 * 64;                                  // elements of one [32][64] slab
+  static constexpr int TILE = Geo<HD>::NS * SLAB;
+  static constexpr int LDS_FWD = TILE * 2;                              // V tile
+  static constexpr int LDS_BWD = 2 * TILE * 2 + 2 * 32 * 4;             // tile A (K, then Q), tile B (dO) + lse + delta
+  static constexpr int MAXW = 8;                                        // waves of a heads-per-workgroup launch
+};
+
+// SmallRows / small_rows of attn_mfma.hip, restated (that file stays as it is).  Tile row j < used belongs to sequence
+// sq = tile * G + j / L, token i = j % L; CLS = VTX_ATTN_TIME_CLS.  grad: row of dqkv, or -1 - (row of dqkv_cls).
+struct Rows { long in, out, grad, lse; };
+template <bool CLS>
+__device__ inline Rows rows_of(const AttnP& p, int tile, int G, int j) {
+  Rows r;
+  const int L = p.L;
+  if (!CLS) {
+    const long row = (long)tile * (G * L) + j;
+    const long sq = row / L;
+    r.in = r.out = r.grad = row;
+    r.lse = sq * p.H * L + (row - sq * L);
+    return r;
+  }
+  const int g = j / L, i = j - g * L;
+  const long sq = (long)tile * G + g;
+  const long b = sq / p.P;
+  r.in = i == 0 ? b * (1 + (long)p.P * p.T) : sq * p.T + b + i;
+  r.out = i == 0 ? (long)p.B * p.P * p.T + sq : sq * p.T + (i - 1);
+  r.grad = i == 0 ? -1 - sq : r.in;
+  r.lse = sq * p.H * L + i;
+  return r;
+}
+
+// A row's HD columns straight from HBM (an invalid lane reads nothing and holds zeros).
+template <int HD>
+__device__ __forceinline__ void load_frags(Frag<HD>& f, const bf16raw* base, long ld, int col0, long row, bool valid, int lane) {
+#pragma unroll
+  for (int ks = 0; ks < Geo<HD>::NK; ++ks) {
+    union { bf16x8 v; uint4 u; } x;
+    x.u = make_uint4(0, 0, 0, 0);
+    if (valid) x.u = *reinterpret_cast<const uint4*>(base + row * ld + col0 + ks * 16 + 8 * (lane >> 5));
+    f.f[ks] = x.v;
+  }
+}
+// The row fragments of a 32-row tile (one row per lane) into the wave's tile, slab by slab.
+template <int HD>
+__device__ __forceinline__ void put_tile(bf16raw* t, const Frag<HD>& f, const FragOff& fo) {
+#pragma unroll
+  for (int ks = 0; ks < Geo<HD>::NK; ++ks) *reinterpret_cast<bf16x8*>(t + (ks >> 2) * Sm<HD>::SLAB + fo.rows[ks & 3]) = f.f[ks];
+}
+// acc[n][d][j] += sum_i tile[i][32 n + d] c[i][j] over the tile's 32 rows, c = 16 values per lane in accumulator order
+template <int HD>
+__device__ __forceinline__ void accum(f32x16 (&acc)[Geo<HD>::NT], const bf16raw* t, const float* c, const FragOff& fo) {
+#pragma unroll
+  for (int s2 = 0; s2 < 2; ++s2) {
+    const bf16x8 pb = pack8(c + 8 * s2);
+#pragma unroll
+    for (int n = 0; n < Geo<HD>::NT; ++n)
+      acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(t + (n >> 1) * Sm<HD>::SLAB, 16 * s2, n & 1, fo), pb, acc[n], 0, 0, 0);
+  }
+}
+
+struct Who {
+  int lane, wave, tile, h;
+  bool run;
+};
+// HW: wave w of the workgroup works on head w of its head group, (head group, tile) folded into blockIdx.x, head group fastest;
+// otherwise one head (blockIdx.y) and four row tiles per workgroup.
+template <bool HW>
+__device__ inline Who who(const AttnP& p, int ntiles) {
+  Who w;
+  w.lane = threadIdx.x & 63;
+  w.wave = threadIdx.x >> 6;
+  const int hw_w = blockDim.x >> 6, hw_ng = HW ? (p.H + hw_w - 1) / hw_w : 1;
+  w.tile = HW ? (int)(blockIdx.x / hw_ng) : blockIdx.x * 4 + w.wave;
+  w.h = HW ? w.wave + (int)(blockIdx.x % hw_ng) * hw_w : blockIdx.y;
+  w.run = w.tile < ntiles && w.h < p.H;
+  return w;
+}
+
+template <int HD, bool HW, bool CLS>
+__global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS) void fwd_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
+                                                                              bf16raw* __restrict__ out, float* __restrict__ lse) {
+  typedef Geo<HD> G_;
+  extern __shared__ __attribute__((aligned(16))) char sm_raw[];
+  const Who w = who<HW>(p, ntiles);
+  if (!w.run) return;                              // (no workgroup barrier below: a wave is on its own)
+  const int lane = w.lane, h = w.h, tile = w.tile, D = p.H * HD;
+  bf16raw* Vs = reinterpret_cast<bf16raw*>(sm_raw + w.wave * Sm<HD>::LDS_FWD);
+  const int L = p.L, G = 32 / L, used = G * L;
+  const long row0 = (long)tile * used, total = (long)p.S * L;
+  const int i = lane & 31;
+  const bool valid = i < used && row0 + i < total;
+  const Rows me = rows_of<CLS>(p, tile, G, valid ? i : 0);
+  const FragOff fo = make_frag_off(lane);
+  Frag<HD> qf, kf, vf;
+  load_frags<HD>(qf, qkv, p.ld_qkv, h * HD, me.in, valid, lane);
+  load_frags<HD>(kf, qkv, p.ld_qkv, D + h * HD, me.in, valid, lane);
+  load_frags<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, me.in, valid, lane);
+  put_tile<HD>(Vs, vf, fo);
+  f32x16 st;
+  zero16(st);
+#pragma unroll
+  for (int ks = 0; ks < G_::NK; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.f[ks], qf.f[ks], st, 0, 0, 0);
+  const float c2 = p.scale * LOG2E;
+  const int qseq = i / L;
+  float m = -INFINITY;
+  float pr[16];
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int key = crow(r, lane);
+    const bool ok = valid && key < used && key / L == qseq && row0 + key < total;
+    pr[r] = ok ? st[r] * c2 : -INFINITY;
+    m = fmaxf(m, pr[r]);
+  }
+  m = fmaxf(m, __shfl_xor(m, 32, 64));
+  if (!valid) m = 0.f;
+  float l = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { pr[r] = __builtin_amdgcn_exp2f(pr[r] - m); l += pr[r]; }
+  l += __shfl_xor(l, 32, 64);
+  wave_lds_sync();
+  f32x16 acc[G_::NT];
+#pragma unroll
+  for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
+  accum<HD>(acc, Vs, pr, fo);
+  // whole rows through the (now idle) V tile
+  hdim::store_rows<HD>(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
+    return (r < used && row0 + r < total) ? out + rows_of<CLS>(p, tile, G, r).out * p.ld_out + h * HD : nullptr;
+  });
+  if (valid && lane < 32) lse[me.lse + (long)h * L] = m * LN2 + __logf(l);
+}
+
+template <int HD, bool HW, bool CLS>
+__global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD == 32 ? 4 : 2) void bwd_kernel(
+    AttnP p, int ntiles, const bf16raw* __restrict__ qkv, const bf16raw* __restrict__ o, const bf16raw* __restrict__ dout,
+    const float* __restrict__ lse, bf16raw* __restrict__ dqkv, bf16raw* __restrict__ dqkv_cls) {
+  typedef Geo<HD> G_;
+  extern __shared__ __attribute__((aligned(16))) char sm_raw[];
+  const Who w = who<HW>(p, ntiles);
+  if (!w.run) return;
+  const int lane = w.lane, h = w.h, tile = w.tile, D = p.H * HD;
+  // two wave-private tiles: A holds K for phase 1 (and stages dQ), then Q for phase 2 (and stages dK); B holds dO (and stages dV)
+  char* wl = sm_raw + w.wave * Sm<HD>::LDS_BWD;
+  bf16raw* Ks = reinterpret_cast<bf16raw*>(wl);
+  bf16raw* Qs = Ks;
+  bf16raw* Os = Ks + Sm<HD>::TILE;
+  float* Ls = reinterpret_cast<float*>(Os + Sm<HD>::TILE);
+  float* Ds = Ls + 32;
+  const int L = p.L, G = 32 / L, used = G * L;
+  const long row0 = (long)tile * used, total = (long)p.S * L;
+  const int i = lane & 31;
+  const bool valid = i < used && row0 + i < total;
+  const Rows me = rows_of<CLS>(p, tile, G, valid ? i : 0);
+  const FragOff fo = make_frag_off(lane);
+  Frag<HD> qf, kf, vf, df;
+  load_frags<HD>(qf, qkv, p.ld_qkv, h * HD, me.in, valid, lane);
+  load_frags<HD>(kf, qkv, p.ld_qkv, D + h * HD, me.in, valid, lane);
+  load_frags<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, me.in, valid, lane);
+  load_frags<HD>(df, dout, p.ld_dout, h * HD, me.out, valid, lane);
+  float dl = 0.f;
+  {
+    Frag<HD> of;
+    load_frags<HD>(of, o, p.ld_out, h * HD, me.out, valid, lane);
+#pragma unroll
+    for (int ks = 0; ks < G_::NK; ++ks) dl += frag_dot(df.f[ks], of.f[ks]);
+  }
+  dl += __shfl_xor(dl, 32, 64);
+  float l2 = 1e30f;
+  if (valid) l2 = lse[me.lse + (long)h * L] * LOG2E;
+  // destination of tile row r's gradient (column origin col of the [3D] row)
+  auto dst = [&](int r, int col) -> bf16raw* {
+    if (!(r < used && row0 + r < total)) return nullptr;
+    const long g = rows_of<CLS>(p, tile, G, r).grad;
+    return (CLS && g < 0 ? dqkv_cls + (-1 - g) * p.ld_dqkv : dqkv + g * p.ld_dqkv) + col + h * HD;
+  };
+  put_tile<HD>(Ks, kf, fo);
+  put_tile<HD>(Os, df, fo);
+  if (lane < 32) { Ls[i] = l2; Ds[i] = dl; }
+  const float c2 = p.scale * LOG2E;
+  const int myseq = i / L;
+  // ---- phase 1: lanes = queries.  dQ^T = K^T dS^T
+  {
+    f32x16 st, dp;
+    zero16(st);
+    zero16(dp);
+#pragma unroll
+    for (int ks = 0; ks < G_::NK; ++ks) {
+      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.f[ks], qf.f[ks], st, 0, 0, 0);
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf.f[ks], df.f[ks], dp, 0, 0, 0);
+    }
+    float ds[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int key = crow(r, lane);
+      const bool ok = valid && key < used && key / L == myseq && row0 + key < total;
+      const float pr = ok ? __builtin_amdgcn_exp2f(st[r] * c2 - l2) : 0.f;
+      ds[r] = pr * (dp[r] - dl) * p.scale;
+    }
+    wave_lds_sync();
+    f32x16 acc[G_::NT];
+#pragma unroll
+    for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
+    accum<HD>(acc, Ks, ds, fo);
+    // K tile: its last reader was the MFMA chain above
+    hdim::store_rows<HD>(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
+  }
+  // ---- phase 2: lanes = keys.  dV^T = dO^T P, dK^T = Q^T dS.  Only this phase's accumulators are live from here on.
+  {
+    put_tile<HD>(Qs, qf, fo);                      // tile A is free again: store_rows above ends with a wave-level sync
+    wave_lds_sync();
+    f32x16 st, dp;
+    zero16(st);
+    zero16(dp);
+#pragma unroll
+    for (int ks = 0; ks < G_::NK; ++ks) {
+      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf.f[ks], kf.f[ks], st, 0, 0, 0);
+      // dO row fragments come back from tile B (it holds dO until dv is staged there) instead of living across the two phases
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os + (ks >> 2) * Sm<HD>::SLAB, 0, ks & 3, fo), vf.f[ks], dp, 0, 0, 0);
+    }
+    float pr[16], ds[16];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const int qrow = 8 * g + 4 * (lane >> 5);
+      const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
+      const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
+      const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int r = 4 * g + j;
+        const int q = qrow + j;
+        const bool ok = valid && q < used && q / L == myseq;
+        const float e = ok ? __builtin_amdgcn_exp2f(st[r] * c2 - lv[j]) : 0.f;
+        pr[r] = e;
+        ds[r] = e * (dp[r] - dvv[j]) * p.scale;
+      }
+    }
+    f32x16 dk[G_::NT], dv[G_::NT];
+#pragma unroll
+    for (int n = 0; n < G_::NT; ++n) { zero16(dk[n]); zero16(dv[n]); }
+    accum<HD>(dv, Os, pr, fo);
+    accum<HD>(dk, Qs, ds, fo);
+    hdim::store_rows<HD>(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
+    hdim::store_rows<HD>(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
+  }
+}
+
+// host side ---------------------------------------------------------------------------------------
+// heads per workgroup: option value n > 0, capped at the head dim's MAXW waves and at H
+template <int HD> static int hw_waves(int n, int H) { n = n < H ? n : H; return n < Sm<HD>::MAXW ? n : Sm<HD>::MAXW; }
+
+template <int HD, bool CLS>
+static int fwd_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+  const int G = 32 / p.L;
+  const int ntiles = (p.S + G - 1) / G;
+  if (options().attn_hw_fwd > 0) {
+    const int w = hw_waves<HD>(options().attn_hw_fwd, p.H);
+    hipLaunchKernelGGL((fwd_kernel<HD, true, CLS>), dim3((unsigned)cdiv(p.H, w) * ntiles), dim3(64 * w), (size_t)w * Sm<HD>::LDS_FWD, st, p, ntiles,
+                       (const bf16raw*)qkv, (bf16raw*)out, lse);
+  } else {
+    hipLaunchKernelGGL((fwd_kernel<HD, false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * Sm<HD>::LDS_FWD, st, p, ntiles,
+                       (const bf16raw*)qkv, (bf16raw*)out, lse);
+  }
+  return check_launch("attn_fwd_hd_small");
+}
+template <int HD, bool CLS>
+static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, void* dqkv_cls,
+                      hipStream_t st) {
+  const int G = 32 / p.L;
+  const int ntiles = (p.S + G - 1) / G;
+  if (options().attn_hw_bwd > 0) {
+    const int w = hw_waves<HD>(options().attn_hw_bwd, p.H);
+    const size_t lds = (size_t)w * Sm<HD>::LDS_BWD;
+    allow_lds<bwd_kernel<HD, true, CLS>>(lds);
+    hipLaunchKernelGGL((bwd_kernel<HD, true, CLS>), dim3((unsigned)cdiv(p.H, w) * ntiles), dim3(64 * w), lds, st, p, ntiles, (const bf16raw*)qkv,
+                       (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
+  } else {
+    const size_t lds = (size_t)4 * Sm<HD>::LDS_BWD;
+    allow_lds<bwd_kernel<HD, false, CLS>>(lds);
+    hipLaunchKernelGGL((bwd_kernel<HD, false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), lds, st, p, ntiles, (const bf16raw*)qkv,
+                       (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
+  }
+  return check_launch("attn_bwd_hd_small");
+}
+template <int HD>
+static int fwd_launch_m(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+  return p.mode == VTX_ATTN_TIME_CLS ? fwd_launch<HD, true>(p, qkv, out, lse, st) : fwd_launch<HD, false>(p, qkv, out, lse, st);
+}
+template <int HD>
+static int bwd_launch_m(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, void* dqkv_cls,
+                        hipStream_t st) {
+  return p.mode == VTX_ATTN_TIME_CLS ? bwd_launch<HD, true>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st)
+                                     : bwd_launch<HD, false>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+}
+
+}  // namespace hdsmall
+
 bool attn_hd_eligible(int dtype, int L, int hd) { return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && L > 32; }
+// up to 32 tokens: the two layouts whose packed tile is addressed row by row (rows_of); SPACE and SPACE_NOCLS stay on the VALU kernels
+bool attn_hd_small_eligible(int dtype, int mode, int L, int hd) {
+  return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && (mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_TIME_CLS) && L >= 1 && L <= 32;
+}
+
+int attn_fwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdsmall::fwd_launch_m<32>(p, qkv, out, lse, st);
+    case 96: return hdsmall::fwd_launch_m<96>(p, qkv, out, lse, st);
+    case 128: return hdsmall::fwd_launch_m<128>(p, qkv, out, lse, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_hd_small: head_dim %d", hd);
+}
+
+int attn_bwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                             void* dqkv_cls, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdsmall::bwd_launch_m<32>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 96: return hdsmall::bwd_launch_m<96>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 128: return hdsmall::bwd_launch_m<128>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_hd_small: head_dim %d", hd);
+}
 
 int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
   switch (hd) {

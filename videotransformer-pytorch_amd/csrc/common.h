@@ -198,8 +198,8 @@ struct Options {
   int pp_cont = 1;           // VTX_GEMM_PP_CONT: continuous flow of the persistent NT GEMM (next tile's first K tiles requested
                              // inside the current main loop) for epilogues that leave the operand ring alone; 0 = per-tile prologue
   unsigned long long pp_trace = 0;   // device address of a long long[256][8][8] timeline buffer (tools/pp_timeline.py), 0 = off
-  int attn_hd = 1;           // VTX_ATTN_HD: bf16 attention of more than 32 tokens at head_dim 32 / 96 / 128: 1 = "mfma", the kernels of attn_hd.hip;
-                             // 0 = "valu", the VALU kernels of attn.hip.  (Last: the fields above keep their offsets.)
+  int attn_hd = 1;           // VTX_ATTN_HD: bf16 attention at head_dim 32 / 96 / 128: 1 = "mfma", the kernels of attn_hd.hip (up to 32 tokens: CONTIG and
+                             // TIME_CLS only); 0 = "valu", the VALU kernels of attn.hip.  (Last: the fields above keep their offsets.)
 };
 Options& options();
 
