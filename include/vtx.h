@@ -65,13 +65,14 @@ const char* vtx_last_error_string(void);
  * read once): "gemm_nt" = auto|pp256|dma2|ring128x3|ring128x4k32|ring256x3|ring256x3k32|ring256x4k32,
  * "gemm_tn" = auto|pp256|ring|dma2|w4, "gemm_nodma", "tn_safe", "attn_valu" = 0|1, "attn_long" = 0|1 (default 1; 0 sends bf16
  * attention of more than 256 tokens back to the fp32 VALU kernels and touches nothing else), "attn_f32" = mfma|valu (library
- * version 230; fp32 attention of more than 32 tokens with head_dim 64, without `probs`: mfma, the default, runs the exact-fp32 MFMA
- * kernels of csrc/attn_f32.hip -- fp32 operands, scores, probabilities and accumulators, the VALU kernels' arithmetic in another
- * summation order; valu restores the VALU kernels bit for bit; bf16 is not touched by either value), "attn_hd" = mfma|valu (bf16
+ * version 230; fp32 attention of more than 32 tokens, without `probs`: mfma, the default, runs the exact-fp32 MFMA kernels of
+ * csrc/attn_f32.hip (head_dim 64) and csrc/attn_hd_f32.hip (head_dim 32, 96, 128) -- fp32 operands, scores, probabilities and
+ * accumulators, the VALU kernels' arithmetic in another summation order; valu restores the VALU kernels bit for bit; bf16 is not
+ * touched by either value), "attn_hd" = mfma|valu (bf16
  * attention with head_dim 32, 96 or 128: mfma, the default, runs the MFMA kernels of csrc/attn_hd.hip -- chunk-streaming above
  * 32 tokens in every layout, packed (32 / L sequences a tile) for up to 32 tokens in VTX_ATTN_CONTIG and VTX_ATTN_TIME_CLS; valu
- * the VALU kernels, which serve everything else at those head dims (fp32, VTX_ATTN_SPACE and VTX_ATTN_SPACE_NOCLS of up to 32
- * tokens, the `probs` pass); head_dim 64 is not touched by either value), "tn_cus" = n (compute units the weight-gradient
+ * the VALU kernels, which serve everything else bf16 at those head dims (VTX_ATTN_SPACE and VTX_ATTN_SPACE_NOCLS of up to 32
+ * tokens, the `probs` pass); head_dim 64 and fp32 are not touched by either value), "tn_cus" = n (compute units the weight-gradient
  * kernel's one-round slab split is sized for: 256; 240 leaves room for 16 CUs held by a collective in flight -- another, equally fixed
  * summation order of the slabs), "attn_hw_fwd", "attn_hw_bwd" = n
  * (short-sequence attention: n heads of a row tile per workgroup, 0 = one head and four row tiles; defaults 16 / 4), "pp_grid", "pp_cg",

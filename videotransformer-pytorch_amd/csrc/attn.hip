@@ -14,8 +14,10 @@
 // run the MFMA kernels of attn_mfma.hip, more than 256 (785 spatial at 448^2, 1569
 // joint) those of attn_long.hip; fp32 with head_dim 64 and more than 32 tokens runs the exact-fp32 MFMA kernels of
 // attn_f32.hip.  These kernels are the fp32 path of up to 32 tokens, the `probs` pass (and the forward in front of it)
-// and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  At head_dim 32, 96 and 128 they are everything but bf16 above 32
-// tokens (attn_hd.hip; attn_hd=valu sends that back here too).  Algorithmic bytes per (sequence, head):
+// and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  At head_dim 32, 96 and 128 the same holds: bf16 runs the MFMA
+// kernels of attn_hd.hip (attn_hd=valu sends it back here), fp32 above 32 tokens the exact-fp32 MFMA kernels of attn_hd_f32.hip
+// (attn_f32=valu), and what stays here is fp32 of up to 32 tokens, bf16 SPACE / SPACE_NOCLS of up to 32 tokens and the `probs`
+// pass.  Algorithmic bytes per (sequence, head):
 // read 3*L*hd, write L*hd elements (+ L fp32 lse).
 #include <stdlib.h>
 #include "attn_common.h"
@@ -309,7 +311,7 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
 // Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins.  The mode matters
 // up to 32 tokens only: CONTIG and TIME_CLS are packed, SPACE_NOCLS runs the one-workgroup kernels at one tile, SPACE (no model
 // has P < 32) the VALU kernels as before.
-enum Route { SMALL, MFMA, LONG, F32, VALU, HDIM, HDSMALL };
+enum Route { SMALL, MFMA, LONG, F32, F32HD, VALU, HDIM, HDSMALL };
 static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // VTX_ATTN_VALU=1 forces the VALU path.
   if (options().attn_valu) return VALU;
@@ -321,12 +323,15 @@ static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // fp32, head_dim 64, more than 32 tokens -> exact-fp32 MFMA kernels (attn_f32.hip); VTX_ATTN_F32=valu sends them back here, and
   // so does a `probs` request: the probabilities are then recomputed from the lse of the kernel they always followed.
   if (options().attn_f32 && !probs && attn_f32_eligible(dtype, L, hd)) return F32;
+  // fp32, head_dim 32 / 96 / 128, more than 32 tokens -> exact-fp32 MFMA kernels (attn_hd_f32.hip), under the same switch and with
+  // the same `probs` rule.
+  if (options().attn_f32 && !probs && attn_hd_f32_eligible(dtype, L, hd)) return F32HD;
   // bf16, head_dim 32 / 96 / 128, more than 32 tokens -> chunk-streaming MFMA kernels (attn_hd.hip); VTX_ATTN_HD=valu sends them
   // back here.
   if (options().attn_hd && attn_hd_eligible(dtype, L, hd)) return HDIM;
   // bf16, head_dim 32 / 96 / 128, up to 32 tokens, CONTIG or TIME_CLS -> packed MFMA kernels (attn_hd.hip), under the same switch.
-  // Everything else at those head dims (fp32; SPACE and SPACE_NOCLS of up to 32 tokens, which no model reaches) has no other
-  // kernel: the routes above all ask for 64.
+  // Everything else at those head dims (fp32 of up to 32 tokens; SPACE and SPACE_NOCLS of up to 32 tokens, which no model
+  // reaches) has no other kernel.
   if (options().attn_hd && attn_hd_small_eligible(dtype, mode, L, hd)) return HDSMALL;
   return VALU;
 }
@@ -427,6 +432,7 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
     case MFMA: rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st); break;
     case LONG: rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st); break;
     case F32: rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st); break;
+    case F32HD: rc = attn_fwd_hd_f32_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case HDIM: rc = attn_fwd_hd_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case HDSMALL: rc = attn_fwd_hd_small_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case VALU: rc = f32 ? valu_fwd_launch<float, 0>(p, d, st) : valu_fwd_launch<bf16raw, 0>(p, d, st); break;
@@ -457,6 +463,7 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
     case MFMA: return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
+    case F32HD: return attn_bwd_hd_f32_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case HDIM: return attn_bwd_hd_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case HDSMALL: return attn_bwd_hd_small_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
     case VALU: break;

@@ -1,6 +1,6 @@
 // attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip and the chunk-streaming kernels
-// (attn_stream.h with its two tile policies, attn_long.hip and attn_f32.hip), and the swizzled-LDS / MFMA fragment helpers of the
-// two bf16 MFMA families.
+// (attn_stream.h with its two tile policies, attn_long.hip and attn_f32.hip; attn_hd.hip and attn_hd_f32.hip at the other head
+// dims), and the swizzled-LDS / MFMA fragment helpers of the two bf16 MFMA families.
 #pragma once
 #include "common.h"
 
@@ -295,5 +295,10 @@ bool attn_hd_small_eligible(int dtype, int mode, int L, int hd);
 int attn_fwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
                              void* dqkv_cls, hipStream_t st);
+// attn_hd_f32.hip (fp32, head_dim 32, 96, 128, more than 32 tokens)
+bool attn_hd_f32_eligible(int dtype, int L, int hd);
+int attn_fwd_hd_f32_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
+int attn_bwd_hd_f32_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
+                           void* dqkv, void* dqkv_cls, hipStream_t st);
 
 }  // namespace vtx

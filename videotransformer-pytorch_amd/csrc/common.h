@@ -182,8 +182,8 @@ struct Options {
                              // fp32 summation order of the weight gradients (still fixed for a given value: bit-reproducible).
   int attn_valu = 0;         // VTX_ATTN_VALU: fp32-VALU attention kernels also for bf16
   int attn_long = 1;         // VTX_ATTN_LONG: bf16 attention of more than 256 tokens on the MFMA kernels of attn_long.hip; 0 = the VALU kernels
-  int attn_f32 = 1;          // VTX_ATTN_F32: fp32 attention of more than 32 tokens (head_dim 64): 1 = "mfma", the exact-fp32 MFMA kernels of
-                             // attn_f32.hip; 0 = "valu", the VALU kernels of attn.hip
+  int attn_f32 = 1;          // VTX_ATTN_F32: fp32 attention of more than 32 tokens: 1 = "mfma", the exact-fp32 MFMA kernels of attn_f32.hip
+                             // (head_dim 64) and attn_hd_f32.hip (32, 96, 128); 0 = "valu", the VALU kernels of attn.hip
   int attn_hw_fwd = 16;      // VTX_ATTN_HW_FWD / _BWD: short-sequence attention with n heads of a row tile in one workgroup
   int attn_hw_bwd = 4;       //   (0: one head per workgroup, four row tiles; backward: 4 heads -- 512 contiguous bytes per row -- measured best)
   int attn_fused = 2;        // VTX_ATTN_FUSED: backward of the 33..224-token attention: 2 = one phase per (sequence, head), operands streamed (193..224
