@@ -362,11 +362,21 @@ static int launch_ring(const vtx_gemm_desc* d, const EpiParams& ep, hipStream_t 
 }
 
 // ------------------------------------------------------------------ bf16, 256x256 tile, two staggered wave groups
-// 8 waves as 2(M) x 4(N), each owning a 128x64 block of the tile (8 accumulators of 32x32).  Waves
+// 8 waves as 2(M) x 4(N), each owning a 128x64 block of the tile (32 accumulators of 16x16).  Waves
 // w and w+4 share a SIMD and sit in different groups (wr = w>>2); group 1 runs ONE barrier behind
-// group 0, so between any two barriers one wave of every SIMD is in an MFMA section (8 MFMAs =
+// group 0, so between any two barriers one wave of every SIMD is in an MFMA section (16 MFMAs =
 // 256 matrix-pipe cycles) while its partner is in a load section (LDS fragment reads + 2 LDS-DMA
 // pieces) -- the matrix pipe of every SIMD always has exactly one client.
+//
+// The instruction is v_mfma_f32_16x16x32_bf16 (every other bf16 kernel of the project issues 32x32x16):
+//   A: lane l holds row l&15, k = 8 (l>>4) + j, j = 0..7      B: lane l holds column l&15, the same k
+//   C/D: lane l holds column l&15, rows 4 (l>>4) + register
+// Same output tile per wave, the same 24 ds_read_b128 per K tile, the same matrix-pipe cycles (16 x 16 instead of 8 x 32
+// per phase) and the same BITS -- one 16x16x32 and two 32x32x16 over the same 32-deep step give identical fp32 sums
+// (tools/mfma_shape_bits.py).  The chip holds a higher clock on this shape (+4 - 18 % inside the main loop), which more than
+// pays for the 6 - 9 % more cycles per K tile that the MFMAs' longer hold on the vector issue port costs the partner wave's
+// load section: 3.0 - 5.5 % less time per launch on the step's six shapes, parent and this build alternated on one box
+// (profiles/mfma_shape_bench.txt).
 //
 // A K tile (64 deep) takes four phases per wave; the wave's block is cut into quadrants
 //   P1: read A0 (rows 0..63 of the block), B0 (cols 0..31)   MFMA A0 x B0
@@ -543,40 +553,48 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     issue(0, 1); issue(1, 1); issue(2, 1);
   };
 
-  // fragment addresses (elements): row (lane&31) of a 32-row group, chunk (2*ks + lane>>5) ^ swizzle;
-  // the swizzle (row>>1)&7 only depends on lane&31 because every group starts at a multiple of 32.
-  const int l31 = lane & 31;
-  int fr[4];
+  // fragment addresses (elements): row (lane&15) of a 16-row group, chunk (4*ks + lane>>4) ^ swizzle -- the 16 x 32 operand of
+  // v_mfma_f32_16x16x32_bf16: lane l holds row l&15, k = 8 (l>>4) + j of the 32-deep step ks.  The swizzle (row>>1)&7 only depends
+  // on lane&15 because every group starts at a multiple of 16, and each of the four 16-lane groups of a ds_read_b128 (8 lanes
+  // of one k-octet on rows {0-3, 12-15} or {4-11}, 8 of the next on the other rows) lands on 16 distinct 16-B slots.
+  const int l15 = lane & 15;
+  int fr[2];
 #pragma unroll
-  for (int ks = 0; ks < 4; ++ks) fr[ks] = l31 * PP_BK + (((2 * ks + (lane >> 5)) ^ ((l31 >> 1) & 7)) << 3);
+  for (int ks = 0; ks < 2; ++ks) fr[ks] = l15 * PP_BK + (((4 * ks + (lane >> 4)) ^ ((l15 >> 1) & 7)) << 3);
   const int a_grp = wr * 64 * PP_BK;             // first row of this wave's rows inside region A0 / A1
   const int b_grp = wc * 32 * PP_BK;             // ... inside region B0 / B1
 
+// fa[m][ks]: rows 16 m .. 16 m + 15 of the region's 64, k step ks; fb[n][ks]: columns 16 n .. of its 32
 #define PP_READ_A(buf_, kind_)                                                                         \
-  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)       \
-      fa[i][ks] = *reinterpret_cast<const bf16x8*>(lds + (buf_) * PP_BUF + (kind_) * PP_REGION + a_grp + i * 32 * PP_BK + fr[ks]);
+  _Pragma("unroll") for (int i = 0; i < 2; ++i) _Pragma("unroll") for (int q = 0; q < 4; ++q)          \
+      fa[2 * i + (q >> 1)][q & 1] = *reinterpret_cast<const bf16x8*>(lds + (buf_) * PP_BUF + (kind_) * PP_REGION + a_grp + (i * 32 + (q >> 1) * 16) * PP_BK + fr[q & 1]);
 #define PP_READ_B(buf_, kind_, fb_)                                                                    \
-  _Pragma("unroll") for (int ks = 0; ks < 4; ++ks)                                                     \
-      fb_[ks] = *reinterpret_cast<const bf16x8*>(lds + (buf_) * PP_BUF + (kind_) * PP_REGION + b_grp + fr[ks]);
+  _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                        \
+      fb_[q >> 1][q & 1] = *reinterpret_cast<const bf16x8*>(lds + (buf_) * PP_BUF + (kind_) * PP_REGION + b_grp + (q >> 1) * 16 * PP_BK + fr[q & 1]);
 // HW_: inside the fence right behind the section's request (waits of a rolling pass); HB_: behind the fence, in the same
-// scheduling region as the section's remaining six MFMAs -- the compiler mixes it into their shadow
+// scheduling region as the section's remaining twelve MFMAs -- the compiler mixes it into their shadow
 #define PP_MMA(i0_, j_, fb_, ISSUE_) PP_MMA_H(i0_, j_, fb_, ISSUE_, , )
 #ifndef VTX_PP_PRIO
 #define VTX_PP_PRIO 1   // 1 = s_setprio 1 around every MFMA section (default); experiments: 0 = none, 3 = the load sections at 1
 #endif
+// i0_ / j_: the 64-row half (A0 / A1) and the 32-column half (B0 / B1) of the wave's 128 x 64 block: accumulators
+// acc[4 i0_ .. 4 i0_ + 3][2 j_ .. 2 j_ + 1].  16 MFMAs of 16 cycles; the request slot sits behind the first four (64 cycles)
 #define PP_MMA_H(i0_, j_, fb_, ISSUE_, HW_, HB_)                                                       \
   if (VTX_PP_PRIO == 1) __builtin_amdgcn_s_setprio(1); else if (VTX_PP_PRIO == 3) __builtin_amdgcn_s_setprio(0); \
-  _Pragma("unroll") for (int ks = 0; ks < 4; ++ks) {                                                   \
-    _Pragma("unroll") for (int i = 0; i < 2; ++i)                                                      \
-        acc[(i0_) + i][j_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][ks], fb_[ks], acc[(i0_) + i][j_], 0, 0, 0); \
-    if (ks == 0) { __builtin_amdgcn_sched_barrier(0); ISSUE_; HW_ __builtin_amdgcn_sched_barrier(0); HB_ }     \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) {                                                   \
+    _Pragma("unroll") for (int i = 0; i < 2; ++i) {                                                    \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                    \
+        acc[4 * (i0_) + 2 * i + (q >> 1)][2 * (j_) + (q & 1)] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(   \
+            fa[2 * i + (q >> 1)][ks], fb_[q & 1][ks], acc[4 * (i0_) + 2 * i + (q >> 1)][2 * (j_) + (q & 1)], 0, 0, 0); \
+      if (ks == 0 && i == 0) { __builtin_amdgcn_sched_barrier(0); ISSUE_; HW_ __builtin_amdgcn_sched_barrier(0); HB_ } \
+    }                                                                                                  \
   }                                                                                                    \
   if (VTX_PP_PRIO == 1) __builtin_amdgcn_s_setprio(0); else if (VTX_PP_PRIO == 3) __builtin_amdgcn_s_setprio(1);
 #define PP_BAR() __builtin_amdgcn_s_barrier()
 
   // One 64-deep K tile = four phases.  ISS_: what the request slots of the four MFMA sections issue; H1_ .. H4_:
   // hooks inside the load sections of P1 .. P4.
-  // The LDS-DMA requests are issued in the shadow of the MFMAs (after the first two of a section): inside a load
+  // The LDS-DMA requests are issued in the shadow of the MFMAs (after the first four of a section: 64 cycles): inside a load
   // section each costs the wave 100+ cycles on the critical path, among MFMAs ~60.  (Round 3, same box A/B of three
   // builds that issued P2's and / or P4's request in that phase's load section instead -- 4 and 0 fragment reads there
   // -- behind the section's wait, i.e. at the same place of the request order: +0.5 / +0.8 / +1.1 % over the twelve GEMMs
@@ -620,13 +638,13 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       H3_                                                                                              \
       lgkm0();                                                                                         \
       PP_BAR();                                                                                        \
-      PP_MMA_H(2, 1, fb1, ISS_(1, kt + 2, e2), M3W_, M3B_);                                            \
+      PP_MMA_H(1, 1, fb1, ISS_(1, kt + 2, e2), M3W_, M3B_);                                            \
       PP_BAR();                                                                                        \
       /* P4: no reads; P1 of the next K tile will read A0(kt+1), B0(kt+1) */                           \
       if (W4_) { if (w2) { if (X4_) wait_vmcnt<8 + NST>(); else if (R4_) wait_vmcnt<10>(); else wait_vmcnt<8>(); } else if (w1) wait_vmcnt<4>(); } \
       H4_                                                                                              \
       PP_BAR();                                                                                        \
-      PP_MMA_H(2, 0, fb0, ISS_(2, kt + 2, e2), M4W_, M4B_);                                            \
+      PP_MMA_H(1, 0, fb0, ISS_(2, kt + 2, e2), M4W_, M4B_);                                            \
       PP_BAR();                                                                                        \
     }
 #define PP_ISS_COND(kind_, ktv_, ex_) if (ex_) issue(kind_, ktv_)          /* only K tiles of this tile */
@@ -645,7 +663,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
   // staging slice, read back into two registers before the first pass.
   typedef __attribute__((address_space(3))) char lds_char;
   const unsigned slot_rd = (unsigned)(unsigned long)(lds_char*)(smem + PP_RING_BYTES);
-  const unsigned bias_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) + 256 + (lane & 31) * 4);
+  const unsigned bias_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) + 256 + (lane & 15) * 4);
   // result stores one wave issues per tile when none of its 16 (pass, half-row) groups is empty: one per group, two with a
   // second output (the activation kernels are only instantiated for the FFN: GELU + GELU', or GELU + pre-activation copy)
   constexpr int NST = HAS_ACT ? 32 : 16;
@@ -663,24 +681,26 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
   m0 = m0s; n0 = n0s;
   prologue();
   while (true) {
-    f32x16 acc[4][2];
+    // acc[p][n]: rows 16 p .. 16 p + 15, columns 16 n .. 16 n + 15 of the wave's 128 x 64 block; lane l holds column l&15,
+    // rows 4 (l>>4) + register
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    bf16x8 fa[2][4], fb0[4], fb1[4];
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    bf16x8 fa[4][2], fb0[2][2], fb1[2][2];
     if constexpr (PREG) {                          // fragment addresses per tile from an opaque lane id: four registers that are not live
       int lf = lane;                               // through the epilogue, where the block's 64 registers sit beside the accumulators
       asm volatile("" : "+v"(lf));
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) fr[ks] = (lf & 31) * PP_BK + (((2 * ks + (lf >> 5)) ^ (((lf & 31) >> 1) & 7)) << 3);
+      for (int ks = 0; ks < 2; ++ks) fr[ks] = (lf & 15) * PP_BK + (((4 * ks + (lf >> 4)) ^ (((lf & 15) >> 1) & 7)) << 3);
     }
     const bool more_c = CONT && t_next < tend;     // continuous flow: another tile follows this one
     // ---- epilogue state of this tile.  epi_head() fills the store addressing (after the main loop -- or in front of its last K
     // tile when the epilogue ROLLS: the first four passes of a lean tile, rows 0 .. 63 of the wave's block, which are final
-    // after P2 of the last K tile, then run inside P3 / P4 of that K tile, in the shadow of its last sixteen MFMAs)
+    // after P2 of the last K tile, then run inside P3 / P4 of that K tile, in the shadow of its last thirty-two MFMAs)
     const int em0 = m0 + wr * 128, en0 = n0 + wc * 64;
     const int tile_m0 = m0;                        // first row of the whole 256-row tile (wave-uniform)
     TileMap cm;
@@ -690,7 +710,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
     int lean_lb = 0;
     const char* lean_cb = nullptr;
     [[maybe_unused]] __amdgpu_buffer_rsrc_t lean_rsrc;   // ROLL: base = lean_cb, bytes up to the end of C's last valid row
-    float bcol[2] = {0.f, 0.f};
+    float bcol[4] = {0.f, 0.f, 0.f, 0.f};         // bias of the lane's column in each 16-column block
     auto epi_head = [&]() {
       cm = make_tile_map(ep.cmap, tile_m0);
       ldcb = (unsigned)ep.ldc * 2u;                // bytes per C row
@@ -724,29 +744,32 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       asm volatile("" : "+v"(ln));
       const unsigned stg0 = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg));
       pl_p2 = ln >> 3;
-      // staging words as in PP_EPI2B: lane (col, hi) writes row pairs 2 hi + {0, 1, 4, 5} at word 132 hi + {0, 64, 264, 328} + 32 ni + col
-      pl_wa0 = stg0 + (unsigned)(((ln >> 5) * 132 + (ln & 31)) * 4);
-      pl_wa1 = pl_wa0 + 264 * 4;
-      pl_rd = stg0 + (unsigned)((pl_p2 * 64 + 4 * ((pl_p2 >> 1) & 1) + 8 * (pl_p2 >> 2) + (ln & 7) * 8) * 4);
+      // staging words as in PP_EPI2B: lane (g = l / 16, c = l % 16) writes row pairs 2 g + {0, 1} at word 192 g + {0, 68} + ((16 n + c) ^ 16 (g & 1)):
+      // one base for the even column blocks n, one for the odd ones (the XOR adds 16 to the first and takes 16 from the second)
+      pl_wa0 = stg0 + (unsigned)(((ln >> 4) * 192 + (ln & 15) + 16 * ((ln >> 4) & 1)) * 4);
+      pl_wa1 = stg0 + (unsigned)(((ln >> 4) * 192 + (ln & 15) - 16 * ((ln >> 4) & 1)) * 4);
+      pl_rd = stg0 + (unsigned)(((pl_p2 >> 1) * 192 + (pl_p2 & 1) * 68 + ((ln & 7) ^ (2 * ((pl_p2 >> 1) & 1))) * 8) * 4);
       pl_v0 = (unsigned)(2 * pl_p2) * ldcb + (unsigned)(ln & 7) * 16u;
     };
 #define PP_LWAIT(n_, ...) asm volatile("s_waitcnt lgkmcnt(%[cnt])" : __VA_ARGS__ : [cnt] "n"(n_) : "memory"); __builtin_amdgcn_sched_barrier(0)
 #define PP_PWAIT(n_) PP_LWAIT(n_, "+v"(pl_w0), "+v"(pl_w1))
 // (the bias add of a register pair is ONE v_pk_add_f32 -- same IEEE add per element --, and a launch without a bias skips it:
 // acc + 0.0f is acc bit for bit, an accumulator that started from +0 never holds -0)
-#define PP_PW(mi_, half_) if (ep.bias) { PP_PW_(mi_, half_, true) } else { PP_PW_(mi_, half_, false) }
-#define PP_PW_(mi_, half_, B_)                                                                          \
+#define PP_PW(mi_, half_) if (ep.bias) { PP_PW_(2 * (mi_) + (half_), true) } else { PP_PW_(2 * (mi_) + (half_), false) }
+#define PP_PW_(p_, B_)                                                                                  \
     {                                                                                                   \
-      _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) { \
-        f32x2 lo = mk2(acc[mi_][ni][8 * (half_) + 4 * kk], acc[mi_][ni][8 * (half_) + 4 * kk + 1]);     \
-        f32x2 hi = mk2(acc[mi_][ni][8 * (half_) + 4 * kk + 2], acc[mi_][ni][8 * (half_) + 4 * kk + 3]); \
+      _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) {                                                \
+        f32x2 lo = mk2(acc[p_][ni][0], acc[p_][ni][1]);                                                 \
+        f32x2 hi = mk2(acc[p_][ni][2], acc[p_][ni][3]);                                                 \
         if (B_) { const f32x2 b2 = mk2(bcol[ni], bcol[ni]); lo = lo + b2; hi = hi + b2; }               \
-        union { bf16x2 v; unsigned u; } x;     /* row pairs 2 hi + 4 kk (registers 4 kk, 4 kk + 1) and + 1 (4 kk + 2, + 3) */ \
+        union { bf16x2 v; unsigned u; } x;     /* row pairs 2 g (registers 0, 1) and 2 g + 1 (registers 2, 3) */ \
         union { bf16x2 v; unsigned u; } y;     /* (no comma outside parentheses in here: the stages are macro ARGUMENTS of the K tile) */ \
         x.v[0] = (__bf16)lo[0]; x.v[1] = (__bf16)lo[1];                                                 \
         y.v[0] = (__bf16)hi[0]; y.v[1] = (__bf16)hi[1];                                                 \
-        if (ni == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset1:64" :: "v"(kk ? pl_wa1 : pl_wa0), "v"(x.u), "v"(y.u) : "memory"); \
-        else asm volatile("ds_write2_b32 %0, %1, %2 offset0:32 offset1:96" :: "v"(kk ? pl_wa1 : pl_wa0), "v"(x.u), "v"(y.u) : "memory"); \
+        if (ni == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset1:68" :: "v"(pl_wa0), "v"(x.u), "v"(y.u) : "memory"); \
+        if (ni == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:16 offset1:84" :: "v"(pl_wa1), "v"(x.u), "v"(y.u) : "memory"); \
+        if (ni == 2) asm volatile("ds_write2_b32 %0, %1, %2 offset0:32 offset1:100" :: "v"(pl_wa0), "v"(x.u), "v"(y.u) : "memory"); \
+        if (ni == 3) asm volatile("ds_write2_b32 %0, %1, %2 offset0:48 offset1:116" :: "v"(pl_wa1), "v"(x.u), "v"(y.u) : "memory"); \
       }                                                                                                 \
     }
 #define PP_PR() asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16" : "=&v"(pl_w0), "=&v"(pl_w1) : "v"(pl_rd) : "memory")
@@ -852,7 +875,7 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         // 0's staging slice -- written in K tile 1, read in K tile 2 -- is dead).  Rows 0 .. 63 of the wave's block are final after P2:
         //   P3 load section   W(0) R(0)                  (behind the A1 fragment reads; the section's own lgkmcnt(0) covers R(0))
         //   P3 MFMA section   F(0) W(1) R(1)             (behind the section's request: its two stores are YOUNGER than that request;
-        //                                                 straight-line code in the scheduling region of the last six MFMAs)
+        //                                                 straight-line code in the scheduling region of the last twelve MFMAs)
         //   P4 load section   wait F(1) W(2) R(2)        (behind the section's counted wait, which gains the two stores of F(0) --
         //                                                 when they were issued: a full block; a ragged one keeps the plain count)
         //   P4 MFMA section   wait F(2) W(3) R(3)
@@ -861,8 +884,8 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           epi_head();
           rolled = true;
           const bool full = em0 + 127 < ep.M && en0 + 63 < ep.N && trace == nullptr;
-          if (ep.bias) asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:128\n\ts_waitcnt lgkmcnt(0)"
-                                    : "=&v"(bcol[0]), "=&v"(bcol[1]) : "v"(bias_rd) : "memory");
+          if (ep.bias) asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:64\n\tds_read_b32 %2, %4 offset:128\n\tds_read_b32 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
+                                    : "=&v"(bcol[0]), "=&v"(bcol[1]), "=&v"(bcol[2]), "=&v"(bcol[3]) : "v"(bias_rd) : "memory");
           pl_setup();
           PP_KTILE_XH(true, true, true, true, true, PP_ISS_ALWAYS, , , PP_PW(0, 0) PP_PR();,
                       PP_PWAIT(0); PP_PF(1) PP_PW(1, 0) PP_PR();,
@@ -897,9 +920,9 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // (= the whole accumulator goes through scratch)
 #define PP_EPI(mi_, half_)                                                                              \
       {                                                                                                 \
-        const int col = lane & 31, rhalf = (lane >> 5) * 4;                                             \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int r = 0; r < 8; ++r)  \
-            stg[((r & 3) + 8 * (r >> 2) + rhalf) * PP_STG_LD + ni * 32 + col] = acc[mi_][ni][8 * (half_) + r]; \
+        const int col = lane & 15, r0 = (lane >> 4) * 4;                                                \
+        _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) _Pragma("unroll") for (int r = 0; r < 4; ++r)  \
+            stg[(r0 + r) * PP_STG_LD + ni * 16 + col] = acc[2 * (mi_) + (half_)][ni][r];                \
         lgkm0();                                                                                        \
         __builtin_amdgcn_wave_barrier();                                                                \
         epilogue<bf16raw, 16, 2, PP_STG_LD>(ep, stg, em0 + (mi_) * 32 + (half_) * 16, en0, lane);       \
@@ -1000,16 +1023,16 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           dma16(pre_base + rr * pre_ld + enc, pre_lds + j * 512);
         }
       }
-      // bias in the ACCUMULATOR layout (a le owns one column of each 32-column half: 2 registers instead of the 8 a
+      // bias in the ACCUMULATOR layout (a le owns one column of each 16-column block: 4 registers instead of the 8 a
       // row-vector le needs, and 64 adds per tile instead of 128); same fp32 add, same result
       if (ep.bias && !rolled) {
         if constexpr (CONT) {                        // landed in the staging slice during K tile 0 (see above)
-          asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:128\n\ts_waitcnt lgkmcnt(0)"
-                       : "=&v"(bcol[0]), "=&v"(bcol[1]) : "v"(bias_rd) : "memory");
+          asm volatile("ds_read_b32 %0, %4\n\tds_read_b32 %1, %4 offset:64\n\tds_read_b32 %2, %4 offset:128\n\tds_read_b32 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
+                       : "=&v"(bcol[0]), "=&v"(bcol[1]), "=&v"(bcol[2]), "=&v"(bcol[3]) : "v"(bias_rd) : "memory");
         } else {
 #pragma unroll
-          for (int ni = 0; ni < 2; ++ni) {
-            const int c = en0 + ni * 32 + (le & 31);
+          for (int ni = 0; ni < 4; ++ni) {
+            const int c = en0 + ni * 16 + (le & 15);
             bcol[ni] = ep.bias[c < ep.N ? c : 0];
           }
         }
@@ -1063,6 +1086,8 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         stamp(4);
         asm volatile("" : "+v"(bcol[0]));
         asm volatile("" : "+v"(bcol[1]));
+        asm volatile("" : "+v"(bcol[2]));
+        asm volatile("" : "+v"(bcol[3]));
         if constexpr (HAS_SC) {
 #pragma unroll
           for (int p = 0; p < 8; ++p) { asm volatile("" : "+v"(sc[p][0])); asm volatile("" : "+v"(sc[p][1])); }
@@ -1076,8 +1101,10 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // The staged rows (and the residual rows) are read back with inline-asm ds_read + lgkmcnt(0) in ONE statement:
       // hipcc orders any ds_read IT emits behind every LDS-DMA in flight (`s_waitcnt vmcnt(0)`), i.e. pass 0 would
       // wait for the 14 prologue requests issued just above.
+      // fp32 staging image: row r, column c at word 64 r + (c ^ 16 ((r >> 2) & 1)).  A lane of the accumulator layout holds rows
+      // 4 g .. 4 g + 3 of column 16 n + l % 16: the XOR puts the two 16-lane groups of a 32-lane half on complementary banks
       const unsigned stg_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) +
-                                                                    ((le >> 3) * PP_STG_LD + (le & 7) * 8) * 4);
+                                                                    ((le >> 3) * PP_STG_LD + ((le & 7) ^ (((le >> 5) & 1) * 2)) * 8) * 4);
       const unsigned pre_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(pre_lds) + le * 16);
       const int kpar = nk & 1;                       // CONT: the ring buffer of a tile's K tile 0 alternates when the K tiles are odd in number
 #define PP_EPI2(p_, mi_, half_)                                                                         \
@@ -1088,11 +1115,11 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         if constexpr (PREG) asm volatile("" : "+v"(lp));                                                \
         const int enp = PREG ? en0 + (lp & 7) * 8 : en, erp = PREG ? em0 + (lp >> 3) : er;              \
         const bool cokp = PREG ? enp < ep.N : col_ok;                                                   \
-        const int col = lp & 31, rhalf = (lp >> 5) * 4;                                                 \
+        const int col = lp & 15, r0 = (lp >> 4) * 4, sw = ((lp >> 4) & 1) * 16;                         \
         if (dbg != 3) {                                                                                 \
-        _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int r = 0; r < 8; ++r)  \
-            stg[((r & 3) + 8 * (r >> 2) + rhalf) * PP_STG_LD + ni * 32 + col] = acc[mi_][ni][8 * (half_) + r] + bcol[ni]; \
-        } else { stg[lp] = acc[mi_][0][8 * (half_)] + acc[mi_][1][8 * (half_) + 7]; }                 \
+        _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) _Pragma("unroll") for (int r = 0; r < 4; ++r)  \
+            stg[(r0 + r) * PP_STG_LD + ((ni * 16 + col) ^ sw)] = acc[p_][ni][r] + bcol[ni];             \
+        } else { stg[lp] = acc[p_][0][0] + acc[p_][3][3]; }                                             \
         lgkm0();                                                                                        \
         __builtin_amdgcn_wave_barrier();                                                                \
         f32x4 s00, s01, s10, s11;                                                                       \
@@ -1170,8 +1197,11 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
       // per le and pass instead of 16 and 4 (the fp32 staging moved 512 KB through the LDS per tile, ~2.3 us of the
       // 4.7 us the eight passes of a plain tile take, most of it on the 64-B-per-clock ds_write_b32 path).  A le then
       // holds rows 2p, 2p+1 (p = le / 8) of 8 columns as 8 words {row 2p | row 2p+1}: eight v_perm_b32 separate them.
-      // Row-pair r sits at word r * 64 + 4 * ((r >> 1) & 1) + 8 * (r >> 2): the 4-word shift keeps the 16-le groups of the
-      // ds_read_b128 on 64 distinct banks, the 8-word one keeps row-pair 3's shifted tail off row-pair 4.  Same value, same rounding (one fp32 add, one round-to-nearest-even) as the fp32 staging.
+      // Row-pair r, column c sits at word 192 (r >> 1) + 68 (r & 1) + (c ^ 16 ((r >> 1) & 1)): a lane of the accumulator layout
+      // (g = le / 16) holds row pairs 2 g and 2 g + 1 of column 16 n + le % 16, and the XOR puts the two 16-lane groups of a
+      // 32-lane half of its ds_write on complementary banks; the 4-word shift of the odd pairs keeps the 16-le groups of the
+      // ds_read_b128 on 64 distinct banks (both checked with SQ_LDS_BANK_CONFLICT, profiles/mfma_shape_bench.txt).  Same value,
+      // same rounding (one fp32 add, one round-to-nearest-even) as the fp32 staging.
       constexpr bool PAIRS = VTX_PP_BF16_STAGE && PRE == PRE_NONE && !HAS_SC && !HAS_ACT;
       // Lean passes (round 4).  Wave-uniform test per tile: the wave's whole 128 x 64 block lies inside M x N, none of its rows
       // is a split row, the C row map is in tile form (at most one group boundary inside the tile) and its skip fits 30 bits
@@ -1207,8 +1237,10 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           PP_PW(3, 1) PP_PWAIT(4); PP_PF(6) PP_PR();
           PP_PWAIT(0); PP_PF(7)
         } else {
-          // fp32 staging as in PP_EPI2: le (col, hi) writes rows 4 hi + {0, 1, 2, 3, 8, 9, 10, 11} at word 256 hi + {0, 64, 128, 192, 512, ...} + 32 ni + col
-          const unsigned wa0 = stg_wr0 + (unsigned)(((ln >> 5) * 256 + (ln & 31)) * 4), wa1 = wa0 + 512 * 4;
+          // fp32 staging as in PP_EPI2: lane (g, c) writes rows 4 g + {0, 1, 2, 3} at word 256 g + {0, 64, 128, 192} + ((16 n + c) ^ 16 (g & 1)):
+          // base wa0 for the even column blocks n, wa1 for the odd ones
+          const unsigned wa0 = stg_wr0 + (unsigned)(((ln >> 4) * 256 + (ln & 15) + 16 * ((ln >> 4) & 1)) * 4);
+          const unsigned wa1 = stg_wr0 + (unsigned)(((ln >> 4) * 256 + (ln & 15) - 16 * ((ln >> 4) & 1)) * 4);
           const unsigned vf0 = (unsigned)(ln >> 3) * ldcb + (unsigned)(ln & 7) * 16u;
           const unsigned ldc2b = (unsigned)ep.ldc2 * 2u;               // second output (GELU'): identity row map
           const unsigned vg0 = (unsigned)(ln >> 3) * ldc2b + (unsigned)(ln & 7) * 16u;
@@ -1218,20 +1250,23 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
           float scu[2] = {1.f, 1.f};                   // the pass's two row scales (rows le / 8 and + 8 of its 16)
           const unsigned bp_addr = (unsigned)(ln >> 3) * 4u;
           PP_BLOAD();
-#define PP_LW(mi_, half_) if (ep.bias) { PP_LW_(mi_, half_, true) } else { PP_LW_(mi_, half_, false) }
-#define PP_LW_(mi_, half_, B_)                                                                          \
+#define PP_LW(mi_, half_) if (ep.bias) { PP_LW_(2 * (mi_) + (half_), true) } else { PP_LW_(2 * (mi_) + (half_), false) }
+#define PP_LW_(p_, B_)                                                                                  \
           {                                                                                             \
-            _Pragma("unroll") for (int kk = 0; kk < 2; ++kk) _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) \
-            _Pragma("unroll") for (int r2 = 0; r2 < 2; ++r2) {                                          \
-              f32x2 xy = mk2(acc[mi_][ni][8 * (half_) + 4 * kk + 2 * r2], acc[mi_][ni][8 * (half_) + 4 * kk + 2 * r2 + 1]); \
+            _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) _Pragma("unroll") for (int r2 = 0; r2 < 2; ++r2) { \
+              f32x2 xy = mk2(acc[p_][ni][2 * r2], acc[p_][ni][2 * r2 + 1]);                             \
               if (B_) { const f32x2 b2 = mk2(bcol[ni], bcol[ni]); xy = xy + b2; }                       \
               const float x = xy[0];                                                                    \
               const float y = xy[1];                                                                    \
-              const unsigned wa = kk ? wa1 : wa0;                                                       \
+              const unsigned wa = (ni & 1) ? wa1 : wa0;                                                 \
               if (ni == 0 && r2 == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset1:64" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
               if (ni == 0 && r2 == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:128 offset1:192" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
-              if (ni == 1 && r2 == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset0:32 offset1:96" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
-              if (ni == 1 && r2 == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:160 offset1:224" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 1 && r2 == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset0:16 offset1:80" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 1 && r2 == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:144 offset1:208" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 2 && r2 == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset0:32 offset1:96" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 2 && r2 == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:160 offset1:224" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 3 && r2 == 0) asm volatile("ds_write2_b32 %0, %1, %2 offset0:48 offset1:112" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
+              if (ni == 3 && r2 == 1) asm volatile("ds_write2_b32 %0, %1, %2 offset0:176 offset1:240" :: "v"(wa), "v"(x), "v"(y) : "memory"); \
             }                                                                                           \
           }
 #define PP_LR(p_)                                                                                       \
@@ -1307,18 +1342,17 @@ __global__ __launch_bounds__(PP_THREADS, 2) void gemm_nt_bf16_pp_kernel(
         unsigned* const stgw = reinterpret_cast<unsigned*>(stg);
         const int p2 = le >> 3;
         const unsigned pair_rd = (unsigned)(unsigned long)(lds_char*)(reinterpret_cast<char*>(stg) +
-                                                                       (p2 * 64 + 4 * ((p2 >> 1) & 1) + 8 * (p2 >> 2) + (le & 7) * 8) * 4);
+                                                                       ((p2 >> 1) * 192 + (p2 & 1) * 68 + ((le & 7) ^ (2 * ((p2 >> 1) & 1))) * 8) * 4);
         typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
 #define PP_EPI2B(p_, mi_, half_)                                                                        \
         {                                                                                               \
-          const int col = le & 31, hi = le >> 5;                                                    \
-          _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) _Pragma("unroll") for (int k = 0; k < 4; ++k) { \
-            /* registers 2k, 2k+1 of this half: rows {0,2,8,10}[k] + 4 hi (+1) of the pass's 16 */     \
-            const int rp = ((2 * k) & 3) / 2 + 4 * ((2 * k) >> 2) + 2 * hi;                             \
+          const int col = le & 15, g = le >> 4;                                                         \
+          _Pragma("unroll") for (int ni = 0; ni < 4; ++ni) _Pragma("unroll") for (int k = 0; k < 2; ++k) { \
+            /* registers 2k, 2k+1: rows 4 g + 2 k (+1) of the pass's 16 = row pair 2 g + k */           \
             union { bf16x2 v; unsigned u; } w;                                                          \
-            w.v[0] = (__bf16)(acc[mi_][ni][8 * (half_) + 2 * k] + bcol[ni]);                            \
-            w.v[1] = (__bf16)(acc[mi_][ni][8 * (half_) + 2 * k + 1] + bcol[ni]);                        \
-            stgw[rp * 64 + 4 * ((rp >> 1) & 1) + 8 * (rp >> 2) + ni * 32 + col] = w.u;                  \
+            w.v[0] = (__bf16)(acc[p_][ni][2 * k] + bcol[ni]);                                           \
+            w.v[1] = (__bf16)(acc[p_][ni][2 * k + 1] + bcol[ni]);                                       \
+            stgw[g * 192 + k * 68 + ((ni * 16 + col) ^ (16 * (g & 1)))] = w.u;                          \
           }                                                                                             \
           lgkm0();                                                                                      \
           __builtin_amdgcn_wave_barrier();                                                              \
