@@ -76,13 +76,33 @@ def _geometry(layout, dims):
     return S, L, B, T, P, B * (1 + P * T), B * P * T + (S if grp else 0), rin, rout, grp
 
 
+def _ramp_qkv(S, L, H, hd, seed):
+    """contig qkv [S L, 3D] whose scaled scores rise by about 8 along the keys: with u = ones(hd) / sqrt(hd), q_i = u + noise / 4
+    and k_j = (j / L) (8 / scale) u + noise / 4, so the running maximum of the online softmax moves at every 8-key chunk and
+    across every 64-key tile; v is random."""
+    D = H * hd
+    noise = rnd(S * L, 3 * D, seed=seed)
+    u = hd ** -0.5
+    j = (torch.arange(S * L) % L).float()[:, None] / L
+    qkv = noise.clone()
+    qkv[:, :D] = u + 0.25 * noise[:, :D]
+    qkv[:, D:2 * D] = j * (8.0 * hd ** 0.5) * u + 0.25 * noise[:, D:2 * D]
+    return qkv
+
+
 @functools.lru_cache(maxsize=None)
-def _reference(layout, dims, H, hd, dtype):
+def _reference(layout, dims, H, hd, dtype, operands='random'):
     """Inputs (float32 CPU) and the float64 results on the operands as `dtype` holds them: out [out rows, D], lse [S, H, L],
-    dqkv [qkv rows, 3D] (the shared cls rows summed over their sequences), the per-sequence cls rows [S, 3D]."""
+    dqkv [qkv rows, 3D] (the shared cls rows summed over their sequences), the per-sequence cls rows [S, 3D].  operands: 'random'
+    (dense normal data) or 'ramp' (_ramp_qkv; contig only)."""
     S, L, B, T, P, rows, orows, rin, rout, grp = _geometry(layout, dims)
     D = H * hd
-    qkv = rnd(rows, 3 * D, seed=L + hd) * 1.5
+    if operands == 'ramp':
+        assert layout == 'contig'
+        qkv = _ramp_qkv(S, L, H, hd, L + hd)
+    else:
+        assert operands == 'random'
+        qkv = rnd(rows, 3 * D, seed=L + hd) * 1.5
     do = rnd(orows, D, seed=L + hd + 1)
     base = q(qkv, dtype).requires_grad_(True)
     seqs = base[torch.from_numpy(rin)]                                  # [S, L, 3D]
@@ -137,14 +157,14 @@ def _untouched(tag, **regions):
         assert X.sentinel_touched(t) == 0, f'{tag}: {name} overwritten'
 
 
-def _against_f64(layout, dims, H, hd, dtype):
+def _against_f64(layout, dims, H, hd, dtype, operands='random'):
     from vtx import _lib as L_
     from vtx import ops
     S, L, B, T, P, rows, orows, rin, rout, grp = _geometry(layout, dims)
     D, W, n = H * hd, 3 * H * hd, S * H * L
-    qkv, do, r_out, r_lse, r_dqkv, r_cls = _reference(layout, dims, H, hd, dtype)
+    qkv, do, r_out, r_lse, r_dqkv, r_cls = _reference(layout, dims, H, hd, dtype, operands)
     out, lse, dqkv, dcls = _launch(layout, dims, H, hd, dtype, qkv, do)
-    tag = f'attn hd={hd} {layout} {dims} {IDS[dtype]}'
+    tag = f'attn hd={hd} {layout} {dims} {IDS[dtype]}' + ('' if operands == 'random' else f' {operands}')
     _untouched(tag, ld_out_pad=out[:, D:], rows_after_out=out[orows:], lse_tail=lse[n:], ld_dqkv_pad=dqkv[:, W:], rows_after_dqkv=dqkv[rows:])
     check(f'{tag} out', out[:orows, :D].float().cpu(), r_out, TOL[dtype])
     check(f'{tag} lse', lse[:n].cpu().reshape(S, H, L), r_lse, LSE_BAR)

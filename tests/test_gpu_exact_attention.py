@@ -139,7 +139,7 @@ def attn_desc(c, dtype, qkv, out, lse, probs=None):
 
 def _shape(c):
     btp = '' if c.layout == 'contig' else f' B={c.B} T={c.T} P={c.P}'
-    return f'{c.layout}{btp} S={c.S} L={c.L} H={c.H}'
+    return f'{c.layout}{btp} S={c.S} L={c.L} H={c.H}' + ('' if c.hd == 64 else f' hd={c.hd}')
 
 
 def run_fwd(c, dtype, probs=False):

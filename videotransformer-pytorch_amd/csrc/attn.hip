@@ -371,8 +371,9 @@ static size_t attn_lds(const AttnP& p, int hd, bool with_stats) {
 }
 
 // The VALU launches, once per element type and head dim.  PROBS = 1 recomputes the probabilities from the lse that a forward left.
-// At head_dim 128 the tiles pass 64 KB (one sequence: 2 (64 * 128 + 4) * 4 B = 65568; packed, G * L <= 128: up to 132.2 KB with
-// the lse / delta rows of the dk / dv pass), hence the opt-in; 160 KB is the CU's.
+// At head_dim 128 the tiles pass 64 KB (one sequence: 2 (64 * 128 + 4) * 4 B = 65568; packed, G * L <= 128: 132160 B at L = 64 and up
+// to 136192 B at L = 1, where the pad of 4 floats counts G = 128 times, with the lse / delta rows of the dk / dv pass), hence the
+// opt-in; 160 KB is the CU's.
 template <typename T, int HD, int PROBS>
 static int valu_fwd_launch_hd(const AttnP& p, const vtx_attn_desc* d, hipStream_t st) {
   const size_t lds = attn_lds(p, HD, false);
