@@ -1,6 +1,7 @@
 // attn_common.h -- launch parameters and row addressing shared by attn.hip (VALU), attn_mfma.hip and the chunk-streaming kernels
-// (attn_stream.h with its two tile policies, attn_long.hip and attn_f32.hip; attn_hd.hip and attn_hd_f32.hip at the other head
-// dims), and the swizzled-LDS / MFMA fragment helpers of the two bf16 MFMA families.
+// (attn_stream.h with its two tile policies, attn_tiles_bf16.h and attn_tiles_f32.h, instantiated by attn_long.hip, attn_f32.hip
+// and attn_hd_f32.hip; attn_hd.hip with the bf16 policy under bodies of its own), and the swizzled-LDS / MFMA fragment helpers of the two bf16 MFMA
+// families.
 #pragma once
 #include "common.h"
 

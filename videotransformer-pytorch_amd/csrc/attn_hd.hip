@@ -5,9 +5,13 @@
 // queries -- 128 keys in the dk / dv kernel --, the other operands stream through two LDS stages, one barrier per chunk, dk / dv
 // with one workgroup per key block walking all queries: fixed summation order, no atomics, no workspace), and the formulation is
 // that of attn_long.hip: v_mfma_f32_32x32x16_bf16, swizzled [rows][64] bf16 tiles, transposed operands through
-// ds_read_b64_tr_b16 (sw_off / frag_rows_o / frag_cols_o of attn_common.h, unchanged).  What differs is the head: attn_stream.h
-// and its two policies fix 64 columns (h * 64, two accumulator tiles, four k-steps) and are left exactly as they are, so that
-// the head_dim-64 kernels compile to the same objects; the three bodies are restated here over HD.
+// ds_read_b64_tr_b16 (sw_off / frag_rows_o / frag_cols_o of attn_common.h, unchanged).  The tile helpers (chunk load / store,
+// row fragments, scores, accum, dkv_tile, store_rows) are Bf16Tiles<HD, 64> of attn_tiles_bf16.h, the policy attn_long.hip
+// instantiates as <64, 128>; the three kernel bodies are still restated here over HD.  attn_stream.h's bodies over the same policy
+// compute the same bits with the same registers and scratch, but their forward at head_dim 128 measured 8.7 % slower at 8 x 1569
+// tokens (0.115 -> 0.125 ms; the other 27 rows held: profiles/attn_stream_hd_refactor_bench.txt, section 4), while with the bodies
+// kept here this file's device code is byte for byte the one before the helpers moved.  The bodies stay until the schedule of
+// that kernel's chunk loop is understood.
 //
 // A head is NS = ceil(HD / 64) column slabs of the [rows][64] tile, the last one half used at 32 and 96 (its upper 32 columns
 // are never written and never read):
@@ -27,7 +31,7 @@
 // Masking as in attn_stream.h: keys >= L have zero K / V rows and score -1e30 before the max; query rows >= L keep to their lane
 // and are never stored; in the dk / dv kernel padded query rows carry lse = +1e30.
 // FLOPs per (sequence, head): forward 4 L^2 HD, backward 10 L^2 HD (+ 4 L^2 HD recomputed scores).
-#include "attn_common.h"
+#include "attn_tiles_bf16.h"
 
 namespace vtx {
 namespace hdim {
@@ -35,22 +39,12 @@ namespace hdim {
 constexpr int THREADS = 256;
 constexpr int ROWS = 128;                          // queries (keys in the dk / dv kernel) of one workgroup: 4 waves x 32
 
-template <int HD> struct Geo {
-  static_assert(HD == 32 || HD == 96 || HD == 128, "head dims of this file");
-  static constexpr int NS = (HD + 63) / 64;        // column slabs of a row
-  static constexpr int NK = HD / 16;               // k-steps of a score tile
-  static constexpr int NT = HD / 32;               // accumulator tiles of a result row
-  static constexpr int CHUNK = 64;                 // rows of the streamed operands per LDS stage
-  static constexpr int KC = CHUNK / 32;
-  static constexpr int SLAB = CHUNK * 64;          // elements of one [CHUNK][64] slab
-  static constexpr int TILE = NS * SLAB;           // one operand of a chunk (8 KiB at one slab, 16 KiB at two)
-  static constexpr int STAGE = 2 * TILE;
-  static constexpr int PR = HD / 8;                // 16-byte pieces of a row
-  static constexpr int PER = CHUNK * PR / THREADS; // pieces of one operand per thread
-  static_assert(CHUNK * PR % THREADS == 0, "whole pieces per thread");
-  static constexpr size_t LDS_KV = (size_t)2 * STAGE * sizeof(bf16raw);
-  static constexpr size_t LDS_DKV = LDS_KV + (size_t)2 * 2 * CHUNK * sizeof(float);
-};
+template <int HD> using Geo = Bf16Tiles<HD, 64>;    // the tile policy (attn_tiles_bf16.h): 64-row chunks at every head dim of this file
+template <int HD> constexpr size_t LDS_KV = stream_lds_kv<Geo<HD>>();
+template <int HD> constexpr size_t LDS_DKV = stream_lds_dkv<Geo<HD>>();
+// dynamic LDS of a launch: forward and dq, dk / dv
+static_assert(LDS_KV<32> == 32768 && LDS_DKV<32> == 33792, "dynamic LDS of a launch");
+static_assert(LDS_KV<96> == 65536 && LDS_DKV<96> == 66560 && LDS_KV<128> == 65536 && LDS_DKV<128> == 66560, "dynamic LDS of a launch");
 
 struct Who {
   int lane, wave, h, D, s, row0, row;              // row0: first of the wave's 32 rows; row: this lane's
@@ -79,179 +73,22 @@ __device__ inline bf16raw* lds_base() {
   return reinterpret_cast<bf16raw*>(sm_raw);
 }
 
-// Rows row0 .. row0 + CHUNK - 1 of two operands of one sequence, in flight between two chunks.
-template <int HD> struct Pre { uint4 a[Geo<HD>::PER], b[Geo<HD>::PER]; };
-
-// Issue the loads of one chunk (rows >= L read as zero; a chunk wholly beyond L issues nothing).
-template <int HD>
-__device__ __forceinline__ void chunk_load(Pre<HD>& x, const bf16raw* b0, long ld0, const RowLin& r0, const bf16raw* b1, long ld1,
-                                           const RowLin& r1, int row0, int L) {
-  typedef Geo<HD> G;
-#pragma unroll
-  for (int i = 0; i < G::PER; ++i) {
-    const int id = threadIdx.x + i * THREADS;
-    const int rr = id / G::PR, c = id - rr * G::PR;
-    const int r = row0 + rr;
-    x.a[i] = make_uint4(0, 0, 0, 0);
-    x.b[i] = make_uint4(0, 0, 0, 0);
-    if (r < L) {
-      x.a[i] = *reinterpret_cast<const uint4*>(b0 + lin_row(r0, r) * ld0 + c * 8);
-      x.b[i] = *reinterpret_cast<const uint4*>(b1 + lin_row(r1, r) * ld1 + c * 8);
-    }
-  }
-}
-template <int HD>
-__device__ __forceinline__ void chunk_store(const Pre<HD>& x, bf16raw* t0, bf16raw* t1) {
-  typedef Geo<HD> G;
-#pragma unroll
-  for (int i = 0; i < G::PER; ++i) {
-    const int id = threadIdx.x + i * THREADS;
-    const int rr = id / G::PR, c = id - rr * G::PR;
-    const int off = (c >> 3) * G::SLAB + rr * 64 + (((c & 7) ^ sw_of(rr)) << 3);
-    *reinterpret_cast<uint4*>(t0 + off) = x.a[i];
-    *reinterpret_cast<uint4*>(t1 + off) = x.b[i];
-  }
-}
-
-// A row's HD columns (this lane's half of every 16) in registers; rows beyond nvalid read row nvalid - 1 (load_row_frags).
-template <int HD> struct Frag { bf16x8 f[Geo<HD>::NK]; };
-template <int HD>
-__device__ __forceinline__ void load_frag(Frag<HD>& f, const bf16raw* base, long ld, int col0, const RowLin& rl, int row, int nvalid,
-                                          int lane) {
-  const int rc = row < nvalid ? row : nvalid - 1;
-  const bf16raw* src = base + lin_row(rl, rc) * ld + col0 + 8 * (lane >> 5);
-#pragma unroll
-  for (int ks = 0; ks < Geo<HD>::NK; ++ks) {
-    union { bf16x8 v; uint4 u; } x;
-    x.u = *reinterpret_cast<const uint4*>(src + ks * 16);
-    f.f[ks] = x.v;
-  }
-}
-template <int HD>
-__device__ __forceinline__ float frag_dot(const Frag<HD>& a, const Frag<HD>& b) {
-  float s = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < Geo<HD>::NK; ++ks) s = frag_dot2(a.f[ks], b.f[ks], s);
-  return s;
-}
-
-// C[i][j] = sum_d tile[row0 + i][d] frag_j[d] for 32 tile rows
-template <int HD>
-__device__ __forceinline__ f32x16 scores(const bf16raw* t, int row0, const Frag<HD>& b, const FragOff& fo) {
-  typedef Geo<HD> G;
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(t, row0, 0, fo), b.f[0], zero, 0, 0, 0);
-#pragma unroll
-  for (int ks = 1; ks < G::NK; ++ks)
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(t + (ks >> 2) * G::SLAB, row0, ks & 3, fo), b.f[ks], st, 0, 0, 0);
-  return st;
-}
-// acc[n][d][j] += sum_i tile[row0 + i][32 n + d] c[i][j], c as scores() left it
-template <int HD>
-__device__ __forceinline__ void accum(f32x16 (&acc)[Geo<HD>::NT], const bf16raw* t, int row0, const f32x16& c, const FragOff& fo) {
-  typedef Geo<HD> G;
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    float pf[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pf[j] = c[8 * s2 + j];
-    const bf16x8 pb = pack8(pf);
-#pragma unroll
-    for (int n = 0; n < G::NT; ++n)
-      acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(t + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), pb, acc[n], 0, 0, 0);
-  }
-}
-// The dk / dv products of one 32-query tile: the S and dP chains interleaved, then dv and dk fed together (attn_long.hip).
-template <int HD>
-__device__ __forceinline__ void dkv_tile(f32x16 (&dk)[Geo<HD>::NT], f32x16 (&dv)[Geo<HD>::NT], const bf16raw* Qs, const bf16raw* Os,
-                                         const float* Ls, const float* Ds, int row0, const Frag<HD>& kf, const Frag<HD>& vf, float c2,
-                                         const FragOff& fo, int lane) {
-  typedef Geo<HD> G;
-  const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  f32x16 st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs, row0, 0, fo), kf.f[0], zero, 0, 0, 0);
-  f32x16 dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os, row0, 0, fo), vf.f[0], zero, 0, 0, 0);
-#pragma unroll
-  for (int ks = 1; ks < G::NK; ++ks) {
-    st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Qs + (ks >> 2) * G::SLAB, row0, ks & 3, fo), kf.f[ks], st, 0, 0, 0);
-    dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os + (ks >> 2) * G::SLAB, row0, ks & 3, fo), vf.f[ks], dp, 0, 0, 0);
-  }
-  float pr[16], ds[16];
-#pragma unroll
-  for (int g = 0; g < 4; ++g) {
-    const int qrow = row0 + 8 * g + 4 * (lane >> 5);
-    const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
-    const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
-    const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = 4 * g + j;
-      const float e = __builtin_amdgcn_exp2f(fmaf(st[r], c2, -lv[j]));
-      pr[r] = e;
-      ds[r] = e * (dp[r] - dvv[j]);                // the softmax scale is applied once to dk at the store
-    }
-  }
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    const bf16x8 pb = pack8(pr + 8 * s2);
-    const bf16x8 dsb = pack8(ds + 8 * s2);
-#pragma unroll
-    for (int n = 0; n < G::NT; ++n) {
-      dv[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Os + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), pb, dv[n], 0, 0, 0);
-      dk[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(Qs + (n >> 1) * G::SLAB, row0 + 16 * s2, n & 1, fo), dsb, dk[n], 0, 0, 0);
-    }
-  }
-}
-
-// Store a [32 x HD] result held transposed (lane & 31 = row, registers = HD columns in NT C tiles): slab by slab through the
-// wave's swizzled [32][64] staging tile, whole 16-byte pieces of a row per lane (store_rows_T of attn_common.h, for NT tiles).
-// ptr_of_row(r) -> destination of tile row r (HD bf16), or nullptr for a padded row.
-template <int HD, typename PtrFn>
-__device__ __forceinline__ void store_rows(bf16raw* stg, const f32x16 (&acc)[Geo<HD>::NT], float mul, int lane, PtrFn ptr_of_row) {
-  typedef Geo<HD> G;
-  const int row = lane & 31;
-#pragma unroll
-  for (int s = 0; s < G::NS; ++s) {
-    const int ntile = G::NT - 2 * s < 2 ? G::NT - 2 * s : 2;     // C tiles of this slab
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-      if (nt < ntile) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int col = nt * 32 + 8 * g + 4 * (lane >> 5);
-          union { bf16x4 v; uint2 u; } w;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) w.v[j] = (__bf16)(acc[2 * s + nt][4 * g + j] * mul);
-          *reinterpret_cast<uint2*>(stg + sw_off(row, col)) = w.u;
-        }
-      }
-    wave_lds_sync();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int r = i * 8 + (lane >> 3), c = lane & 7;
-      const uint4 v = *reinterpret_cast<const uint4*>(stg + r * 64 + ((c ^ sw_of(r)) << 3));
-      bf16raw* dst = ptr_of_row(r);
-      if (dst && c < ntile * 4) *reinterpret_cast<uint4*>(dst + s * 64 + c * 8) = v;
-    }
-    wave_lds_sync();
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ forward
 template <int HD>
 __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void fwd_kernel(AttnP p, const bf16raw* __restrict__ qkv, bf16raw* __restrict__ out,
                                                          float* __restrict__ lse) {
   typedef Geo<HD> G;
-  constexpr int CHUNK = G::CHUNK, KC = G::KC;
+  constexpr int CHUNK = G::CHUNK, KC = CHUNK / 32;
   bf16raw* sm = lds_base();
   const Who w = who<HD>(p);
   const int lane = w.lane, h = w.h;
   const bf16raw* kb = qkv + w.D + h * HD;
   const bf16raw* vb = qkv + 2 * w.D + h * HD;
-  Frag<HD> qf;
-  load_frag<HD>(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
-  Pre<HD> pre;
-  chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
-  chunk_store<HD>(pre, sm, sm + G::TILE);
+  typename G::Frag qf;
+  G::load_frag(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
+  typename G::Pre pre;
+  G::chunk_load(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
+  G::chunk_store(pre, sm, sm + G::TILE);
   __syncthreads();
   const FragOff ln = make_frag_off(lane);
   const float c2 = p.scale * LOG2E;
@@ -263,14 +100,14 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void fwd_kernel(AttnP p,
   for (int c = 0; c < nch; ++c) {
     const bf16raw* Ks = sm + (c & 1) * G::STAGE;
     const bf16raw* Vs = Ks + G::TILE;
-    chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
+    G::chunk_load(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
     if (w.active) {
       const int nrows = min(CHUNK, p.L - c * CHUNK);
       const int nt = (nrows + 31) >> 5;
       f32x16 st[KC];                               // (tiles beyond nt stay undefined: every use below is guarded)
 #pragma unroll
       for (int t = 0; t < KC; ++t)
-        if (t < nt) st[t] = scores<HD>(Ks, t * 32, qf, ln);
+        if (t < nt) st[t] = G::scores(Ks, t * 32, qf, ln);
       float bm = -1e30f;
 #pragma unroll
       for (int t = 0; t < KC; ++t)
@@ -305,17 +142,17 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void fwd_kernel(AttnP p,
       }
 #pragma unroll
       for (int t = 0; t < KC; ++t)
-        if (t < nt) accum<HD>(acc, Vs, t * 32, st[t], ln);
+        if (t < nt) G::accum(acc, Vs, t * 32, st[t], ln);
     }
     if (c + 1 < nch) {
       bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE; // last read in iteration c - 1, behind that iteration's barrier
-      chunk_store<HD>(pre, nx, nx + G::TILE);
+      G::chunk_store(pre, nx, nx + G::TILE);
     }
     __syncthreads();
   }
   if (!w.active) return;
   bf16raw* stg = sm + w.wave * MA_STAGE_ELEMS;     // every wave is past the last chunk: the stages are free
-  store_rows<HD>(stg, acc, 1.0f / l, lane, [&](int r) -> bf16raw* {
+  G::store_rows(stg, acc, 1.0f / l, lane, [&](int r) -> bf16raw* {
     const int qq = w.row0 + r;
     return qq < p.L ? out + lin_row(w.lo, qq) * p.ld_out + h * HD : nullptr;
   });
@@ -329,20 +166,20 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void bwd_dq_kernel(AttnP
                                                             float* __restrict__ delta, bf16raw* __restrict__ dqkv,
                                                             bf16raw* __restrict__ dqkv_cls) {
   typedef Geo<HD> G;
-  constexpr int CHUNK = G::CHUNK, KC = G::KC;
+  constexpr int CHUNK = G::CHUNK, KC = CHUNK / 32;
   bf16raw* sm = lds_base();
   const Who w = who<HD>(p);
   const int lane = w.lane, h = w.h;
   const bf16raw* kb = qkv + w.D + h * HD;
   const bf16raw* vb = qkv + 2 * w.D + h * HD;
-  Frag<HD> qf, df;
+  typename G::Frag qf, df;
   float dl;                                        // delta = rowsum(dO * O): this lane's half of the row's columns
   {
-    Frag<HD> of;
-    load_frag<HD>(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
-    load_frag<HD>(df, dout, p.ld_dout, h * HD, w.lo, w.row, p.L, lane);
-    load_frag<HD>(of, o, p.ld_out, h * HD, w.lo, w.row, p.L, lane);
-    dl = frag_dot<HD>(df, of);
+    typename G::Frag of;
+    G::load_frag(qf, qkv, p.ld_qkv, h * HD, w.li, w.row, p.L, lane);
+    G::load_frag(df, dout, p.ld_dout, h * HD, w.lo, w.row, p.L, lane);
+    G::load_frag(of, o, p.ld_out, h * HD, w.lo, w.row, p.L, lane);
+    dl = G::frag_dot(df, of);
   }
   dl += __shfl_xor(dl, 32, 64);
   float l2 = 0.f;
@@ -351,9 +188,9 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void bwd_dq_kernel(AttnP
     l2 = lse[lidx] * LOG2E;
     if (lane < 32) delta[lidx] = dl;
   }
-  Pre<HD> pre;
-  chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
-  chunk_store<HD>(pre, sm, sm + G::TILE);
+  typename G::Pre pre;
+  G::chunk_load(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, 0, p.L);
+  G::chunk_store(pre, sm, sm + G::TILE);
   __syncthreads();
   const FragOff ln = make_frag_off(lane);
   const float c2 = p.scale * LOG2E;
@@ -364,15 +201,15 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void bwd_dq_kernel(AttnP
   for (int c = 0; c < nch; ++c) {
     const bf16raw* Ks = sm + (c & 1) * G::STAGE;
     const bf16raw* Vs = Ks + G::TILE;
-    chunk_load<HD>(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
+    G::chunk_load(pre, kb, p.ld_qkv, w.li, vb, p.ld_qkv, w.li, (c + 1) * CHUNK, p.L);
     if (w.active) {
       const int nrows = min(CHUNK, p.L - c * CHUNK);
       const int nt = (nrows + 31) >> 5;
 #pragma unroll
       for (int t = 0; t < KC; ++t)
         if (t < nt) {
-          const f32x16 st = scores<HD>(Ks, t * 32, qf, ln);
-          f32x16 ds = scores<HD>(Vs, t * 32, df, ln);
+          const f32x16 st = G::scores(Ks, t * 32, qf, ln);
+          f32x16 ds = G::scores(Vs, t * 32, df, ln);
           // dS = P (dP - delta); the softmax scale is applied once to dq at the store.  A padded key has zero K and V rows:
           // its dS is finite and multiplies zeros; it is zeroed all the same, which keeps the pack clean.
 #pragma unroll
@@ -382,18 +219,18 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : 2) void bwd_dq_kernel(AttnP
             for (int r = 0; r < 16; ++r)
               if (t * 32 + crow(r, lane) >= nrows) ds[r] = 0.f;
           }
-          accum<HD>(acc, Ks, t * 32, ds, ln);
+          G::accum(acc, Ks, t * 32, ds, ln);
         }
     }
     if (c + 1 < nch) {
       bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE;
-      chunk_store<HD>(pre, nx, nx + G::TILE);
+      G::chunk_store(pre, nx, nx + G::TILE);
     }
     __syncthreads();
   }
   if (!w.active) return;
   bf16raw* stg = sm + w.wave * MA_STAGE_ELEMS;
-  store_rows<HD>(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
+  G::store_rows(stg, acc, p.scale, lane, [&](int r) -> bf16raw* {
     const int qq = w.row0 + r;
     if (qq >= p.L) return nullptr;
     return attn_cls_row(p, qq) ? dqkv_cls + (long)w.s * p.ld_dqkv + h * HD : dqkv + lin_row(w.li, qq) * p.ld_dqkv + h * HD;
@@ -408,7 +245,7 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
                                                                             const float* __restrict__ lse, const float* __restrict__ delta,
                                                                             bf16raw* __restrict__ dqkv, bf16raw* __restrict__ dqkv_cls) {
   typedef Geo<HD> G;
-  constexpr int CHUNK = G::CHUNK, QC = G::KC;
+  constexpr int CHUNK = G::CHUNK, QC = CHUNK / 32;
   bf16raw* sm = lds_base();
   float* stats = reinterpret_cast<float*>(sm + 2 * G::STAGE);    // [stage][lse * log2(e) | delta][CHUNK]
   const Who w = who<HD>(p);
@@ -417,9 +254,9 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
   const bf16raw* ob = dout + h * HD;
   const float* lb = lse + ((long)w.s * p.H + h) * p.L;
   const float* db = delta + ((long)w.s * p.H + h) * p.L;
-  Frag<HD> kf, vf;
-  load_frag<HD>(kf, qkv, p.ld_qkv, D + h * HD, w.li, w.row, p.L, lane);
-  load_frag<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, w.li, w.row, p.L, lane);
+  typename G::Frag kf, vf;
+  G::load_frag(kf, qkv, p.ld_qkv, D + h * HD, w.li, w.row, p.L, lane);
+  G::load_frag(vf, qkv, p.ld_qkv, 2 * D + h * HD, w.li, w.row, p.L, lane);
   // thread t < CHUNK: lse of chunk row t (scaled; +huge on padded rows -> P = 0); CHUNK <= t < 2 CHUNK: delta of chunk row t - CHUNK
   const int srow = threadIdx.x & (CHUNK - 1);
   const bool is_lse = threadIdx.x < CHUNK, has_stat = threadIdx.x < 2 * CHUNK;
@@ -428,10 +265,10 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
     if (!has_stat || r >= p.L) return is_lse ? 1e30f : 0.f;
     return is_lse ? lb[r] * LOG2E : db[r];
   };
-  Pre<HD> pre;
-  chunk_load<HD>(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, 0, p.L);
+  typename G::Pre pre;
+  G::chunk_load(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, 0, p.L);
   float sv = stat_load(0);
-  chunk_store<HD>(pre, sm, sm + G::TILE);
+  G::chunk_store(pre, sm, sm + G::TILE);
   if (has_stat) stats[threadIdx.x] = sv;
   __syncthreads();
   const FragOff ln = make_frag_off(lane);
@@ -445,7 +282,7 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
     const bf16raw* Os = Qs + G::TILE;
     const float* Ls = stats + (c & 1) * 2 * CHUNK;
     const float* Ds = Ls + CHUNK;
-    chunk_load<HD>(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, (c + 1) * CHUNK, p.L);
+    G::chunk_load(pre, qb, p.ld_qkv, w.li, ob, p.ld_dout, w.lo, (c + 1) * CHUNK, p.L);
     sv = stat_load((c + 1) * CHUNK);
     if (w.active) {
       const int nrows = min(CHUNK, p.L - c * CHUNK);
@@ -453,11 +290,11 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
 #pragma unroll
       for (int t = 0; t < QC; ++t)
         // padded query rows: Ls = +huge -> P = 0, zero Q / dO rows; padded keys only feed dk / dv rows that are never stored
-        if (t < nt) dkv_tile<HD>(dk, dv, Qs, Os, Ls, Ds, t * 32, kf, vf, c2, ln, lane);
+        if (t < nt) G::dkv_tile(dk, dv, Qs, Os, Ls, Ds, t * 32, kf, vf, c2, ln, lane);
     }
     if (c + 1 < nch) {
       bf16raw* nx = sm + ((c + 1) & 1) * G::STAGE;
-      chunk_store<HD>(pre, nx, nx + G::TILE);
+      G::chunk_store(pre, nx, nx + G::TILE);
       if (has_stat) stats[((c + 1) & 1) * 2 * CHUNK + threadIdx.x] = sv;
     }
     __syncthreads();
@@ -469,8 +306,8 @@ __global__ __launch_bounds__(THREADS, HD == 32 ? 3 : HD == 96 ? 2 : 1) void bwd_
     if (kk >= p.L) return nullptr;
     return attn_cls_row(p, kk) ? dqkv_cls + (long)w.s * p.ld_dqkv : dqkv + lin_row(w.li, kk) * p.ld_dqkv;
   };
-  store_rows<HD>(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * HD : nullptr; });
-  store_rows<HD>(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * HD : nullptr; });
+  G::store_rows(stg, dk, p.scale, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + D + h * HD : nullptr; });
+  G::store_rows(stg, dv, 1.0f, lane, [&](int r) -> bf16raw* { bf16raw* b = base_of(r); return b ? b + 2 * D + h * HD : nullptr; });
 }
 
 // host side ---------------------------------------------------------------------------------------
@@ -478,18 +315,18 @@ static dim3 grid_of(const AttnP& p) { return dim3((unsigned)p.S * (unsigned)cdiv
 
 template <int HD>
 static int fwd_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
-  hipLaunchKernelGGL(fwd_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_KV, st, p, (const bf16raw*)qkv, (bf16raw*)out, lse);
+  hipLaunchKernelGGL(fwd_kernel<HD>, grid_of(p), dim3(THREADS), LDS_KV<HD>, st, p, (const bf16raw*)qkv, (bf16raw*)out, lse);
   return check_launch("attn_fwd_hd");
 }
 template <int HD>
 static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, float* delta, void* dqkv,
                       void* dqkv_cls, hipStream_t st) {
-  hipLaunchKernelGGL(bwd_dq_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_KV, st, p, (const bf16raw*)qkv, (const bf16raw*)o,
+  hipLaunchKernelGGL(bwd_dq_kernel<HD>, grid_of(p), dim3(THREADS), LDS_KV<HD>, st, p, (const bf16raw*)qkv, (const bf16raw*)o,
                      (const bf16raw*)dout, lse, delta, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
   const int rc = check_launch("attn_bwd_dq_hd");
   if (rc) return rc;
-  allow_lds<bwd_dkv_kernel<HD>>(Geo<HD>::LDS_DKV);
-  hipLaunchKernelGGL(bwd_dkv_kernel<HD>, grid_of(p), dim3(THREADS), Geo<HD>::LDS_DKV, st, p, (const bf16raw*)qkv, (const bf16raw*)dout,
+  allow_lds<bwd_dkv_kernel<HD>>(LDS_DKV<HD>);
+  hipLaunchKernelGGL(bwd_dkv_kernel<HD>, grid_of(p), dim3(THREADS), LDS_DKV<HD>, st, p, (const bf16raw*)qkv, (const bf16raw*)dout,
                      lse, (const float*)delta, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
   return check_launch("attn_bwd_dkv_hd");
 }
@@ -513,8 +350,8 @@ static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void
 // =====================================================================================================================
 namespace hdsmall {
 
-using hdim::Frag;
-using hdim::Geo;
+using hdim::Geo;                                  // NS / NK / NT, Frag and store_rows of a head
+template <int HD> using Frag = typename Geo<HD>::Frag;
 
 template <int HD> struct Sm {
   static constexpr int SLAB = 32 * 64;                                  // elements of one [32][64] slab
@@ -642,7 +479,7 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS) void fwd_kerne
   for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
   accum<HD>(acc, Vs, pr, fo);
   // whole rows through the (now idle) V tile
-  hdim::store_rows<HD>(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
+  Geo<HD>::store_rows(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
     return (r < used && row0 + r < total) ? out + rows_of<CLS>(p, tile, G, r).out * p.ld_out + h * HD : nullptr;
   });
   if (valid && lane < 32) lse[me.lse + (long)h * L] = m * LN2 + __logf(l);
@@ -720,7 +557,7 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
     for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
     accum<HD>(acc, Ks, ds, fo);
     // K tile: its last reader was the MFMA chain above
-    hdim::store_rows<HD>(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
+    Geo<HD>::store_rows(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
   }
   // ---- phase 2: lanes = keys.  dV^T = dO^T P, dK^T = Q^T dS.  Only this phase's accumulators are live from here on.
   {
@@ -757,8 +594,8 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
     for (int n = 0; n < G_::NT; ++n) { zero16(dk[n]); zero16(dv[n]); }
     accum<HD>(dv, Os, pr, fo);
     accum<HD>(dk, Qs, ds, fo);
-    hdim::store_rows<HD>(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
-    hdim::store_rows<HD>(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
+    Geo<HD>::store_rows(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
+    Geo<HD>::store_rows(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
   }
 }
 
