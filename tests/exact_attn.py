@@ -18,6 +18,11 @@ the T frames of a clip, so its code, Q, K and V are drawn once per (clip, head))
 patch position p; the cls row is shared by the P sequences of a clip), 'space_nocls' (VTX_ATTN_SPACE_NOCLS: clip b, frame
 t, token rows only), 'cross' (separate q [B, Lq, C] and k, v [B, Lk, C]).  layout_rows restates the row addressing of the
 three strided layouts.  The float64 reference works on the winner lists, never on a dense L x L matrix.
+
+Kinds: 'exact' (every output representable in bf16), 'round' (forward only: V in 128..255, ties and inexact outputs at the
+store) and 'graded' (forward only: winners' scores graded in steps of 8 under a scale that makes c2 exactly 2^-3, so the
+rescale of the online softmax takes the factors 1/2 and 1/4; see the section "graded scores").  A case carries the scale
+it is to be run with: SCALE, or SCALE_GRADED for 'graded'.
 """
 import math
 
@@ -144,7 +149,8 @@ def _ints(rng, shape, lo, hi, density=1.0):
 
 class Items:
     """Batch of I routed items with nq queries and nk keys each (float64 numpy): Q, dO [I, nq, hd]; K, V [I, nk, hd];
-    win [I, nq, 4]; nwin [I, nq]; kcode / qcode; R, hd, kind ('exact' | 'round'), bwd."""
+    win [I, nq, 4]; nwin [I, nq]; kcode / qcode; R, hd, kind ('exact' | 'round' | 'graded'), bwd.  Graded items (build_graded)
+    also carry grade [I, nk], top [I, nq] and straddle."""
 
 
 def build_items(I, nq, nk, hd, kind, bwd, seed, R=None, shared=None, required=None):
@@ -263,6 +269,226 @@ def _ds_item(it, n):
     return wi, valid, P * (dP - delta[:, None]) * valid
 
 
+# ------------------------------------------------------------------------------------------------ graded scores
+# kind 'graded' (forward only): the online softmax's rescale factor takes the values 1/2 and 1/4, not only 0 and 1.
+# The kernels form c2 = scale * LOG2E in fp32; with scale = fl32(ln 2) / 8 that product is exactly 2^-3 (asserted below and in
+# tests/test_exact_attn_graded_premise.py; both fp32 neighbours of fl32(ln 2) miss it), so raw scores that are multiples of 8
+# are integers in the exponent and alpha and every probability are powers of two.  Two more routing dims, R and R + 1, grade
+# the scores: in dim R a key carries -grade and every query 8; in dim R + 1 every key carries 1 and a query -8 top.  A winner
+# scores -8 (grade + top), a loser at most -T_NEG.  Groups of 1, 2 and 4 keys hold the grades (0), (0, 0) and (2, 2, 1, 0) in
+# the order of the key index, so l = sum 2^-grade is 1, 2 or 2, the final maximum is -8 top, lse = (log2 l - top) ln 2, and the
+# running maximum of a four-group rises along the keys.  For every chunk boundary b (the multiples of 64 below nk: the 64-key
+# chunks of attn_hd.hip, the 128-key chunks and blocks of the others) STRADDLE queries take a four-group with keys on both
+# sides of b: the maximum they carry into the later chunk is lower by 8 or 16 than the one they find there.
+# V holds integers 1..31: O = (sum 2^-grade v) / l is n / 8 with n <= 248, representable in bf16, and there is no
+# cancellation, so an ulp on an unpacked fp32 factor (should the hardware's exp2 miss a power of two by one) stays a relative
+# error of a few 2^-24 and cannot move the stored bf16 value.
+LOG2E_F32 = np.float32(1.4426950408889634)         # csrc/attn_common.h
+SCALE_GRADED = float(np.float32(math.log(2.0)) / np.float32(8.0))
+assert np.float32(SCALE_GRADED) * LOG2E_F32 == np.float32(0.125)
+GRADES = {1: (0,), 2: (0, 0), 4: (2, 2, 1, 0)}
+TOPS = 3                                           # top in 0 .. TOPS - 1
+STRADDLE = 8                                       # queries per chunk boundary and item
+CHUNK_EDGE = 64
+
+
+def chunk_bounds(nk):
+    return list(range(CHUNK_EDGE, nk, CHUNK_EDGE))
+
+
+def _graded_groups(nk, rng, g0):
+    """Partition of range(nk) into ascending groups of 1, 2 or 4 and, per chunk boundary, the indices of the four-groups built
+    to straddle it (up to STRADDLE, as many as the keys on either side allow, at least one; 1, 2 or 3 of the four keys on
+    the later side).  g0 (None: no shared row): the grade of key 0 -- 2 puts it in a four-group, where the lowest key index
+    has that grade, 0 in a group of 1 or 2; the third value is the index of key 0's group."""
+    free = set(range(nk)) - ({0} if g0 is not None else set())
+    groups, strad = [], {}
+    for b in chunk_bounds(nk):
+        early = [int(x) for x in rng.permutation(sorted(x for x in free if b - CHUNK_EDGE <= x < b))]
+        late = [int(x) for x in rng.permutation(sorted(x for x in free if b <= x < b + CHUNK_EDGE))]
+        strad[b] = []
+        for j in range(STRADDLE):
+            nl = min(1 + j % 3, len(late))
+            if nl == 0 or len(early) < 4 - nl:
+                break
+            g = sorted([late.pop() for _ in range(nl)] + [early.pop() for _ in range(4 - nl)])
+            free -= set(g)
+            strad[b].append(len(groups))
+            groups.append(g)
+        assert strad[b], f'no four-group straddles key {b} of {nk}'
+    first = None
+    if g0 is not None:
+        rest = [int(x) for x in rng.permutation(sorted(free))]
+        size = 4 if g0 == 2 else int(rng.choice([1, 2]))
+        assert len(rest) >= size - 1
+        g = [0] + sorted(rest[:size - 1])
+        free -= set(g)
+        first = len(groups)
+        groups.append(g)
+    perm = [int(x) for x in rng.permutation(sorted(free))]
+    i = 0
+    while i < len(perm):
+        s = int(rng.choice([1, 2, 4], p=[0.25, 0.45, 0.30]))
+        while s > len(perm) - i:
+            s //= 2
+        groups.append(sorted(perm[i:i + s]))
+        i += s
+    return groups, strad, first
+
+
+def build_graded(I, nq, nk, hd, seed, R=None, shared=None):
+    """I graded items (see above).  shared: dict(first_code, g0, top0 [I]; Q0, K0, V0 [I, hd]) -- the shared cls row: code,
+    grade entry, top, Q, K and V of row 0 fixed per item; query 0 takes key 0's group.  Items gains grade [I, nk], top
+    [I, nq] and straddle {b: [I, STRADDLE] query indices}."""
+    rng = np.random.default_rng(seed)
+    if R is None:
+        R = routing_dims(int(math.ceil(nk / 1.3)) + 2)
+    R2 = R + 2
+    assert R2 + 2 <= hd, (R, hd)
+    bounds = chunk_bounds(nk)
+    assert nq >= STRADDLE * len(bounds) + 1, 'too few queries for the straddle quota'
+    it = Items()
+    it.I, it.nq, it.nk, it.hd, it.kind, it.bwd, it.R = I, nq, nk, hd, 'graded', False, R
+    pairs = np.array(_pairs(R))
+    ncodes = len(pairs)
+    kcode = np.empty((I, nk), np.int64)
+    grade = np.empty((I, nk), np.int64)
+    qcode = np.empty((I, nq), np.int64)
+    win = np.full((I, nq, 4), -1, np.int64)
+    nwin = np.empty((I, nq), np.int64)
+    it.straddle = {b: np.empty((I, STRADDLE), np.int64) for b in bounds}
+    for n in range(I):
+        g0 = None if shared is None else int(shared['g0'][n])
+        groups, strad, first = _graded_groups(nk, rng, g0)
+        assert len(groups) <= ncodes, (len(groups), ncodes)
+        if shared is None:
+            codes = rng.choice(ncodes, len(groups), replace=False)
+        else:
+            fc = int(shared['first_code'][n])
+            codes = np.full(len(groups), fc)
+            others = [j for j in range(len(groups)) if j != first]
+            codes[others] = rng.permutation([c for c in range(ncodes) if c != fc])[:len(others)]
+        for g, c in zip(groups, codes):
+            kcode[n, g] = c
+            grade[n, g] = GRADES[len(g)]
+        # queries: query 0 -> key 0's group (shared row); STRADDLE per boundary, round-robin over its groups; then every group
+        # not yet taken once, as far as the queries go; the rest at random
+        head = [] if first is None else [first]
+        quota = [strad[b][j % len(strad[b])] for b in bounds for j in range(STRADDLE)]
+        taken = set(head + quota)
+        cover = [int(j) for j in rng.permutation(len(groups)) if j not in taken]
+        tail = (quota + cover + [int(j) for j in rng.integers(0, len(groups), nq)])[:nq - len(head)]
+        pos = rng.permutation(nq - len(head)) + len(head)                  # position of every entry of tail
+        qgrp = np.empty(nq, np.int64)
+        qgrp[:len(head)] = head
+        qgrp[pos] = tail
+        for k, b in enumerate(bounds):
+            it.straddle[b][n] = pos[k * STRADDLE:(k + 1) * STRADDLE]
+        for i, gi in enumerate(qgrp):
+            g = groups[gi]
+            win[n, i, :len(g)] = g
+            nwin[n, i] = len(g)
+        qcode[n] = codes[qgrp]
+    top = rng.integers(0, TOPS, (I, nq))
+    fa = R2 + (hd - R2) // 2                               # free dims: Q in [R2, fa), K in [fa, hd)
+    Q = np.full((I, nq, hd), -T_NEG)
+    Q[:, :, fa:] = 0.0
+    Q[:, :, R2:fa] = _ints(rng, (I, nq, fa - R2), -2, 2, 0.5)
+    np.put_along_axis(Q, pairs[qcode], 0.0, axis=2)
+    K = np.zeros((I, nk, hd))
+    K[:, :, fa:] = _ints(rng, (I, nk, hd - fa), -2, 2, 0.5)
+    np.put_along_axis(K, pairs[kcode], 1.0, axis=2)
+    V = _ints(rng, (I, nk, hd), 1, 31)
+    if shared is not None:
+        top[:, 0] = shared['top0']
+        assert (grade[:, 0] == shared['g0']).all()
+        Q[:, 0], K[:, 0], V[:, 0] = shared['Q0'], shared['K0'], shared['V0']
+    Q[:, :, R], Q[:, :, R + 1] = 8.0, -8.0 * top
+    K[:, :, R], K[:, :, R + 1] = -grade, 1.0
+    it.Q, it.K, it.V, it.win, it.nwin, it.kcode, it.qcode, it.grade, it.top = Q, K, V, win, nwin, kcode, qcode, grade, top
+    it.dO = np.zeros((I, nq, hd))
+    return it
+
+
+def shared_rows_graded(I, hd, R, seed):
+    """Row 0 of Q / K / V, its code, its grade entry (0 or 2) and its top for I (clip, head) pairs: drawn once each."""
+    rng = np.random.default_rng(seed)
+    pairs = np.array(_pairs(R))
+    code = rng.integers(0, len(pairs), I)
+    g0 = 2 * rng.integers(0, 2, I)
+    top0 = rng.integers(0, TOPS, I)
+    R2 = R + 2
+    fa = R2 + (hd - R2) // 2
+    Q0 = np.full((I, hd), -T_NEG)
+    Q0[:, fa:] = 0.0
+    Q0[:, R2:fa] = _ints(rng, (I, fa - R2), -2, 2, 0.5)
+    np.put_along_axis(Q0, pairs[code], 0.0, axis=1)
+    K0 = np.zeros((I, hd))
+    K0[:, fa:] = _ints(rng, (I, hd - fa), -2, 2, 0.5)
+    np.put_along_axis(K0, pairs[code], 1.0, axis=1)
+    V0 = _ints(rng, (I, hd), 1, 31)
+    return dict(first_code=code, g0=g0, top0=top0, Q0=Q0, K0=K0, V0=V0)
+
+
+def straddle_counts(it):
+    """{b: [I] number of queries whose winners lie on both sides of key b with the strictly higher score on the later side}"""
+    valid = it.win >= 0
+    wi = np.where(valid, it.win, 0)
+    g = np.take_along_axis(it.grade, wi.reshape(it.I, -1), 1).reshape(wi.shape).astype(np.float64)
+    res = {}
+    for b in chunk_bounds(it.nk):
+        early = np.where(valid & (wi < b), -g, -np.inf).max(2)              # best score / 8 on either side (top is common)
+        late = np.where(valid & (wi >= b), -g, -np.inf).max(2)
+        res[b] = (np.isfinite(early) & np.isfinite(late) & (late > early)).sum(1)
+    return res
+
+
+def reference_graded(it):
+    """Exact float64 results of graded items, with every premise asserted.  Returns a dict of torch float64: O, O_abs (= O: V is
+    positive) [I, nq, hd], O_n (terms per output), lse, log2l, top [I, nq], nwin."""
+    I, nq, nk = it.I, it.nq, it.nk
+    assert not it.bwd and np.isin(it.nwin, (1, 2, 4)).all()
+    for name, a in (('Q', it.Q), ('K', it.K), ('V', it.V)):
+        t = torch.from_numpy(a)
+        assert torch.equal(X.rne_bf16(t).double(), t), f'{name} is not bf16-representable'
+    valid = it.win >= 0
+    wi = np.where(valid, it.win, 0)
+    gw = np.take_along_axis(it.grade, wi.reshape(I, -1), 1).reshape(wi.shape)
+    # dense scores of every item: a winner scores -8 (grade + top), every other key <= -T_NEG; exponents relative to the row
+    # maximum, in the kernels' fp32 arithmetic: winners are integers, losers underflow (<= -150: below the smallest denormal)
+    for n in range(I):
+        s = it.Q[n] @ it.K[n].T
+        w = np.zeros((nq, nk), bool)
+        w[np.arange(nq)[:, None].repeat(4, 1)[valid[n]], wi[n][valid[n]]] = True
+        want = -8.0 * (it.grade[n][None, :] + it.top[n][:, None])
+        assert (s[w] == want[w]).all() and (s[~w] <= -T_NEG).all(), 'graded scores'
+        assert (w.sum(1) == it.nwin[n]).all()
+        assert (s.max(1) == -8.0 * it.top[n]).all(), 'the final maximum is -8 top'
+        e = (s - s.max(1, keepdims=True)) * 0.125
+        assert (e[w] == np.round(e[w])).all() and e[~w].max(initial=-np.inf) <= -150.0, 'exponents'
+    assert np.abs(it.Q).sum(-1).max() * 2.0 < X.EXACT_LIMIT                    # |q.k| partial sums (|k| <= 2)
+    assert np.abs(it.V).sum(1).max() < X.EXACT_LIMIT                           # O accumulator of a chunk that is wiped later
+    wgt = np.where(valid, 2.0 ** -gw, 0.0)
+    l = wgt.sum(2)
+    assert np.isin(l, (1.0, 2.0)).all() and (l == np.where(it.nwin == 1, 1.0, 2.0)).all()
+    assert ((np.diff(it.win, axis=2) > 0) | ~valid[..., 1:]).all(), 'winner lists ascend'
+    assert ((np.diff(gw, axis=2) <= 0) | ~valid[..., 1:]).all(), 'the grade falls as the key index rises'
+    Vw = it.V[np.arange(I)[:, None, None], wi]
+    O = (wgt[..., None] * Vw).sum(2) / l[..., None]
+    Ot = torch.from_numpy(O)
+    assert torch.equal(X.rne_bf16(Ot).double(), Ot), 'graded case: O is not bf16-representable'
+    for b, cnt in straddle_counts(it).items():
+        assert (cnt >= STRADDLE).all(), f'boundary {b}: {cnt.min()} queries see the maximum rise across it'
+        rows = it.straddle[b]
+        lo = np.take_along_axis(it.win[:, :, 0], rows, 1)
+        hi = np.take_along_axis(it.win[:, :, 3], rows, 1)
+        assert ((lo < b) & (hi >= b)).all(), 'a straddle query does not straddle'
+    log2l = np.log2(l)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))     # noqa: E731
+    return dict(O=Ot, O_abs=Ot.clone(), O_n=t(np.broadcast_to(it.nwin[..., None], O.shape)), lse=t((log2l - it.top) * LN2),
+                log2l=t(log2l), top=t(it.top), nwin=torch.from_numpy(it.nwin))
+
+
 def reference(it, scale=SCALE):
     """Exact float64 results of one batch of items, with every premise asserted.  Returns a dict of torch float64:
     O [I, nq, hd], lse [I, nq], nwin [I, nq]; with bwd also dq [I, nq, hd], dk, dv [I, nk, hd] and their sums of |terms|
@@ -350,7 +576,8 @@ def assert_edges(it, ref, required=None):
 # ------------------------------------------------------------------------------------------------ cases by layout
 class Case:
     """A routed case in a physical layout: layout in 'contig', 'space', 'time_cls', 'space_nocls' (self-attention) or
-    'cross'.  Self-attention cases carry their own B, T, P (0 for contig), cls_group -- the number of sequences that share one
+    'cross'.  scale is the descriptor's scale (SCALE; SCALE_GRADED for kind 'graded', whose cases also carry out_abs / out_n for
+    value_bounds and log2l / top, shaped as lse, for lse_graded_ok).  Self-attention cases carry their own B, T, P (0 for contig), cls_group -- the number of sequences that share one
     cls row: T for space, P for time_cls, 0 otherwise -- and cls_rows, the cls row of every clip in qkv / dqkv.
     Tensors (float64 CPU):
     self-attention: qkv [rows, 3D] (space_nocls: cls rows NaN), dout [out_rows, D]; expected out [out_rows, D], lse
@@ -364,13 +591,30 @@ def _sh(a, S, H, L, hd):
     return a.reshape(S, H, L, hd).transpose(0, 2, 1, 3).reshape(S, L, H * hd)
 
 
-def contig_case(S, L, H, kind='exact', bwd=True, seed=0, hd=64):
-    it = build_items(S * H, L, L, hd, kind, bwd, seed)
+def _routed(I, nq, nk, hd, kind, bwd, seed, R=None, shared=None):
+    """Items and their reference: build_items + reference (+ assert_edges), or build_graded + reference_graded."""
+    if kind == 'graded':
+        assert not bwd, 'graded cases are forward only'
+        it = build_graded(I, nq, nk, hd, seed, R=R, shared=shared)
+        return it, reference_graded(it)
+    it = build_items(I, nq, nk, hd, kind, bwd, seed, R=R, shared=shared)
     r = reference(it)
     if bwd:
         assert_edges(it, r)
+    return it, r
+
+
+def _graded_fields(c, r, place, lse_shape):
+    """Graded case: out_abs / out_n (the operands of value_bounds, laid out as out by `place`), log2l and top (as lse)."""
+    c.out_abs, c.out_n = place(r['O_abs'].numpy()), place(r['O_n'].numpy())
+    c.log2l, c.top = r['log2l'].numpy().reshape(lse_shape), r['top'].numpy().reshape(lse_shape)
+
+
+def contig_case(S, L, H, kind='exact', bwd=True, seed=0, hd=64):
+    it, r = _routed(S * H, L, L, hd, kind, bwd, seed)
     c = Case()
     c.layout, c.S, c.L, c.H, c.hd, c.kind, c.bwd, c.items, c.ref = 'contig', S, L, H, hd, kind, bwd, it, r
+    c.scale = SCALE_GRADED if kind == 'graded' else SCALE
     c.B, c.T, c.P, c.cls_group = 0, 0, 0, 0
     D = H * hd
     c.qkv = np.concatenate([_sh(it.Q, S, H, L, hd), _sh(it.K, S, H, L, hd), _sh(it.V, S, H, L, hd)], 2).reshape(S * L, 3 * D)
@@ -378,6 +622,8 @@ def contig_case(S, L, H, kind='exact', bwd=True, seed=0, hd=64):
     c.out = _sh(r['O'].numpy(), S, H, L, hd).reshape(S * L, D)
     c.lse = r['lse'].numpy().reshape(S, H, L)
     c.nwin = it.nwin.reshape(S, H, L)
+    if kind == 'graded':
+        _graded_fields(c, r, lambda a: _sh(a, S, H, L, hd).reshape(S * L, D), (S, H, L))
     if bwd:
         for key in ('', '_abs', '_n'):
             c.__dict__['dqkv' + key] = np.concatenate(
@@ -419,16 +665,14 @@ def _layout_case(layout, B, T, P, H, kind, bwd, seed, hd):
     cls_group = {'space': T, 'time_cls': P, 'space_nocls': 0}[layout]
     if cls_group:
         R = routing_dims(int(math.ceil(L / 1.3)) + 2)
-        sh = shared_rows(B * H, hd, R, kind, bwd, seed + 1)
+        sh = shared_rows_graded(B * H, hd, R, seed + 1) if kind == 'graded' else shared_rows(B * H, hd, R, kind, bwd, seed + 1)
         # item n = s * H + h uses the shared rows of (b, h), b = s // cls_group
         idx = (np.arange(S)[:, None] // cls_group * H + np.arange(H)[None, :]).reshape(-1)
-        it = build_items(S * H, L, L, hd, kind, bwd, seed, R=R, shared={k: v[idx] for k, v in sh.items()})
+        it, r = _routed(S * H, L, L, hd, kind, bwd, seed, R=R, shared={k: v[idx] for k, v in sh.items()})
     else:
-        it = build_items(S * H, L, L, hd, kind, bwd, seed)
-    r = reference(it)
-    if bwd:
-        assert_edges(it, r)
+        it, r = _routed(S * H, L, L, hd, kind, bwd, seed)
     c = Case()
+    c.scale = SCALE_GRADED if kind == 'graded' else SCALE
     c.layout, c.S, c.L, c.H, c.hd, c.B, c.T, c.P, c.kind, c.bwd, c.items, c.ref = \
         layout, S, L, H, hd, B, T, P, kind, bwd, it, r
     c.cls_group = cls_group
@@ -444,6 +688,12 @@ def _layout_case(layout, B, T, P, H, kind, bwd, seed, hd):
     c.out[rout.reshape(-1)] = _sh(r['O'].numpy(), S, H, L, hd).reshape(S * L, D)
     c.lse = r['lse'].numpy().reshape(S, H, L)
     c.nwin = it.nwin.reshape(S, H, L)
+    if kind == 'graded':
+        def place(a):
+            full = np.zeros((orows, D))
+            full[rout.reshape(-1)] = _sh(a, S, H, L, hd).reshape(S * L, D)
+            return full
+        _graded_fields(c, r, place, (S, H, L))
     if bwd:
         i0 = 1 if cls_group else 0
         for key in ('', '_abs', '_n'):
@@ -473,12 +723,10 @@ def space_nocls_case(B, T, P, H, kind='exact', bwd=True, seed=0, hd=64):
 
 
 def cross_case(B, Lq, Lk, heads, hd, kind='exact', bwd=True, seed=0):
-    it = build_items(B * heads, Lq, Lk, hd, kind, bwd, seed)
-    r = reference(it)
-    if bwd:
-        assert_edges(it, r)
+    it, r = _routed(B * heads, Lq, Lk, hd, kind, bwd, seed)
     c = Case()
     c.layout, c.B, c.Lq, c.Lk, c.H, c.hd, c.kind, c.bwd, c.items, c.ref = 'cross', B, Lq, Lk, heads, hd, kind, bwd, it, r
+    c.scale = SCALE_GRADED if kind == 'graded' else SCALE
     c.q = _sh(it.Q, B, heads, Lq, hd)
     c.k = _sh(it.K, B, heads, Lk, hd)
     c.v = _sh(it.V, B, heads, Lk, hd)
@@ -486,6 +734,8 @@ def cross_case(B, Lq, Lk, heads, hd, kind='exact', bwd=True, seed=0):
     c.out = _sh(r['O'].numpy(), B, heads, Lq, hd)
     c.lse = r['lse'].numpy().reshape(B, heads, Lq)
     c.nwin = it.nwin.reshape(B, heads, Lq)
+    if kind == 'graded':
+        _graded_fields(c, r, lambda a: _sh(a, B, heads, Lq, hd), (B, heads, Lq))
     if bwd:
         for key in ('', '_abs', '_n'):
             c.__dict__['dq' + key] = _sh(r['dq' + key].numpy(), B, heads, Lq, hd)
@@ -497,8 +747,10 @@ def cross_case(B, Lq, Lk, heads, hd, kind='exact', bwd=True, seed=0):
 # ------------------------------------------------------------------------------------------------ expectations
 def expect(name, v, dtype, kind='round'):
     """Expected stored output of an exact float64 value: fp32 itself, bf16 RNE.  kind 'exact' also asserts the values are
-    bf16-representable; 'round' asserts the tie / inexact shares of exact.expect_bf16; None only the fp32 premise."""
+    bf16-representable, and so does 'graded'; 'round' asserts the tie / inexact shares of exact.expect_bf16; None only the
+    fp32 premise."""
     v = torch.as_tensor(v).double()
+    kind = 'exact' if kind == 'graded' else kind
     if dtype == torch.float32:
         X.assert_fp32_exact(name, v)
         return v.float()
@@ -534,6 +786,19 @@ def lse_ok(got, nwin, ulps=4):
     want = torch.log(torch.as_tensor(nwin).double())
     ulp = torch.where(want > 0, 2.0 ** (torch.floor(torch.log2(want.clamp(min=1e-30))) - 23), torch.zeros_like(want))
     return torch.where(want == 0, got == 0, (got - want).abs() <= ulps * ulp)
+
+
+def lse_graded_ok(got, log2l, top, ulps=4, top_ulps=2):
+    """lse of a graded case against (k - top) ln 2, k = log2 l: within `ulps` fp32 ulps at |k ln 2| (lse_ok's bar: the error of
+    log l) plus `top_ulps` fp32 ulps at |top ln 2| (the rounded constant in the product (m c2) LN2, which is otherwise exact
+    for top = 1, 2, and the final sum); exactly 0 where k = top = 0."""
+    got = got.double()
+    k, top = torch.as_tensor(log2l).double(), torch.as_tensor(top).double()
+
+    def ulp(x):
+        return torch.where(x > 0, 2.0 ** (torch.floor(torch.log2(x.clamp(min=1e-30))) - 23), torch.zeros_like(x))
+    bar = ulps * ulp(k * LN2) + top_ulps * ulp(top * LN2)
+    return (got - (k - top) * LN2).abs() <= bar
 
 
 def probs_ok(got, want, ulps=2):
