@@ -17,6 +17,7 @@ from oracle import synth, vt_oracle as O
 from oracle.synth import synth_tensor
 
 from model_common import DEV, PRECS, SMALL, _build, _reset_precision, _train_step  # noqa: F401
+from traj import ffn_drop_pattern as _ffn_drop_pattern      # the DropPath mask predictor, shared with the trajectory tests
 
 pytestmark = pytest.mark.gpu
 
@@ -179,22 +180,6 @@ def test_direct_parameter_gradients_match_autograd_accumulation():
                 check(f'{prec} two backward passes {k}', p.grad.cpu(), 2 * ref[k].cpu(), 1e-6)
         finally:
             functions.set_direct_grads(False)
-
-
-def _ffn_drop_pattern(seed, B, P, T, layers, rate=0.1):
-    """The FFN DropPath masks a training forward draws after torch.manual_seed(seed): per layer with p > 0 the reference draws
-    (B*P) temporal, (B*T) spatial and B FFN values from the CPU generator, in that order (transformer.py:34-42, 268-275, 371-377, 543)."""
-    torch.manual_seed(seed)
-    out = []
-    for p in np.linspace(0, rate, layers):
-        if p == 0:
-            out.append([False] * B)
-            continue
-        torch.rand(B * P, 1, 1)
-        torch.rand(B * T, 1, 1)
-        u = torch.rand(B, 1, 1).reshape(B)
-        out.append([bool(np.floor(np.float32(1 - p) + np.float32(v)) == 0) for v in u.tolist()])
-    return out
 
 
 @pytest.mark.parametrize('prec,tol,gtol', PRECS)
