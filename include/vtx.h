@@ -72,7 +72,8 @@ const char* vtx_last_error_string(void);
  * attention with head_dim 32, 96 or 128: mfma, the default, runs the MFMA kernels of csrc/attn_hd.hip -- chunk-streaming above
  * 32 tokens in every layout, packed (32 / L sequences a tile) for up to 32 tokens in VTX_ATTN_CONTIG and VTX_ATTN_TIME_CLS; valu
  * the VALU kernels, which serve everything else bf16 at those head dims (VTX_ATTN_SPACE and VTX_ATTN_SPACE_NOCLS of up to 32
- * tokens, the `probs` pass); head_dim 64 and fp32 are not touched by either value), "tn_cus" = n (compute units the weight-gradient
+ * tokens, the `probs` pass); head_dim 64 -- whose packed kernels are instantiations of the same bodies in csrc/attn_hd.hip -- and
+ * fp32 are not touched by either value), "tn_cus" = n (compute units the weight-gradient
  * kernel's one-round slab split is sized for: 256; 240 leaves room for 16 CUs held by a collective in flight -- another, equally fixed
  * summation order of the slabs), "attn_hw_fwd", "attn_hw_bwd" = n
  * (short-sequence attention: n heads of a row tile per workgroup, 0 = one head and four row tiles; defaults 16 / 4), "pp_grid", "pp_cg",

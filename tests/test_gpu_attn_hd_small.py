@@ -1,5 +1,6 @@
-"""Packed MFMA attention for up to 32 tokens at head_dim 32, 96 and 128 (csrc/attn_hd.hip, namespace hdsmall: bf16, layouts
-CONTIG and TIME_CLS; option attn_hd = mfma, the default).  G = 32 / L sequences share a 32-row tile, one wave per (tile, head).
+"""Packed MFMA attention for up to 32 tokens (csrc/attn_hd.hip, attn_fwd_small_kernel / attn_bwd_small_kernel<HD, HW, CLS>: bf16,
+layouts CONTIG and TIME_CLS), here at head_dim 32, 96 and 128, where option attn_hd = mfma, the default, selects it.  G = 32 / L
+sequences share a 32-row tile, one wave per (tile, head).
 
   1. exact arithmetic (tests/exact_attn.py, runners of tests/test_gpu_exact_attention.py): every output equals RNE(exact),
      the lse meets its standard, guards and pad columns stay untouched; with one head and four tiles per workgroup
@@ -10,7 +11,8 @@ CONTIG and TIME_CLS; option attn_hd = mfma, the default).  G = 32 / L sequences 
   4. a second run is bit-identical;
   5. the switch is live: attn_hd=valu is attn_valu=1 bit for bit, the default route is within the bars of
      test_mfma_matches_valu of it and differs from it somewhere; fp32 and head_dim 64 ignore the switch;
-  6. head_dim 64 against a build of the parent commit, bit for bit (VTX_PARENT_LIB; skipped otherwise).
+  6. against a build of the parent commit, bit for bit (VTX_PARENT_LIB; skipped otherwise): all four head dims of the packed
+     route on whole guarded buffers, and the two head_dim-64 tests from before the kernels were written once.
 """
 import functools
 
@@ -19,8 +21,8 @@ import torch
 
 import exact_attn as A
 import test_gpu_exact_attention as E
-from helpers import check
-from test_gpu_attn_head_dims import HDS, _against_f64, _plain, attn_hd  # noqa: F401  (attn_hd: fixture)
+from helpers import check, report
+from test_gpu_attn_head_dims import HDS, _against_f64, _geometry, _launch, _plain, attn_hd  # noqa: F401  (attn_hd: fixture)
 from test_gpu_kernels import dev, rnd
 from test_gpu_long_attention import _bits, assert_parent_bit_for_bit, parent_build_cases
 
@@ -167,6 +169,58 @@ def time_cls_cases(spec):
         torch.cuda.synchronize()
         res[f'time_cls {B} {T} {P} {H}'] = [t.cpu() for t in (o, lse, dqkv, dcls)]
     return res
+
+
+PACKED_HDS = (32, 64, 96, 128)
+PACKED_DEFAULT = [('contig', (40, 1)), ('contig', (7, 8)), ('contig', (7, 9)), ('contig', (7, 17)), ('contig', (7, 32)),
+                  ('time_cls', (2, 8, 5)), ('time_cls', (2, 4, 9))]                  # H = 2; (2, 4, 9): a tile spans two clips
+# attn_hw_fwd = attn_hw_bwd = hw: H = 5, where 3 divides no group; H = 12, where the cap of 16 waves at head_dim 64 and of 8
+# elsewhere differ (hw = 16: one group of 12 heads against groups of 8 and 4)
+PACKED_HW = [(hw, dims, H) for hw in ('0', '3', '16') for dims, H in (((37, 8), 5), ((5, 8), 12))]
+
+
+def packed_cases(hds):
+    """{'hd': {case: [out, lse, dqkv(, dqkv_cls)] as allocated, on the CPU}} of this process's library: the packed route, bf16,
+    guarded buffers (the launcher of tests/test_gpu_attn_head_dims.py)."""
+    import vtx
+    vtx.set_option('attn_hd', 'mfma')
+    res = {}
+    try:
+        for hd in hds:
+            row = {}
+            for hw, layout, dims, H in [('', lay, d, 2) for lay, d in PACKED_DEFAULT] + [(hw, 'contig', d, H) for hw, d, H in PACKED_HW]:
+                for opt, default in (('attn_hw_fwd', '16'), ('attn_hw_bwd', '4')):
+                    vtx.set_option(opt, hw or default)
+                S, L, B, T, P, nrows, orows, rin, rout, grp = _geometry(layout, dims)
+                assert L <= 32                                          # csrc/attn.hip: attn_route
+                qkv, do = rnd(nrows, 3 * H * hd, seed=L + hd) * 1.5, rnd(orows, H * hd, seed=L + hd + 1)
+                got = _launch(layout, tuple(dims), H, hd, BF16, qkv, do)
+                row[f'{layout} {" ".join(str(d) for d in dims)} H={H}' + (f' hw={hw}' if hw else '')] = [t.cpu() for t in got if t is not None]
+            res[str(hd)] = row
+    finally:
+        vtx.set_option('attn_hw_fwd', '16')
+        vtx.set_option('attn_hw_bwd', '4')
+    return res
+
+
+def test_packed_route_is_the_parent_bit_for_bit(tmp_path):
+    """Every head dim of the packed kernels against a build of the parent commit (where head_dim 64 was a copy of its own in
+    csrc/attn_mfma.hip): whole guarded buffers, NaN sentinels included; all rows in one child process."""
+    want, lib = parent_build_cases(packed_cases, list(PACKED_HDS), tmp_path)
+    got = packed_cases(PACKED_HDS)
+    assert sorted(got) == sorted(want) == sorted(str(hd) for hd in PACKED_HDS)
+    for hd in got:
+        assert sorted(got[hd]) == sorted(want[hd]) and len(got[hd]) == len(PACKED_DEFAULT) + len(PACKED_HW) == 13
+        for case in got[hd]:
+            assert len(got[hd][case]) == len(want[hd][case]) == (4 if case.startswith('time_cls') else 3)
+            for name, a, b in zip(('out', 'lse', 'dqkv', 'dqkv_cls'), got[hd][case], want[hd][case]):
+                assert a.dtype == b.dtype and a.shape == b.shape
+                assert torch.isfinite(a.float()).any(), f'head_dim {hd}, {case}: {name} was never written'
+                assert torch.equal(_bits(a), _bits(b)), \
+                    f'head_dim {hd}, {case}: {name} differs from the parent in {int((_bits(a) != _bits(b)).sum())} of {a.numel()} elements'
+        line = f'ok   packed attention bfloat16 head_dim {hd} bit-identical to {lib} on {len(got[hd])} shapes (whole buffers): ' + ', '.join(got[hd])
+        print(line)
+        report(line)
 
 
 def test_head_dim_64_contig_is_the_parent_bit_for_bit(tmp_path):

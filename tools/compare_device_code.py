@@ -50,9 +50,13 @@ def device_code(obj):
 def main():
     other = sys.argv[1]
     this = sys.argv[2] if len(sys.argv) > 2 else ROOT
-    names = sorted(f for f in os.listdir(os.path.join(this, OBJ)) if f.endswith('.o'))
+    objs = [{f for f in os.listdir(os.path.join(t, OBJ)) if f.endswith('.o')} for t in (other, this)]
     bad = 0
-    for n in names:
+    for n in sorted(objs[0] | objs[1]):
+        if n not in objs[0] or n not in objs[1]:                # a source file was added or retired: its kernels have no partner here
+            bad += 1
+            print(f'{n:18s} ONLY IN {"THIS" if n in objs[1] else "THE OTHER"} TREE')
+            continue
         ta, ka = device_code(os.path.join(other, OBJ, n))
         tb, kb = device_code(os.path.join(this, OBJ, n))
         ha, hb = hashlib.sha256(ta).hexdigest()[:16], hashlib.sha256(tb).hexdigest()[:16]

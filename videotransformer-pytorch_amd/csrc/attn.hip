@@ -10,8 +10,8 @@
 //
 // Small sequences (temporal attention, L = T = 8) pack G = 256/L sequences per
 // workgroup; long ones use one sequence per workgroup and 64-key tiles.  bf16 with
-// head_dim 64 never gets here by default: <= 32 and 33..256 tokens (L = 197 spatial)
-// run the MFMA kernels of attn_mfma.hip, more than 256 (785 spatial at 448^2, 1569
+// head_dim 64 never gets here by default: up to 32 tokens run the packed kernels of attn_hd.hip,
+// 33..256 (L = 197 spatial) the MFMA kernels of attn_mfma.hip, more than 256 (785 spatial at 448^2, 1569
 // joint) those of attn_long.hip; fp32 with head_dim 64 and more than 32 tokens runs the exact-fp32 MFMA kernels of
 // attn_f32.hip.  These kernels are the fp32 path of up to 32 tokens, the `probs` pass (and the forward in front of it)
 // and what attn_valu=1 / attn_long=0 / attn_f32=valu select.  At head_dim 32, 96 and 128 the same holds: bf16 runs the MFMA
@@ -311,11 +311,14 @@ __global__ __launch_bounds__(AT_THREADS, 1) void attn_bwd_dkv_kernel(AttnP p, co
 // Which kernel family serves (dtype, mode, L, head_dim).  The whole precedence is here; the first match wins.  The mode matters
 // up to 32 tokens only: CONTIG and TIME_CLS are packed, SPACE_NOCLS runs the one-workgroup kernels at one tile, SPACE (no model
 // has P < 32) the VALU kernels as before.
-enum Route { SMALL, MFMA, LONG, F32, F32HD, VALU, HDIM, HDSMALL };
+enum Route { SMALL, MFMA, LONG, F32, F32HD, VALU, HDIM };
 static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // VTX_ATTN_VALU=1 forces the VALU path.
   if (options().attn_valu) return VALU;
-  if (attn_small_eligible(dtype, mode, L, hd)) return SMALL;
+  // bf16, up to 32 tokens, CONTIG or TIME_CLS, every head dim -> packed MFMA kernels (attn_hd.hip); at head_dim 32 / 96 / 128
+  // VTX_ATTN_HD=valu sends them to the VALU kernels.  Everything else of up to 32 tokens at those head dims (fp32; SPACE and
+  // SPACE_NOCLS, which no model reaches) has no other kernel.
+  if ((hd == 64 || options().attn_hd) && attn_small_eligible(dtype, mode, L, hd)) return SMALL;
   // bf16, head_dim 64, 33..256 tokens (SPACE_NOCLS: 1..256) -> MFMA kernels (attn_mfma.hip).
   if (attn_mfma_eligible(dtype, mode, L, hd)) return MFMA;
   // bf16, head_dim 64, more than 256 tokens -> chunk-streaming MFMA kernels (attn_long.hip); VTX_ATTN_LONG=0 sends them back here.
@@ -329,10 +332,6 @@ static Route attn_route(int dtype, int mode, int L, int hd, bool probs) {
   // bf16, head_dim 32 / 96 / 128, more than 32 tokens -> chunk-streaming MFMA kernels (attn_hd.hip); VTX_ATTN_HD=valu sends them
   // back here.
   if (options().attn_hd && attn_hd_eligible(dtype, L, hd)) return HDIM;
-  // bf16, head_dim 32 / 96 / 128, up to 32 tokens, CONTIG or TIME_CLS -> packed MFMA kernels (attn_hd.hip), under the same switch.
-  // Everything else at those head dims (fp32 of up to 32 tokens; SPACE and SPACE_NOCLS of up to 32 tokens, which no model
-  // reaches) has no other kernel.
-  if (options().attn_hd && attn_hd_small_eligible(dtype, mode, L, hd)) return HDSMALL;
   return VALU;
 }
 
@@ -429,13 +428,12 @@ extern "C" int vtx_attn_fwd(const vtx_attn_desc* d, void* stream) {
   hipStream_t st = as_stream(stream);
   const bool f32 = d->dtype == VTX_F32;
   switch (attn_route(d->dtype, d->mode, d->L, d->hd, d->probs != nullptr)) {
-    case SMALL: rc = attn_fwd_small_launch(p, d->qkv, d->out, d->lse, st); break;
+    case SMALL: rc = attn_fwd_small_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case MFMA: rc = attn_fwd_mfma_launch(p, d->qkv, d->out, d->lse, st); break;
     case LONG: rc = attn_fwd_long_launch(p, d->qkv, d->out, d->lse, st); break;
     case F32: rc = attn_fwd_f32_launch(p, d->qkv, d->out, d->lse, st); break;
     case F32HD: rc = attn_fwd_hd_f32_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case HDIM: rc = attn_fwd_hd_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
-    case HDSMALL: rc = attn_fwd_hd_small_launch(p, d->hd, d->qkv, d->out, d->lse, st); break;
     case VALU: rc = f32 ? valu_fwd_launch<float, 0>(p, d, st) : valu_fwd_launch<bf16raw, 0>(p, d, st); break;
   }
   if (rc || !d->probs) return rc;
@@ -460,13 +458,12 @@ extern "C" int vtx_attn_bwd(const vtx_attn_bwd_desc* d, void* stream) {
     VTX_REQUIRE(e == hipSuccess, VTX_EINVAL, "attn_bwd: zeroing the cls rows of dqkv: %s", hipGetErrorString(e));
   }
   switch (attn_route(d->f.dtype, d->f.mode, d->f.L, d->f.hd, false)) {
-    case SMALL: return attn_bwd_small_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
+    case SMALL: return attn_bwd_small_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
     case MFMA: return attn_bwd_mfma_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case LONG: return attn_bwd_long_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32: return attn_bwd_f32_launch(p, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case F32HD: return attn_bwd_hd_f32_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
     case HDIM: return attn_bwd_hd_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->delta, d->dqkv, d->dqkv_cls, st);
-    case HDSMALL: return attn_bwd_hd_small_launch(p, d->f.hd, d->f.qkv, d->f.out, d->dout, d->f.lse, d->dqkv, d->dqkv_cls, st);
     case VALU: break;
   }
   return d->f.dtype == VTX_F32 ? valu_bwd_launch<float>(p, d, st) : valu_bwd_launch<bf16raw>(p, d, st);

@@ -41,7 +41,7 @@ __device__ inline long out_row(const AttnP& p, int s, int i) {
 }
 
 
-// ---- bf16 MFMA building blocks shared by attn_mfma.hip (<= 256 tokens) and attn_long.hip (> 256 tokens) ----
+// ---- bf16 MFMA building blocks shared by attn_mfma.hip (33..256 tokens), attn_long.hip (> 256) and attn_hd.hip (its packed kernels: <= 32) ----
 constexpr int MA_THREADS = 256;
 constexpr int MA_MAXT = 8;            // up to 8 tiles of 32 rows (Lp <= 256)
 constexpr int MA_KB = 4;              // key tiles per online-softmax block in the forward kernel
@@ -269,10 +269,6 @@ __device__ inline void store_rows_T(bf16raw* stg, const f32x16 (&acc)[2], float 
 
 // attn_mfma.hip
 bool attn_mfma_eligible(int dtype, int mode, int L, int hd);
-bool attn_small_eligible(int dtype, int mode, int L, int hd);
-int attn_fwd_small_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
-int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                          void* dqkv_cls, hipStream_t st);
 int attn_fwd_mfma_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_mfma_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                          float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);
@@ -286,16 +282,16 @@ bool attn_f32_eligible(int dtype, int L, int hd);
 int attn_fwd_f32_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_f32_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse,
                         float* delta, void* dqkv, void* dqkv_cls, hipStream_t st);
-// attn_hd.hip (head_dim 32, 96, 128)
+// attn_hd.hip (head_dim 32, 96, 128, more than 32 tokens)
 bool attn_hd_eligible(int dtype, int L, int hd);
 int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
 int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
                        void* dqkv, void* dqkv_cls, hipStream_t st);
-// attn_hd.hip, up to 32 tokens (CONTIG, TIME_CLS): the packed kernels
-bool attn_hd_small_eligible(int dtype, int mode, int L, int hd);
-int attn_fwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
-int attn_bwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                             void* dqkv_cls, hipStream_t st);
+// attn_hd.hip, up to 32 tokens (bf16, CONTIG and TIME_CLS, head_dim 32, 64, 96, 128): the packed kernels
+bool attn_small_eligible(int dtype, int mode, int L, int hd);
+int attn_fwd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);
+int attn_bwd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                          void* dqkv_cls, hipStream_t st);
 // attn_hd_f32.hip (fp32, head_dim 32, 96, 128, more than 32 tokens)
 bool attn_hd_f32_eligible(int dtype, int L, int hd);
 int attn_fwd_hd_f32_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st);

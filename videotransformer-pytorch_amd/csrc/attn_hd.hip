@@ -1,5 +1,6 @@
-// attn_hd.hip -- bf16 MFMA attention core for head_dim 32, 96 and 128: more than 32 tokens per sequence in all four layouts
-// (namespace hdim, described here), up to 32 tokens in the layouts CONTIG and TIME_CLS (namespace hdsmall, at the end of the file).
+// attn_hd.hip -- bf16 MFMA attention core over the head dim: more than 32 tokens per sequence at head_dim 32, 96 and 128 in all
+// four layouts (namespace hdim, described here), and the packed kernels for up to 32 tokens in the layouts CONTIG and TIME_CLS at
+// head_dim 32, 64, 96 and 128 (at the end of the file).
 //
 // The structure is the chunk streaming of attn_stream.h (read its header first: transposed scores, a workgroup of 4 waves owns 128
 // queries -- 128 keys in the dk / dv kernel --, the other operands stream through two LDS stages, one barrier per chunk, dk / dv
@@ -34,6 +35,9 @@
 #include "attn_tiles_bf16.h"
 
 namespace vtx {
+// NOTE for whoever edits or moves the hdim kernels: the packed kernels at the end of this file compile to their present registers only
+// with the hdim forward or dq kernel in the same translation unit; without them every attn_bwd_small_kernel comes out at its register cap
+// (32: 90 -> 128), scratch at 64 and 128.  Cause not found: profiles/attn_small_refactor_bench.txt, 3b; test_attn_hd_small_host.py holds scratch at 0.
 namespace hdim {
 
 constexpr int THREADS = 256;
@@ -333,40 +337,91 @@ static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void
 
 }  // namespace hdim
 
+bool attn_hd_eligible(int dtype, int L, int hd) { return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && L > 32; }
+
+int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdim::fwd_launch<32>(p, qkv, out, lse, st);
+    case 96: return hdim::fwd_launch<96>(p, qkv, out, lse, st);
+    case 128: return hdim::fwd_launch<128>(p, qkv, out, lse, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_hd: head_dim %d", hd);
+}
+
+int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
+                       void* dqkv, void* dqkv_cls, hipStream_t st) {
+  switch (hd) {
+    case 32: return hdim::bwd_launch<32>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+    case 96: return hdim::bwd_launch<96>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+    case 128: return hdim::bwd_launch<128>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
+  }
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_hd: head_dim %d", hd);
+}
+
 // =====================================================================================================================
-// Up to 32 tokens, layouts CONTIG and TIME_CLS: the packed formulation of attn_mfma.hip's attn_fwd_small_kernel /
-// attn_bwd_small_kernel (read the comment there), over HD.  G = 32 / L sequences share one 32-row tile under a block-diagonal
-// mask, ONE WAVE handles a (tile, head) pair end to end, row fragments come straight from HBM, the transposed operands sit in
-// wave-private LDS tiles, whole rows are stored through the idle tile, delta is neither read nor written.
-// A wave-private tile is Geo<HD>::NS slabs of the swizzled [32][64] tile (4 KiB at head_dim 32, 8 KiB at 96 and 128; the
-// upper half of the last slab is never written and never read at 32 and 96: a 32-column slab would need a swizzle and readers
-// of its own for 2 KiB a wave).  Forward: one tile (V).  Backward: tile A (K, then Q), tile B (dO) and 32 lse + 32 delta:
-// 8.25 KiB at 32, 16.25 KiB at 96 / 128 -- that is what bounds the waves of a CU there (9 of them in 160 KiB; a workgroup
+// Up to 32 tokens, layouts CONTIG and TIME_CLS, head_dim 32, 64, 96 and 128: the packed kernels (attn_fwd_small_kernel /
+// attn_bwd_small_kernel).  Temporal attention of the divided block (L = T = 8), T + 1 in the space-then-time order, ViViT's
+// temporal encoder (L = 9).  The formulation is the one of attn_mfma.hip (read its header for the transposed scores and the
+// swizzled tiles).
+//
+// G = 32 / L sequences are packed into one 32-row MFMA tile under a block-diagonal mask; ONE WAVE handles a (tile, head) pair end
+// to end: the row fragments come straight from HBM (the row-wise fragment pattern covers the tile exactly once), the transposed
+// operands sit in wave-private LDS tiles, whole rows are stored through the tile that has just gone idle, delta is neither read
+// nor written.  HBM-bound: the forward moves 4 and the backward 8 row-blocks of [rows][HD] per head.
+// A wave-private tile is Bf16Tiles<HD, 64>::NS slabs of the swizzled [32][64] tile (4 KiB at head_dim 32 and 64, 8 KiB at 96
+// and 128; the upper half of the last slab is never written and never read at 32 and 96: a 32-column slab would need a swizzle
+// and readers of its own for 2 KiB a wave).  Forward: one tile (V).  Backward: tile A (K, then Q), tile B (dO) and 32 lse + 32
+// delta: 8.25 KiB at one slab, 16.25 KiB at two -- that is what bounds the waves of a CU there (9 of them in 160 KiB; a workgroup
 // of 4 takes 65 KiB, hence the opt-in), and the register bound follows it: two waves a SIMD, 256 registers.
-// attn_hw_fwd / attn_hw_bwd mean what they mean at head_dim 64 (n heads of a row tile per workgroup, head groups of a tile in
-// consecutive workgroups; 0 = one head, four row tiles), capped at MAXW = 8 waves: at 96 / 128 for the forward's registers and
-// the backward's LDS (D = 768 has 8 and 6 heads there), at 32 because 8 heads measured faster than 16 (temporal forward at 24
-// heads: 0.191 against 0.245 ms, profiles/attn_hd_small_bench.txt).
+//
+// What differs per head dim is Small<HD> and nothing else.  Why head_dim 64 is here and not in a file of the packed kernels: the NOTE at the top.
 // =====================================================================================================================
-namespace hdsmall {
 
-using hdim::Geo;                                  // NS / NK / NT, Frag and store_rows of a head
-template <int HD> using Frag = typename Geo<HD>::Frag;
+// How a lane finds its pieces of a swizzled [32][64] slab.  FragOff (attn_common.h) keeps the 12 per-lane offsets in registers;
+// LaneIdx computes them at each read with the generic readers frag_rows / frag_cols.  The backward at head_dim 64 is bound to
+// four waves a SIMD = 128 registers and has no room for the 12 (profiles/attn_small_refactor_bench.txt, section 3c).
+struct LaneIdx { int lane; };
+__device__ __forceinline__ void make_reader(LaneIdx& r, int lane) { r.lane = lane; }
+__device__ __forceinline__ void make_reader(FragOff& r, int lane) { r = make_frag_off(lane); }
+// element offset of this lane's piece ks of its row (lane & 31)
+__device__ __forceinline__ int row_piece(int ks, const LaneIdx& r) { return sw_off(r.lane & 31, 16 * ks + 8 * (r.lane >> 5)); }
+__device__ __forceinline__ int row_piece(int ks, const FragOff& r) { return r.rows[ks]; }
+__device__ __forceinline__ bf16x8 read_rows(const bf16raw* t, int ks, const LaneIdx& r) { return frag_rows(t, 0, ks, r.lane); }
+__device__ __forceinline__ bf16x8 read_rows(const bf16raw* t, int ks, const FragOff& r) { return frag_rows_o(t, 0, ks, r); }
+__device__ __forceinline__ bf16x8 read_cols(const bf16raw* t, int row0, int n2, const LaneIdx& r) { return frag_cols(t, row0, n2 * 32, r.lane); }
+__device__ __forceinline__ bf16x8 read_cols(const bf16raw* t, int row0, int n2, const FragOff& r) { return frag_cols_o(t, row0, n2, r); }
 
-template <int HD> struct Sm {
-  static constexpr int SLAB = 32 * 64;                                  // elements of one [32][64] slab
-  static constexpr int TILE = Geo<HD>::NS * SLAB;
-  static constexpr int LDS_FWD = TILE * 2;                              // V tile
-  static constexpr int LDS_BWD = 2 * TILE * 2 + 2 * 32 * 4;             // tile A (K, then Q), tile B (dO) + lse + delta
-  static constexpr int MAXW = 8;                                        // waves of a heads-per-workgroup launch
+template <int HD> struct SmallReader { typedef FragOff type; };
+template <> struct SmallReader<64> { typedef LaneIdx type; };
+template <int HD> struct Small {
+  typedef Bf16Tiles<HD, 64> Geo;                                         // NS / NK / NT, Frag and store_rows of a head
+  typedef typename Geo::Frag Frag;
+  typedef typename SmallReader<HD>::type Reader;
+  static constexpr int SLAB = 32 * 64;                                   // elements of one [32][64] slab
+  static constexpr int TILE = Geo::NS * SLAB;
+  static constexpr int LDS_FWD = TILE * 2;                               // V tile
+  static constexpr int LDS_BWD = 2 * TILE * 2 + 2 * 32 * 4;              // tile A (K, then Q), tile B (dO) + lse + delta
+  // Waves of a heads-per-workgroup launch.  8 at 96 / 128 for the forward's registers and the backward's LDS (D = 768 has 8 and
+  // 6 heads there), at 32 because 8 heads measured faster than 16 (profiles/attn_hd_small_bench.txt); 16 at 64 (D = 768: 12 heads).
+  static constexpr int MAXW = HD == 64 ? 16 : 8;
+  static constexpr int BWD_BLOCKS = HD <= 64 ? 4 : 2;                    // minimum workgroups a CU of the four-tile backward
+  // dv and dk fed from one loop, not one accum after the other (same products and order per accumulator): keeps the lse / delta reads whole
+  static constexpr bool PAIRED = HD == 64;
 };
 
-// SmallRows / small_rows of attn_mfma.hip, restated (that file stays as it is).  Tile row j < used belongs to sequence
-// sq = tile * G + j / L, token i = j % L; CLS = VTX_ATTN_TIME_CLS.  grad: row of dqkv, or -1 - (row of dqkv_cls).
-struct Rows { long in, out, grad, lse; };
+// Rows of a packed tile.  Tile row j < used belongs to sequence sq = tile * G + j / L, token i = j % L.  CONTIG: all tensors
+// hold it at row0 + j.  CLS (VTX_ATTN_TIME_CLS, sequence (b, p) = the clip's cls row + T consecutive token rows): qkv holds
+// token i >= 1 at sq * T + b + i and the cls row at b * (1 + P*T); out / dout hold it at sq * T + i - 1, the sequence's cls
+// row behind the B*P*T token rows; the gradient of the gathered cls row goes to dqkv_cls[sq], the P of them of a clip are
+// summed by vtx_cls_qkv_reduce.  lse is [S, H, L] in every layout: index (sq * H + h) * L + i.
+struct SmallRows {
+  long in, out;          // rows of qkv / of out and dout
+  long grad;             // row of dqkv, or -1 - (row of dqkv_cls)
+  long lse;              // sq * H * L + i (without the head)
+};
 template <bool CLS>
-__device__ inline Rows rows_of(const AttnP& p, int tile, int G, int j) {
-  Rows r;
+__device__ inline SmallRows small_rows(const AttnP& p, int tile, int G, int j) {
+  SmallRows r;
   const int L = p.L;
   if (!CLS) {
     const long row = (long)tile * (G * L) + j;
@@ -387,9 +442,9 @@ __device__ inline Rows rows_of(const AttnP& p, int tile, int G, int j) {
 
 // A row's HD columns straight from HBM (an invalid lane reads nothing and holds zeros).
 template <int HD>
-__device__ __forceinline__ void load_frags(Frag<HD>& f, const bf16raw* base, long ld, int col0, long row, bool valid, int lane) {
+__device__ __forceinline__ void load_frags(typename Small<HD>::Frag& f, const bf16raw* base, long ld, int col0, long row, bool valid, int lane) {
 #pragma unroll
-  for (int ks = 0; ks < Geo<HD>::NK; ++ks) {
+  for (int ks = 0; ks < Small<HD>::Geo::NK; ++ks) {
     union { bf16x8 v; uint4 u; } x;
     x.u = make_uint4(0, 0, 0, 0);
     if (valid) x.u = *reinterpret_cast<const uint4*>(base + row * ld + col0 + ks * 16 + 8 * (lane >> 5));
@@ -398,31 +453,35 @@ __device__ __forceinline__ void load_frags(Frag<HD>& f, const bf16raw* base, lon
 }
 // The row fragments of a 32-row tile (one row per lane) into the wave's tile, slab by slab.
 template <int HD>
-__device__ __forceinline__ void put_tile(bf16raw* t, const Frag<HD>& f, const FragOff& fo) {
+__device__ __forceinline__ void put_tile(bf16raw* t, const typename Small<HD>::Frag& f, const typename Small<HD>::Reader& rd) {
 #pragma unroll
-  for (int ks = 0; ks < Geo<HD>::NK; ++ks) *reinterpret_cast<bf16x8*>(t + (ks >> 2) * Sm<HD>::SLAB + fo.rows[ks & 3]) = f.f[ks];
+  for (int ks = 0; ks < Small<HD>::Geo::NK; ++ks) *reinterpret_cast<bf16x8*>(t + (ks >> 2) * Small<HD>::SLAB + row_piece(ks & 3, rd)) = f.f[ks];
 }
 // acc[n][d][j] += sum_i tile[i][32 n + d] c[i][j] over the tile's 32 rows, c = 16 values per lane in accumulator order
 template <int HD>
-__device__ __forceinline__ void accum(f32x16 (&acc)[Geo<HD>::NT], const bf16raw* t, const float* c, const FragOff& fo) {
+__device__ __forceinline__ void accum(f32x16 (&acc)[Small<HD>::Geo::NT], const bf16raw* t, const float* c, const typename Small<HD>::Reader& rd) {
 #pragma unroll
   for (int s2 = 0; s2 < 2; ++s2) {
     const bf16x8 pb = pack8(c + 8 * s2);
 #pragma unroll
-    for (int n = 0; n < Geo<HD>::NT; ++n)
-      acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols_o(t + (n >> 1) * Sm<HD>::SLAB, 16 * s2, n & 1, fo), pb, acc[n], 0, 0, 0);
+    for (int n = 0; n < Small<HD>::Geo::NT; ++n)
+      acc[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_cols(t + (n >> 1) * Small<HD>::SLAB, 16 * s2, n & 1, rd), pb, acc[n], 0, 0, 0);
   }
 }
 
-struct Who {
+struct SmallWho {
   int lane, wave, tile, h;
   bool run;
 };
-// HW: wave w of the workgroup works on head w of its head group, (head group, tile) folded into blockIdx.x, head group fastest;
-// otherwise one head (blockIdx.y) and four row tiles per workgroup.
+// HW (heads in the workgroup): wave w of a workgroup works on head w of ONE row tile's head group, so that the workgroup as a
+// whole reads the tile's rows contiguously at one moment -- instead of one 128-B line out of every row per workgroup, with the
+// other heads' lines of the same rows requested by other CUs at other times.  (head group, tile) is folded into blockIdx.x
+// (grid.y stops at 65535), head group fastest: the groups of a tile are CONSECUTIVE workgroups, they run at the same time and
+// read neighbouring segments of the same rows (temporal backward, 4 heads per workgroup: 356 -> 332 us against tile fastest).
+// Otherwise one head (blockIdx.y) and four row tiles per workgroup.
 template <bool HW>
-__device__ inline Who who(const AttnP& p, int ntiles) {
-  Who w;
+__device__ inline SmallWho small_who(const AttnP& p, int ntiles) {
+  SmallWho w;
   w.lane = threadIdx.x & 63;
   w.wave = threadIdx.x >> 6;
   const int hw_w = blockDim.x >> 6, hw_ng = HW ? (p.H + hw_w - 1) / hw_w : 1;
@@ -433,29 +492,31 @@ __device__ inline Who who(const AttnP& p, int ntiles) {
 }
 
 template <int HD, bool HW, bool CLS>
-__global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS) void fwd_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
-                                                                              bf16raw* __restrict__ out, float* __restrict__ lse) {
-  typedef Geo<HD> G_;
+__global__ __launch_bounds__(HW ? 64 * Small<HD>::MAXW : MA_THREADS) void attn_fwd_small_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
+                                                                                          bf16raw* __restrict__ out, float* __restrict__ lse) {
+  typedef Small<HD> Sm;
+  typedef typename Sm::Geo Geo;
   extern __shared__ __attribute__((aligned(16))) char sm_raw[];
-  const Who w = who<HW>(p, ntiles);
+  const SmallWho w = small_who<HW>(p, ntiles);
   if (!w.run) return;                              // (no workgroup barrier below: a wave is on its own)
   const int lane = w.lane, h = w.h, tile = w.tile, D = p.H * HD;
-  bf16raw* Vs = reinterpret_cast<bf16raw*>(sm_raw + w.wave * Sm<HD>::LDS_FWD);
+  bf16raw* Vs = reinterpret_cast<bf16raw*>(sm_raw + w.wave * Sm::LDS_FWD);
   const int L = p.L, G = 32 / L, used = G * L;
   const long row0 = (long)tile * used, total = (long)p.S * L;
   const int i = lane & 31;
   const bool valid = i < used && row0 + i < total;
-  const Rows me = rows_of<CLS>(p, tile, G, valid ? i : 0);
-  const FragOff fo = make_frag_off(lane);
-  Frag<HD> qf, kf, vf;
+  const SmallRows me = small_rows<CLS>(p, tile, G, valid ? i : 0);
+  typename Sm::Reader rd;
+  make_reader(rd, lane);
+  typename Sm::Frag qf, kf, vf;
   load_frags<HD>(qf, qkv, p.ld_qkv, h * HD, me.in, valid, lane);
   load_frags<HD>(kf, qkv, p.ld_qkv, D + h * HD, me.in, valid, lane);
   load_frags<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, me.in, valid, lane);
-  put_tile<HD>(Vs, vf, fo);
+  put_tile<HD>(Vs, vf, rd);
   f32x16 st;
   zero16(st);
 #pragma unroll
-  for (int ks = 0; ks < G_::NK; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.f[ks], qf.f[ks], st, 0, 0, 0);
+  for (int ks = 0; ks < Geo::NK; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.f[ks], qf.f[ks], st, 0, 0, 0);
   const float c2 = p.scale * LOG2E;
   const int qseq = i / L;
   float m = -INFINITY;
@@ -474,50 +535,53 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS) void fwd_kerne
   for (int r = 0; r < 16; ++r) { pr[r] = __builtin_amdgcn_exp2f(pr[r] - m); l += pr[r]; }
   l += __shfl_xor(l, 32, 64);
   wave_lds_sync();
-  f32x16 acc[G_::NT];
+  f32x16 acc[Geo::NT];
 #pragma unroll
-  for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
-  accum<HD>(acc, Vs, pr, fo);
-  // whole rows through the (now idle) V tile
-  Geo<HD>::store_rows(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
-    return (r < used && row0 + r < total) ? out + rows_of<CLS>(p, tile, G, r).out * p.ld_out + h * HD : nullptr;
+  for (int n = 0; n < Geo::NT; ++n) zero16(acc[n]);
+  accum<HD>(acc, Vs, pr, rd);
+  // whole rows through the (now idle) V tile: a direct store writes 8-byte pieces of 32 different rows per instruction
+  Geo::store_rows(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
+    return (r < used && row0 + r < total) ? out + small_rows<CLS>(p, tile, G, r).out * p.ld_out + h * HD : nullptr;
   });
   if (valid && lane < 32) lse[me.lse + (long)h * L] = m * LN2 + __logf(l);
 }
 
 template <int HD, bool HW, bool CLS>
-__global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD == 32 ? 4 : 2) void bwd_kernel(
+__global__ __launch_bounds__(HW ? 64 * Small<HD>::MAXW : MA_THREADS, HW ? 1 : Small<HD>::BWD_BLOCKS) void attn_bwd_small_kernel(
     AttnP p, int ntiles, const bf16raw* __restrict__ qkv, const bf16raw* __restrict__ o, const bf16raw* __restrict__ dout,
     const float* __restrict__ lse, bf16raw* __restrict__ dqkv, bf16raw* __restrict__ dqkv_cls) {
-  typedef Geo<HD> G_;
+  typedef Small<HD> Sm;
+  typedef typename Sm::Geo Geo;
   extern __shared__ __attribute__((aligned(16))) char sm_raw[];
-  const Who w = who<HW>(p, ntiles);
+  const SmallWho w = small_who<HW>(p, ntiles);
   if (!w.run) return;
   const int lane = w.lane, h = w.h, tile = w.tile, D = p.H * HD;
-  // two wave-private tiles: A holds K for phase 1 (and stages dQ), then Q for phase 2 (and stages dK); B holds dO (and stages dV)
-  char* wl = sm_raw + w.wave * Sm<HD>::LDS_BWD;
+  // two wave-private tiles: A holds K for phase 1 (and stages dQ), then Q for phase 2 (and stages dK); B holds dO (and stages
+  // dV) -- a third of the LDS less than a tile per operand: LDS is what bounds the waves per CU of this kernel
+  char* wl = sm_raw + w.wave * Sm::LDS_BWD;
   bf16raw* Ks = reinterpret_cast<bf16raw*>(wl);
   bf16raw* Qs = Ks;
-  bf16raw* Os = Ks + Sm<HD>::TILE;
-  float* Ls = reinterpret_cast<float*>(Os + Sm<HD>::TILE);
+  bf16raw* Os = Ks + Sm::TILE;
+  float* Ls = reinterpret_cast<float*>(Os + Sm::TILE);
   float* Ds = Ls + 32;
   const int L = p.L, G = 32 / L, used = G * L;
   const long row0 = (long)tile * used, total = (long)p.S * L;
   const int i = lane & 31;
   const bool valid = i < used && row0 + i < total;
-  const Rows me = rows_of<CLS>(p, tile, G, valid ? i : 0);
-  const FragOff fo = make_frag_off(lane);
-  Frag<HD> qf, kf, vf, df;
+  const SmallRows me = small_rows<CLS>(p, tile, G, valid ? i : 0);
+  typename Sm::Reader rd;
+  make_reader(rd, lane);
+  typename Sm::Frag qf, kf, vf, df;
   load_frags<HD>(qf, qkv, p.ld_qkv, h * HD, me.in, valid, lane);
   load_frags<HD>(kf, qkv, p.ld_qkv, D + h * HD, me.in, valid, lane);
   load_frags<HD>(vf, qkv, p.ld_qkv, 2 * D + h * HD, me.in, valid, lane);
   load_frags<HD>(df, dout, p.ld_dout, h * HD, me.out, valid, lane);
   float dl = 0.f;
   {
-    Frag<HD> of;
+    typename Sm::Frag of;
     load_frags<HD>(of, o, p.ld_out, h * HD, me.out, valid, lane);
 #pragma unroll
-    for (int ks = 0; ks < G_::NK; ++ks) dl += frag_dot(df.f[ks], of.f[ks]);
+    for (int ks = 0; ks < Geo::NK; ++ks) dl += frag_dot(df.f[ks], of.f[ks]);
   }
   dl += __shfl_xor(dl, 32, 64);
   float l2 = 1e30f;
@@ -525,11 +589,11 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
   // destination of tile row r's gradient (column origin col of the [3D] row)
   auto dst = [&](int r, int col) -> bf16raw* {
     if (!(r < used && row0 + r < total)) return nullptr;
-    const long g = rows_of<CLS>(p, tile, G, r).grad;
+    const long g = small_rows<CLS>(p, tile, G, r).grad;
     return (CLS && g < 0 ? dqkv_cls + (-1 - g) * p.ld_dqkv : dqkv + g * p.ld_dqkv) + col + h * HD;
   };
-  put_tile<HD>(Ks, kf, fo);
-  put_tile<HD>(Os, df, fo);
+  put_tile<HD>(Ks, kf, rd);
+  put_tile<HD>(Os, df, rd);
   if (lane < 32) { Ls[i] = l2; Ds[i] = dl; }
   const float c2 = p.scale * LOG2E;
   const int myseq = i / L;
@@ -539,7 +603,7 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
     zero16(st);
     zero16(dp);
 #pragma unroll
-    for (int ks = 0; ks < G_::NK; ++ks) {
+    for (int ks = 0; ks < Geo::NK; ++ks) {
       st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf.f[ks], qf.f[ks], st, 0, 0, 0);
       dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf.f[ks], df.f[ks], dp, 0, 0, 0);
     }
@@ -552,25 +616,26 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
       ds[r] = pr * (dp[r] - dl) * p.scale;
     }
     wave_lds_sync();
-    f32x16 acc[G_::NT];
+    f32x16 acc[Geo::NT];
 #pragma unroll
-    for (int n = 0; n < G_::NT; ++n) zero16(acc[n]);
-    accum<HD>(acc, Ks, ds, fo);
+    for (int n = 0; n < Geo::NT; ++n) zero16(acc[n]);
+    accum<HD>(acc, Ks, ds, rd);
     // K tile: its last reader was the MFMA chain above
-    Geo<HD>::store_rows(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
+    Geo::store_rows(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
   }
   // ---- phase 2: lanes = keys.  dV^T = dO^T P, dK^T = Q^T dS.  Only this phase's accumulators are live from here on.
   {
-    put_tile<HD>(Qs, qf, fo);                      // tile A is free again: store_rows above ends with a wave-level sync
+    put_tile<HD>(Qs, qf, rd);                      // tile A is free again: store_rows above ends with a wave-level sync
     wave_lds_sync();
     f32x16 st, dp;
     zero16(st);
     zero16(dp);
 #pragma unroll
-    for (int ks = 0; ks < G_::NK; ++ks) {
+    for (int ks = 0; ks < Geo::NK; ++ks) {
       st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf.f[ks], kf.f[ks], st, 0, 0, 0);
-      // dO row fragments come back from tile B (it holds dO until dv is staged there) instead of living across the two phases
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows_o(Os + (ks >> 2) * Sm<HD>::SLAB, 0, ks & 3, fo), vf.f[ks], dp, 0, 0, 0);
+      // dO row fragments come back from tile B (it holds dO until dv is staged there): kept in registers across the two
+      // phases they cost head_dim 64 its fourth wave a SIMD
+      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_rows(Os + (ks >> 2) * Sm::SLAB, ks & 3, rd), vf.f[ks], dp, 0, 0, 0);
     }
     float pr[16], ds[16];
 #pragma unroll
@@ -589,108 +654,102 @@ __global__ __launch_bounds__(HW ? 64 * Sm<HD>::MAXW : MA_THREADS, HW ? 1 : HD ==
         ds[r] = e * (dp[r] - dvv[j]) * p.scale;
       }
     }
-    f32x16 dk[G_::NT], dv[G_::NT];
+    f32x16 dk[Geo::NT], dv[Geo::NT];
 #pragma unroll
-    for (int n = 0; n < G_::NT; ++n) { zero16(dk[n]); zero16(dv[n]); }
-    accum<HD>(dv, Os, pr, fo);
-    accum<HD>(dk, Qs, ds, fo);
-    Geo<HD>::store_rows(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
-    Geo<HD>::store_rows(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
+    for (int n = 0; n < Geo::NT; ++n) { zero16(dk[n]); zero16(dv[n]); }
+    if constexpr (Sm::PAIRED) {
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        const bf16x8 pb = pack8(pr + 8 * s2);
+        const bf16x8 db = pack8(ds + 8 * s2);
+#pragma unroll
+        for (int n = 0; n < Geo::NT; ++n) {
+          dv[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_cols(Os + (n >> 1) * Sm::SLAB, 16 * s2, n & 1, rd), pb, dv[n], 0, 0, 0);
+          dk[n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(read_cols(Qs + (n >> 1) * Sm::SLAB, 16 * s2, n & 1, rd), db, dk[n], 0, 0, 0);
+        }
+      }
+    } else {
+      accum<HD>(dv, Os, pr, rd);
+      accum<HD>(dk, Qs, ds, rd);
+    }
+    Geo::store_rows(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
+    Geo::store_rows(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
   }
 }
 
 // host side ---------------------------------------------------------------------------------------
-// heads per workgroup: option value n > 0, capped at the head dim's MAXW waves and at H
-template <int HD> static int hw_waves(int n, int H) { n = n < H ? n : H; return n < Sm<HD>::MAXW ? n : Sm<HD>::MAXW; }
+// the two layouts whose packed tile is addressed row by row (small_rows); SPACE and SPACE_NOCLS of up to 32 tokens run elsewhere
+bool attn_small_eligible(int dtype, int mode, int L, int hd) {
+  return dtype == VTX_BF16 && (hd == 32 || hd == 64 || hd == 96 || hd == 128) && (mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_TIME_CLS) &&
+         L >= 1 && L <= 32;
+}
 
-template <int HD, bool CLS>
-static int fwd_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+// Grid, block and dynamic LDS of a launch: hw > 0 heads of a row tile per workgroup (capped at maxw waves and at H), else one head, four tiles
+struct SmallGeom { dim3 grid, block; size_t lds; int ntiles; };
+static SmallGeom small_geom(const AttnP& p, int hw, int maxw, size_t wave_lds) {
   const int G = 32 / p.L;
   const int ntiles = (p.S + G - 1) / G;
-  if (options().attn_hw_fwd > 0) {
-    const int w = hw_waves<HD>(options().attn_hw_fwd, p.H);
-    hipLaunchKernelGGL((fwd_kernel<HD, true, CLS>), dim3((unsigned)cdiv(p.H, w) * ntiles), dim3(64 * w), (size_t)w * Sm<HD>::LDS_FWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (bf16raw*)out, lse);
-  } else {
-    hipLaunchKernelGGL((fwd_kernel<HD, false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * Sm<HD>::LDS_FWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (bf16raw*)out, lse);
-  }
-  return check_launch("attn_fwd_hd_small");
+  if (hw <= 0) return {dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * wave_lds, ntiles};
+  int w = hw < p.H ? hw : p.H;
+  if (w > maxw) w = maxw;
+  return {dim3((unsigned)cdiv(p.H, w) * ntiles), dim3(64 * w), w * wave_lds, ntiles};
 }
-template <int HD, bool CLS>
-static int bwd_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, void* dqkv_cls,
-                      hipStream_t st) {
-  const int G = 32 / p.L;
-  const int ntiles = (p.S + G - 1) / G;
-  if (options().attn_hw_bwd > 0) {
-    const int w = hw_waves<HD>(options().attn_hw_bwd, p.H);
-    const size_t lds = (size_t)w * Sm<HD>::LDS_BWD;
-    allow_lds<bwd_kernel<HD, true, CLS>>(lds);
-    hipLaunchKernelGGL((bwd_kernel<HD, true, CLS>), dim3((unsigned)cdiv(p.H, w) * ntiles), dim3(64 * w), lds, st, p, ntiles, (const bf16raw*)qkv,
-                       (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
-  } else {
-    const size_t lds = (size_t)4 * Sm<HD>::LDS_BWD;
-    allow_lds<bwd_kernel<HD, false, CLS>>(lds);
-    hipLaunchKernelGGL((bwd_kernel<HD, false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), lds, st, p, ntiles, (const bf16raw*)qkv,
-                       (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
-  }
-  return check_launch("attn_bwd_hd_small");
+
+template <int HD, bool HW, bool CLS>
+static int fwd_launch(const AttnP& p, const SmallGeom& g, const void* qkv, void* out, float* lse, hipStream_t st) {
+  hipLaunchKernelGGL((attn_fwd_small_kernel<HD, HW, CLS>), g.grid, g.block, g.lds, st, p, g.ntiles, (const bf16raw*)qkv, (bf16raw*)out, lse);
+  return check_launch("attn_fwd_small");
+}
+template <int HD, bool HW, bool CLS>
+static int bwd_launch(const AttnP& p, const SmallGeom& g, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                      void* dqkv_cls, hipStream_t st) {
+  allow_lds<attn_bwd_small_kernel<HD, HW, CLS>>(g.lds);
+  hipLaunchKernelGGL((attn_bwd_small_kernel<HD, HW, CLS>), g.grid, g.block, g.lds, st, p, g.ntiles, (const bf16raw*)qkv, (const bf16raw*)o,
+                     (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
+  return check_launch("attn_bwd_small");
+}
+
+// the instantiation for the run-time workgroup shape (attn_hw_* > 0: heads of a tile) and layout
+template <int HD>
+static int fwd_launch_hd(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
+  const int hw = options().attn_hw_fwd;
+  const bool cls = p.mode == VTX_ATTN_TIME_CLS;
+  const SmallGeom g = small_geom(p, hw, Small<HD>::MAXW, Small<HD>::LDS_FWD);
+  if (hw > 0) return cls ? fwd_launch<HD, true, true>(p, g, qkv, out, lse, st) : fwd_launch<HD, true, false>(p, g, qkv, out, lse, st);
+  return cls ? fwd_launch<HD, false, true>(p, g, qkv, out, lse, st) : fwd_launch<HD, false, false>(p, g, qkv, out, lse, st);
 }
 template <int HD>
-static int fwd_launch_m(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
-  return p.mode == VTX_ATTN_TIME_CLS ? fwd_launch<HD, true>(p, qkv, out, lse, st) : fwd_launch<HD, false>(p, qkv, out, lse, st);
-}
-template <int HD>
-static int bwd_launch_m(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, void* dqkv_cls,
-                        hipStream_t st) {
-  return p.mode == VTX_ATTN_TIME_CLS ? bwd_launch<HD, true>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st)
-                                     : bwd_launch<HD, false>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
-}
-
-}  // namespace hdsmall
-
-bool attn_hd_eligible(int dtype, int L, int hd) { return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && L > 32; }
-// up to 32 tokens: the two layouts whose packed tile is addressed row by row (rows_of); SPACE and SPACE_NOCLS stay on the VALU kernels
-bool attn_hd_small_eligible(int dtype, int mode, int L, int hd) {
-  return dtype == VTX_BF16 && (hd == 32 || hd == 96 || hd == 128) && (mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_TIME_CLS) && L >= 1 && L <= 32;
+static int bwd_launch_hd(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv, void* dqkv_cls,
+                         hipStream_t st) {
+  const int hw = options().attn_hw_bwd;
+  const bool cls = p.mode == VTX_ATTN_TIME_CLS;
+  const SmallGeom g = small_geom(p, hw, Small<HD>::MAXW, Small<HD>::LDS_BWD);
+  if (hw > 0)
+    return cls ? bwd_launch<HD, true, true>(p, g, qkv, o, dout, lse, dqkv, dqkv_cls, st)
+               : bwd_launch<HD, true, false>(p, g, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+  return cls ? bwd_launch<HD, false, true>(p, g, qkv, o, dout, lse, dqkv, dqkv_cls, st)
+             : bwd_launch<HD, false, false>(p, g, qkv, o, dout, lse, dqkv, dqkv_cls, st);
 }
 
-int attn_fwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
+int attn_fwd_small_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
   switch (hd) {
-    case 32: return hdsmall::fwd_launch_m<32>(p, qkv, out, lse, st);
-    case 96: return hdsmall::fwd_launch_m<96>(p, qkv, out, lse, st);
-    case 128: return hdsmall::fwd_launch_m<128>(p, qkv, out, lse, st);
+    case 32: return fwd_launch_hd<32>(p, qkv, out, lse, st);
+    case 64: return fwd_launch_hd<64>(p, qkv, out, lse, st);
+    case 96: return fwd_launch_hd<96>(p, qkv, out, lse, st);
+    case 128: return fwd_launch_hd<128>(p, qkv, out, lse, st);
   }
-  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_hd_small: head_dim %d", hd);
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_small: head_dim %d", hd);
 }
 
-int attn_bwd_hd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                             void* dqkv_cls, hipStream_t st) {
+int attn_bwd_small_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
+                          void* dqkv_cls, hipStream_t st) {
   switch (hd) {
-    case 32: return hdsmall::bwd_launch_m<32>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
-    case 96: return hdsmall::bwd_launch_m<96>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
-    case 128: return hdsmall::bwd_launch_m<128>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 32: return bwd_launch_hd<32>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 64: return bwd_launch_hd<64>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 96: return bwd_launch_hd<96>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
+    case 128: return bwd_launch_hd<128>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
   }
-  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_hd_small: head_dim %d", hd);
-}
-
-int attn_fwd_hd_launch(const AttnP& p, int hd, const void* qkv, void* out, float* lse, hipStream_t st) {
-  switch (hd) {
-    case 32: return hdim::fwd_launch<32>(p, qkv, out, lse, st);
-    case 96: return hdim::fwd_launch<96>(p, qkv, out, lse, st);
-    case 128: return hdim::fwd_launch<128>(p, qkv, out, lse, st);
-  }
-  VTX_REQUIRE(false, VTX_EINVAL, "attn_fwd_hd: head_dim %d", hd);
-}
-
-int attn_bwd_hd_launch(const AttnP& p, int hd, const void* qkv, const void* o, const void* dout, const float* lse, float* delta,
-                       void* dqkv, void* dqkv_cls, hipStream_t st) {
-  switch (hd) {
-    case 32: return hdim::bwd_launch<32>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
-    case 96: return hdim::bwd_launch<96>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
-    case 128: return hdim::bwd_launch<128>(p, qkv, o, dout, lse, delta, dqkv, dqkv_cls, st);
-  }
-  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_hd: head_dim %d", hd);
+  VTX_REQUIRE(false, VTX_EINVAL, "attn_bwd_small: head_dim %d", hd);
 }
 
 }  // namespace vtx

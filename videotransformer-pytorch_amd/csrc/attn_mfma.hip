@@ -30,7 +30,8 @@
 // Layout of this file: the tile arithmetic first, each body ONCE (fwd_query_tile, score_pair, dq_ds / dq_mask_keys /
 // dq_accumulate, dkv_probs / dkv_accumulate, row_delta, the destination rows, the LDS-DMA request); then the kernels, which
 // own the schedules -- workgroup per item (forward, dq, dk / dv), one pass (attn_bwd_fused_mfma_kernel), streamed
-// (attn_bwd_stream_mfma_kernel, attn_fwd_stream_mfma_kernel) -- and call those bodies; then the short-sequence kernels.
+// (attn_bwd_stream_mfma_kernel, attn_fwd_stream_mfma_kernel) -- and call those bodies.  The packed kernels for up to 32 tokens
+// (attn_fwd_small_kernel / attn_bwd_small_kernel) are at the end of attn_hd.hip, written once for every head dim.
 #include "attn_common.h"
 
 namespace vtx {
@@ -220,9 +221,9 @@ __device__ inline bf16raw* dq_dst_row(const AttnP& p, int s, int h, const RowLin
 // (Why the requests are inline asm: the wave-7 comment of attn_bwd_stream_mfma_kernel.)
 typedef __attribute__((address_space(3))) char lds_char;
 // The lane's constants: its row of 8 and its source chunk (elements) for even / odd G.  A kernel forms them ONCE, in its own
-// body and not inside a lambda: sw_of and crow are shared with the short-sequence kernels, and with `lane` reaching sw_of
-// through a closure the compiler no longer knows its range in ANY caller -- attn_bwd_small_kernel then compiled to 128
-// registers + 30 spilled (124 and none before).
+// body and not inside a lambda: with `lane` reaching sw_of through a closure the compiler no longer knows its range in ANY
+// caller of sw_of and crow (seen when the packed kernels, now in attn_hd.hip, were in this file: attn_bwd_small_kernel went
+// from 124 registers to 128 + 30 spilled).
 struct DmaLane { int rl8, swz[2]; };
 __device__ inline DmaLane dma_lane(int lane) {
   const int rl8 = lane >> 3, pc = lane & 7;
@@ -260,19 +261,6 @@ __device__ inline void dma_rows8(const DmaSrc& x, int G, bf16raw* dst, const Dma
     asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen lds" ::"v"(voff), "s"(x.desc), "s"(soff), "s"(m0v)
                  : "memory", "m0");
   }
-}
-
-// Direct variant (8-byte pieces, no staging) for the packed short-sequence kernels below.
-__device__ inline void store_rows_direct(bf16raw* dst_row, const f32x16 (&acc)[2], float mul, int lane) {
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      union { bf16x4 v; uint2 u; } w;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) w.v[j] = (__bf16)(acc[nt][4 * g + j] * mul);
-      *reinterpret_cast<uint2*>(dst_row + nt * 32 + 8 * g + 4 * (lane >> 5)) = w.u;
-    }
 }
 
 // ------------------------------------------------------------------------------ forward
@@ -1207,314 +1195,16 @@ __global__ __launch_bounds__(MF_THREADS, 1) void attn_fwd_stream_mfma_kernel(Att
   mg_barrier();
 }
 
-// =====================================================================================
-// Short sequences (L <= 32, contiguous rows): temporal attention of the divided block
-// (L = T = 8) and ViViT's temporal encoder (L = 9).  G = 32/L sequences are packed into one
-// 32-row MFMA tile (block-diagonal mask); ONE WAVE handles a (tile, head) pair end to end, with
-// operands loaded straight from HBM into MFMA fragments (the row-wise fragment pattern covers
-// the [32][64] tile exactly once) and a wave-private 4 KB LDS tile per transposed operand.
-// HBM-bound: forward moves 4 and backward 8 row-blocks of [rows][64] per head.
-// =====================================================================================
-constexpr int SM_WAVE_LDS_FWD = 32 * 64 * 2;                   // V tile
-constexpr int SM_WAVE_LDS_BWD = 2 * 32 * 64 * 2 + 2 * 32 * 4;   // tile A (K, then Q), tile B (dO) + lse + delta
-
-__device__ inline void load_frags(bf16x8 (&f)[4], const bf16raw* base, long ld, int col0, long row, bool valid, int lane) {
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    union { bf16x8 v; uint4 u; } x;
-    x.u = make_uint4(0, 0, 0, 0);
-    if (valid) x.u = *reinterpret_cast<const uint4*>(base + row * ld + col0 + ks * 16 + 8 * (lane >> 5));
-    f[ks] = x.v;
-  }
-}
-
-// Rows of a packed tile.  Tile row j < used belongs to sequence sq = tile * G + j / L, token i = j % L.  CONTIG: all tensors
-// hold it at row0 + j.  CLS (VTX_ATTN_TIME_CLS, sequence (b, p) = the clip's cls row + T consecutive token rows): qkv holds
-// token i >= 1 at sq * T + b + i and the cls row at b * (1 + P*T); out / dout hold it at sq * T + i - 1, the sequence's cls
-// row behind the B*P*T token rows; the gradient of the gathered cls row goes to dqkv_cls[sq], the P of them of a clip are
-// summed by vtx_cls_qkv_reduce.  lse / delta are [S, H, L] in every layout: index (sq * H + h) * L + i.
-template <bool CLS> struct SmallRows {
-  long in, out;          // rows of qkv / of out and dout
-  long grad;             // row of dqkv, or -1 - (row of dqkv_cls)
-  long lse;              // sq * H * L + i (without the head)
-};
-template <bool CLS>
-__device__ inline SmallRows<CLS> small_rows(const AttnP& p, int tile, int G, int j) {
-  SmallRows<CLS> r;
-  const int L = p.L;
-  if (!CLS) {
-    const long row = (long)tile * (G * L) + j;
-    const long sq = row / L;
-    r.in = r.out = r.grad = row;
-    r.lse = sq * p.H * L + (row - sq * L);
-    return r;
-  }
-  const int g = j / L, i = j - g * L;
-  const long sq = (long)tile * G + g;
-  const long b = sq / p.P;
-  r.in = i == 0 ? b * (1 + (long)p.P * p.T) : sq * p.T + b + i;
-  r.out = i == 0 ? (long)p.B * p.P * p.T + sq : sq * p.T + (i - 1);
-  r.grad = i == 0 ? -1 - sq : r.in;
-  r.lse = sq * p.H * L + i;
-  return r;
-}
-
-// HW (heads in the workgroup): wave w of a workgroup works on head w of ONE row tile, so that the workgroup as a whole
-// reads the tile's rows contiguously (32 x 3 H x 128 B) at one moment -- instead of one 128-B line out of every
-// 4.6 KB row per workgroup, with the other heads' lines of the same rows requested by other CUs at other times.
-template <bool HW, bool CLS>
-__global__ __launch_bounds__(HW ? 1024 : MA_THREADS) void attn_fwd_small_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
-                                                                    bf16raw* __restrict__ out, float* __restrict__ lse) {
-  extern __shared__ __attribute__((aligned(16))) char sm_raw[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // HW: the head groups of a row tile are CONSECUTIVE workgroups (blockIdx.x = head group): they run at the same time and read
-  // neighbouring 128-byte segments of the same rows -- with the tile index fastest the groups of one tile were a whole grid row
-  // apart (temporal backward, 4 heads per workgroup: 356 -> 332 us)
-  // (head group, tile) folded into blockIdx.x, head group fastest -- grid.y stops at 65535 tiles, grid.x at 2^31
-  const int hw_w = blockDim.x >> 6, hw_ng = HW ? (p.H + hw_w - 1) / hw_w : 1;
-  const int tile = HW ? (int)(blockIdx.x / hw_ng) : blockIdx.x * 4 + wave, h = HW ? wave + (int)(blockIdx.x % hw_ng) * hw_w : blockIdx.y, D = p.H * 64;
-  if (tile >= ntiles || h >= p.H) return;
-  bf16raw* Vs = reinterpret_cast<bf16raw*>(sm_raw + wave * SM_WAVE_LDS_FWD);
-  const int L = p.L, G = 32 / L, used = G * L;
-  const long row0 = (long)tile * used, total = (long)p.S * L;
-  const int i = lane & 31;
-  const bool valid = i < used && row0 + i < total;
-  const SmallRows<CLS> me = small_rows<CLS>(p, tile, G, valid ? i : 0);
-  bf16x8 qf[4], kf[4], vf[4];
-  load_frags(qf, qkv, p.ld_qkv, h * 64, me.in, valid, lane);
-  load_frags(kf, qkv, p.ld_qkv, D + h * 64, me.in, valid, lane);
-  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, me.in, valid, lane);
-  put_tile(Vs, vf, lane);
-  f32x16 st;
-  zero16(st);
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
-  const float c2 = p.scale * LOG2E;
-  const int qseq = i / L;
-  float m = -INFINITY;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int key = crow(r, lane);
-    const bool ok = valid && key < used && key / L == qseq && row0 + key < total;
-    st[r] = ok ? st[r] * c2 : -INFINITY;
-    m = fmaxf(m, st[r]);
-  }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  if (!valid) m = 0.f;
-  float l = 0.f;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { st[r] = __builtin_amdgcn_exp2f(st[r] - m); l += st[r]; }
-  l += __shfl_xor(l, 32, 64);
-  wave_lds_sync();
-  f32x16 acc[2];
-  zero16(acc[0]);
-  zero16(acc[1]);
-#pragma unroll
-  for (int s2 = 0; s2 < 2; ++s2) {
-    float pf[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pf[j] = st[8 * s2 + j];
-    const bf16x8 pb = pack8(pf);
-#pragma unroll
-    for (int n2 = 0; n2 < 2; ++n2)
-      acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Vs, 16 * s2, n2 * 32, lane), pb, acc[n2], 0, 0, 0);
-  }
-  // whole 128-B rows through the (now idle) V tile: the direct store writes 8-byte pieces of 32 different rows per
-  // instruction, and the vector memory pipeline handles those one line at a time
-  store_rows_T(Vs, acc, valid ? 1.0f / l : 0.f, lane, [&](int r) -> bf16raw* {
-    return (r < used && row0 + r < total) ? out + small_rows<CLS>(p, tile, G, r).out * p.ld_out + h * 64 : nullptr;
-  });
-  if (valid && lane < 32) lse[me.lse + (long)h * L] = m * LN2 + __logf(l);
-}
-
-template <bool HW, bool CLS>
-__global__ __launch_bounds__(HW ? 1024 : MA_THREADS, HW ? 1 : 4) void attn_bwd_small_kernel(AttnP p, int ntiles, const bf16raw* __restrict__ qkv,
-                                                                    const bf16raw* __restrict__ o, const bf16raw* __restrict__ dout,
-                                                                    const float* __restrict__ lse, bf16raw* __restrict__ dqkv,
-                                                                    bf16raw* __restrict__ dqkv_cls) {
-  extern __shared__ __attribute__((aligned(16))) char sm_raw[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // HW: the head groups of a row tile are CONSECUTIVE workgroups (blockIdx.x = head group): they run at the same time and read
-  // neighbouring 128-byte segments of the same rows -- with the tile index fastest the groups of one tile were a whole grid row
-  // apart (temporal backward, 4 heads per workgroup: 356 -> 332 us)
-  // (head group, tile) folded into blockIdx.x, head group fastest -- grid.y stops at 65535 tiles, grid.x at 2^31
-  const int hw_w = blockDim.x >> 6, hw_ng = HW ? (p.H + hw_w - 1) / hw_w : 1;
-  const int tile = HW ? (int)(blockIdx.x / hw_ng) : blockIdx.x * 4 + wave, h = HW ? wave + (int)(blockIdx.x % hw_ng) * hw_w : blockIdx.y, D = p.H * 64;
-  if (tile >= ntiles || h >= p.H) return;
-  // two wave-private tiles: A holds K for phase 1 (and stages dQ), then Q for phase 2 (and stages dK); B holds dO
-  // (and stages dV) -- 8.25 KB per wave instead of 12.25 KB: LDS is what bounds the waves per CU of this kernel
-  char* wl = sm_raw + wave * SM_WAVE_LDS_BWD;
-  bf16raw* Ks = reinterpret_cast<bf16raw*>(wl);
-  bf16raw* Qs = Ks;
-  bf16raw* Os = Ks + 32 * 64;
-  float* Ls = reinterpret_cast<float*>(Os + 32 * 64);
-  float* Ds = Ls + 32;
-  const int L = p.L, G = 32 / L, used = G * L;
-  const long row0 = (long)tile * used, total = (long)p.S * L;
-  const int i = lane & 31;
-  const bool valid = i < used && row0 + i < total;
-  const SmallRows<CLS> me = small_rows<CLS>(p, tile, G, valid ? i : 0);
-  bf16x8 qf[4], kf[4], vf[4], df[4];
-  load_frags(qf, qkv, p.ld_qkv, h * 64, me.in, valid, lane);
-  load_frags(kf, qkv, p.ld_qkv, D + h * 64, me.in, valid, lane);
-  load_frags(vf, qkv, p.ld_qkv, 2 * D + h * 64, me.in, valid, lane);
-  load_frags(df, dout, p.ld_dout, h * 64, me.out, valid, lane);
-  float dl = 0.f;
-  {
-    bf16x8 of[4];
-    load_frags(of, o, p.ld_out, h * 64, me.out, valid, lane);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) dl += frag_dot(df[ks], of[ks]);
-  }
-  dl += __shfl_xor(dl, 32, 64);
-  float l2 = 1e30f;
-  if (valid) l2 = lse[me.lse + (long)h * L] * LOG2E;
-  // destination of tile row r's gradient (column origin col of the [3D] row)
-  auto dst = [&](int r, int col) -> bf16raw* {
-    if (!(r < used && row0 + r < total)) return nullptr;
-    const long g = small_rows<CLS>(p, tile, G, r).grad;
-    return (CLS && g < 0 ? dqkv_cls + (-1 - g) * p.ld_dqkv : dqkv + g * p.ld_dqkv) + col + h * 64;
-  };
-  put_tile(Ks, kf, lane);
-  put_tile(Os, df, lane);
-  if (lane < 32) { Ls[i] = l2; Ds[i] = dl; }
-  const float c2 = p.scale * LOG2E;
-  const int myseq = i / L;
-  // ---- phase 1: lanes = queries.  dQ^T = K^T dS^T
-  {
-    f32x16 st, dp;
-    zero16(st);
-    zero16(dp);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], st, 0, 0, 0);
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ks], df[ks], dp, 0, 0, 0);
-    }
-    float ds[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int key = crow(r, lane);
-      const bool ok = valid && key < used && key / L == myseq && row0 + key < total;
-      const float pr = ok ? __builtin_amdgcn_exp2f(st[r] * c2 - l2) : 0.f;
-      ds[r] = pr * (dp[r] - dl) * p.scale;
-    }
-    wave_lds_sync();
-    f32x16 acc[2];
-    zero16(acc[0]);
-    zero16(acc[1]);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-      for (int n2 = 0; n2 < 2; ++n2)
-        acc[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Ks, 16 * s2, n2 * 32, lane), db, acc[n2], 0, 0, 0);
-    }
-    // K tile: its last reader was the MFMA chain above
-    store_rows_T(Ks, acc, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 0); });
-  }
-  // ---- phase 2: lanes = keys.  dV^T = dO^T P, dK^T = Q^T dS
-  {
-    put_tile(Qs, qf, lane);                        // tile A is free again: store_rows_T above ends with a wave-level sync
-    wave_lds_sync();
-    f32x16 st, dp;
-    zero16(st);
-    zero16(dp);
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf[ks], kf[ks], st, 0, 0, 0);
-      // dO row fragments come back from tile B (it holds dO until dv is staged there): kept in registers across the two phases they
-      // put the kernel at 138 registers = three waves per SIMD instead of four (124 now: 415 -> 393 us at 96 clips)
-      dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_rows(Os, 0, ks, lane), vf[ks], dp, 0, 0, 0);
-    }
-    float pr[16], ds[16];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const int qrow = 8 * g + 4 * (lane >> 5);
-      const float4 l4 = *reinterpret_cast<const float4*>(Ls + qrow);
-      const float4 d4 = *reinterpret_cast<const float4*>(Ds + qrow);
-      const float lv[4] = {l4.x, l4.y, l4.z, l4.w}, dvv[4] = {d4.x, d4.y, d4.z, d4.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int r = 4 * g + j;
-        const int q = qrow + j;
-        const bool ok = valid && q < used && q / L == myseq;
-        const float e = ok ? __builtin_amdgcn_exp2f(st[r] * c2 - lv[j]) : 0.f;
-        pr[r] = e;
-        ds[r] = e * (dp[r] - dvv[j]) * p.scale;
-      }
-    }
-    f32x16 dk[2], dv[2];
-    zero16(dk[0]); zero16(dk[1]); zero16(dv[0]); zero16(dv[1]);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const bf16x8 pb = pack8(pr + 8 * s2);
-      const bf16x8 db = pack8(ds + 8 * s2);
-#pragma unroll
-      for (int n2 = 0; n2 < 2; ++n2) {
-        dv[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Os, 16 * s2, n2 * 32, lane), pb, dv[n2], 0, 0, 0);
-        dk[n2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_cols(Qs, 16 * s2, n2 * 32, lane), db, dk[n2], 0, 0, 0);
-      }
-    }
-    store_rows_T(Qs, dk, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, D); });
-    store_rows_T(Os, dv, 1.0f, lane, [&](int r) -> bf16raw* { return dst(r, 2 * D); });
-  }
-}
-
 // host-side launchers used by attn.hip's entry points --------------------------------------
 // 33..256 tokens; and the one layout of up to 32 tokens that the packed kernels do not take: SPACE_NOCLS (rows of a sequence
 // T apart, so a 32-row tile of packed sequences is not a run of consecutive rows) runs here at one tile per sequence
 bool attn_mfma_eligible(int dtype, int mode, int L, int hd) {
   return dtype == VTX_BF16 && hd == 64 && L <= 32 * MA_MAXT && (L > 32 || (mode == VTX_ATTN_SPACE_NOCLS && L >= 1));
 }
-bool attn_small_eligible(int dtype, int mode, int L, int hd) {
-  return dtype == VTX_BF16 && hd == 64 && (mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_TIME_CLS) && L >= 1 && L <= 32;
-}
 // The persistent 7-tile kernels (attn_fwd_stream_mfma_kernel / attn_bwd_stream_mfma_kernel) address rows through mg_lin_in /
 // mg_lin_out, which know the two layouts of the default operator order; the other layouts of 193..224 tokens (SPACE_NOCLS at
 // 196) run the one-workgroup-per-(sequence, head) kernels, whose addressing is lin_in / lin_out.
 static bool mg_mode(int mode) { return mode == VTX_ATTN_CONTIG || mode == VTX_ATTN_SPACE; }
-// heads per workgroup in the HW variants: option value n > 0, capped at 16 waves (1024 threads) and at H
-static int hw_waves(int n, int H) { n = n < H ? n : H; return n < 16 ? n : 16; }
-
-template <bool CLS>
-static int attn_fwd_small_launch_t(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
-  const int G = 32 / p.L;
-  const int ntiles = (p.S + G - 1) / G;
-  if (options().attn_hw_fwd > 0) {
-    const int w = hw_waves(options().attn_hw_fwd, p.H);
-    hipLaunchKernelGGL((attn_fwd_small_kernel<true, CLS>), dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), w * SM_WAVE_LDS_FWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (bf16raw*)out, lse);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_small_kernel<false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_FWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (bf16raw*)out, lse);
-  }
-  return check_launch("attn_fwd_small");
-}
-int attn_fwd_small_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
-  return p.mode == VTX_ATTN_TIME_CLS ? attn_fwd_small_launch_t<true>(p, qkv, out, lse, st) : attn_fwd_small_launch_t<false>(p, qkv, out, lse, st);
-}
-template <bool CLS>
-static int attn_bwd_small_launch_t(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                                   void* dqkv_cls, hipStream_t st) {
-  const int G = 32 / p.L;
-  const int ntiles = (p.S + G - 1) / G;
-  if (options().attn_hw_bwd > 0) {
-    const int w = hw_waves(options().attn_hw_bwd, p.H);
-    const size_t lds = (size_t)w * SM_WAVE_LDS_BWD;
-    allow_lds<attn_bwd_small_kernel<true, CLS>>(lds);
-    hipLaunchKernelGGL((attn_bwd_small_kernel<true, CLS>), dim3(((p.H + w - 1) / w) * ntiles), dim3(64 * w), lds, st, p, ntiles,
-                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
-  } else {
-    hipLaunchKernelGGL((attn_bwd_small_kernel<false, CLS>), dim3((ntiles + 3) / 4, p.H), dim3(MA_THREADS), 4 * SM_WAVE_LDS_BWD, st, p, ntiles,
-                       (const bf16raw*)qkv, (const bf16raw*)o, (const bf16raw*)dout, lse, (bf16raw*)dqkv, (bf16raw*)dqkv_cls);
-  }
-  return check_launch("attn_bwd_small");
-}
-int attn_bwd_small_launch(const AttnP& p, const void* qkv, const void* o, const void* dout, const float* lse, void* dqkv,
-                          void* dqkv_cls, hipStream_t st) {
-  return p.mode == VTX_ATTN_TIME_CLS ? attn_bwd_small_launch_t<true>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st)
-                                     : attn_bwd_small_launch_t<false>(p, qkv, o, dout, lse, dqkv, dqkv_cls, st);
-}
 
 int attn_fwd_mfma_launch(const AttnP& p, const void* qkv, void* out, float* lse, hipStream_t st) {
   const int nt = (p.L + 31) >> 5, Lp = nt * 32;

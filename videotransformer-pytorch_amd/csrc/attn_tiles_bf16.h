@@ -10,7 +10,7 @@
 //   no padded products: the half-used slab costs LDS, not matrix instructions.
 // One operand of a chunk is NS slabs of CHUNK rows, a stage holds two operands.  attn_long.hip is Bf16Tiles<64, 128> under the
 // bodies of attn_stream.h; attn_hd.hip is Bf16Tiles<HD, 64> at head_dim 32, 96 and 128 under its own three bodies (its header
-// says why), and its packed kernels (namespace hdsmall) take Frag, the slab counts and store_rows from here.
+// says why), and its packed kernels for up to 32 tokens (head_dim 64 among them) take Frag, the slab counts and store_rows from here.
 #pragma once
 #include "attn_stream.h"
 
